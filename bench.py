@@ -29,6 +29,9 @@ steps, the algorithmic and physical roofline fractions, the kernels as the libra
 baseline of the oracle's C port (oracle/baselines.py).  Each entry runs under its own deadline; none can lose
 the headline.  The whole default run takes under a minute.
 
+--dump-outputs DIR writes, after the timed steps, the fields the timed path leaves a caller (u1, s1; a fixed seeded sample of
+cells, plus norms over the whole block) as DIR/<name>.npy (dump_outputs), so that two builds can be compared output for output.
+
 Watchdogs: every rank arms faulthandler.dump_traceback_later(--timeout): a rank that hangs in init or in an exchange
 dumps its stacks and exits non-zero; the self-launching parent (which never touches a GPU) additionally kills the
 child process group --timeout + 30 s after starting it.
@@ -301,6 +304,46 @@ def measure(elastic, args, comm, steps, warmup):
                 ranks=int(round(sum(comm.gather(1.0)))))
 
 
+DUMP_BYTES = 48 << 20      # --dump-outputs: all ranks' files together stay under 64 MB
+
+
+def dump_outputs(blk, outdir, rank, world, seed=0):
+    """--dump-outputs DIR: what the timed path leaves a caller (ElasticLF4.run returns u1, s1) after its last step.
+    Fields larger than the budget are sampled: a fixed, seeded, sorted set of cells, the same from run to run.
+      u1.npy  [k, nd, d]     velocity at the sampled cells        s1.npy  [k, nd, d, d]  stress at the sampled cells
+      cells.npy [k]          the sampled cell indices (block-local)
+      field_norms.npy [4]    over the WHOLE block: ||u1||_2, ||s1||_2, max |u1|, max |s1| (nodal values)
+    float64; with more than one rank every name carries _rank<r>."""
+    from seigen_amd import _lib
+    os.makedirs(outdir, exist_ok=True)
+    nc = blk.ncells
+    shapes = [blk.field_shape(f)[1:] for f in (_lib.FIELD_U, _lib.FIELD_S)]
+    per_cell = 8 * sum(int(np.prod(s)) for s in shapes) + 8
+    k = min(nc, DUMP_BYTES // max(world, 1) // per_cell)
+    if k == nc:
+        cells = np.arange(nc)
+        u, s = blk.get_field(_lib.FIELD_U), blk.get_field(_lib.FIELD_S)
+    else:
+        cells = np.sort(np.random.default_rng(seed).choice(nc, size=k, replace=False))
+        u = np.empty((k,) + shapes[0])
+        s = np.empty((k,) + shapes[1])
+        for i, c in enumerate(cells):
+            blk.get_field_range(_lib.FIELD_U, int(c), 1, out=u[i:i + 1])
+            blk.get_field_range(_lib.FIELD_S, int(c), 1, out=s[i:i + 1])
+    sq = [0.0, 0.0]
+    mx = [0.0, 0.0]
+    chunk = 16384
+    for j, f in enumerate((_lib.FIELD_U, _lib.FIELD_S)):
+        for c0 in range(0, nc, chunk):
+            a = blk.get_field_range(f, c0, min(chunk, nc - c0))
+            sq[j] += float(np.dot(a.ravel(), a.ravel()))
+            mx[j] = max(mx[j], float(np.abs(a).max()))
+    sfx = "_rank%d" % rank if world > 1 else ""
+    for name, arr in (("u1", u), ("s1", s), ("cells", cells.astype(np.float64)),
+                      ("field_norms", np.array([math.sqrt(sq[0]), math.sqrt(sq[1]), mx[0], mx[1]]))):
+        np.save(os.path.join(outdir, name + sfx + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+
 def stage_accounting(dim, sym):
     """Words per node and STAGE (UH1 STEMP U1 SH1 UTEMP S1): algorithmic (every input of the stage read once, every output
     written once, d x d stress) and what the kernels physically move when the stress is stored symmetric (d (d + 1) / 2
@@ -488,7 +531,13 @@ def main():
     ap.add_argument("--config-timeout", type=float, default=75.0, help="deadline of each entry of --configs, seconds")
     ap.add_argument("--timeout", type=float, default=900.0,
                     help="seconds after which a rank that has not finished dumps its stacks and exits non-zero")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the headline's fields (u1, s1; a fixed seeded sample of cells) "
+                         "as DIR/<name>.npy, float64, under 64 MB in all; give --steps for outputs comparable between runs")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps is None:
+        print("bench.py: --dump-outputs without --steps: the step count follows the measured rate, so the outputs "
+              "will not be comparable between runs", file=sys.stderr)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args.gpus, args.timeout)      # never returns
@@ -546,6 +595,8 @@ def main():
     n = args.n
     m = measure(elastic, args, comm, args.steps, args.warmup)
     args.steps = m["steps"]
+    if args.dump_outputs:
+        dump_outputs(blk, args.dump_outputs, rank, world)
     elapsed, c0, c1, ranks_reporting = m["elapsed"], m["c0"], m["c1"], m["ranks"]
 
     d = 3

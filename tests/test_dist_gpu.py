@@ -231,3 +231,35 @@ def test_bench_line_config4_share_variants_and_degree_comparison(gpu):
     assert "error" not in p1, p1
     assert p1["degree"] == 1 and p1["steps"] == 1024 and p1["cells"] == 2 * 256 * 256 and "22-31" in p1["workload"]
     assert p1["u_error"] < 1e-2 and 0 < p1["roofline"]["frac_physical"] < p1["roofline"]["frac"] < 1
+
+
+def test_bench_dump_outputs(gpu, tmp_path):
+    """`bench.py --dump-outputs DIR`: the fields the timed path leaves after exactly --steps timed steps, as float64 .npy
+    files under 64 MB - bitwise the same from run to run (a 16^3-cube block, sampled), and the whole block when it fits
+    (8^3 cubes), whose norms must then be those of the dumped fields."""
+    def run(n, d):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--n", str(n), "--steps", "3", "--warmup", "1",
+                            "--no-cpu-baseline", "--configs", "none", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, cwd=ROOT, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0
+        names = ("u1", "s1", "cells", "field_norms")
+        assert sorted(os.listdir(str(d))) == sorted(k + ".npy" for k in names)
+        assert sum(os.path.getsize(str(d / (k + ".npy"))) for k in names) < 64 << 20
+        arrs = {k: np.load(str(d / (k + ".npy"))) for k in names}
+        assert all(a.dtype == np.float64 for a in arrs.values())
+        return out, arrs
+
+    out_a, a = run(16, tmp_path / "a")
+    _, b = run(16, tmp_path / "b")
+    cells = out_a["config"]["cells"]
+    assert cells == 6 * 16 ** 3 and 1000 < len(a["cells"]) < cells
+    assert a["u1"].shape == (len(a["cells"]), 35, 3) and a["s1"].shape == (len(a["cells"]), 35, 3, 3)
+    assert np.isfinite(a["u1"]).all() and np.abs(a["u1"]).max() > 0 and np.abs(a["s1"]).max() > 0
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    _, w = run(8, tmp_path / "whole")
+    assert np.array_equal(w["cells"], np.arange(6 * 8 ** 3))
+    want = [np.linalg.norm(w["u1"].ravel()), np.linalg.norm(w["s1"].ravel()), np.abs(w["u1"]).max(), np.abs(w["s1"]).max()]
+    np.testing.assert_allclose(w["field_norms"], want, rtol=1e-12)

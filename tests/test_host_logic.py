@@ -507,6 +507,49 @@ def test_traffic_digest_follows_the_kernel_sources(tmp_path):
     assert len(d) == 64 and d == bench.csrc_digest()
 
 
+def test_bench_dump_outputs_samples_within_budget(tmp_path):
+    """bench.py --dump-outputs: a block too large to write whole is sampled - the same seeded cells every time, values
+    exactly the block's at those cells, whole-block norms, float64, all ranks' files together under 64 MB."""
+    import bench
+    from seigen_amd import _lib
+
+    class Block(object):              # 24^3 cubes x 6 tets, P4 (35 nodes): larger than the budget
+        ncells, nd, dim = 6 * 24 ** 3, 35, 3
+
+        def field_shape(self, f):
+            return (self.ncells, self.nd, 3, 3) if f == _lib.FIELD_S else (self.ncells, self.nd, 3)
+
+        def get_field_range(self, f, c0, n, out=None):
+            shape = (n,) + self.field_shape(f)[1:]
+            v = (np.arange(c0, c0 + n, dtype=np.float64) * (3.0 if f == _lib.FIELD_S else 1.0) % 7.0 - 3.0)
+            a = np.broadcast_to(v.reshape((n,) + (1,) * (len(shape) - 1)), shape)
+            if out is None:
+                return a.copy()
+            out[...] = a
+            return out
+
+    blk = Block()
+    for world in (1, 2):
+        d = tmp_path / ("w%d" % world)
+        bench.dump_outputs(blk, str(d), 0, world)
+        bench.dump_outputs(blk, str(tmp_path / ("again%d" % world)), 0, world)
+        sfx = "_rank0" if world > 1 else ""
+        names = ["u1", "s1", "cells", "field_norms"]
+        arrs = {k: np.load(str(d / (k + sfx + ".npy"))) for k in names}
+        assert all(a.dtype == np.float64 for a in arrs.values())
+        assert sum(os.path.getsize(str(d / (k + sfx + ".npy"))) for k in names) * world < 64 << 20
+        cells = arrs["cells"].astype(np.int64)
+        assert len(cells) > 1000 and np.all(np.diff(cells) > 0) and cells[-1] < blk.ncells
+        assert arrs["u1"].shape == (len(cells), 35, 3) and arrs["s1"].shape == (len(cells), 35, 3, 3)
+        np.testing.assert_array_equal(arrs["u1"][:, 0, 0], cells * 1.0 % 7.0 - 3.0)
+        np.testing.assert_array_equal(arrs["s1"][:, 0, 0, 0], cells * 3.0 % 7.0 - 3.0)
+        for k in names:
+            np.testing.assert_array_equal(arrs[k], np.load(str(tmp_path / ("again%d" % world) / (k + sfx + ".npy"))))
+        allu = np.arange(blk.ncells, dtype=np.float64) % 7.0 - 3.0
+        np.testing.assert_allclose(arrs["field_norms"][0], np.sqrt(np.sum(allu ** 2) * 105), rtol=1e-12)
+        assert arrs["field_norms"][2] == 3.0 and arrs["field_norms"][3] == 3.0
+
+
 def test_expression_evaluate_times_equals_per_step_evaluation():
     """The per-step source table (elastic.py:285-288: the source Expression re-interpolated before every step) is
     built in one vectorised pass over all steps; element for element it must be what `evaluate` gives with `t` set
