@@ -11,7 +11,8 @@
  *   - plain C types only; no torch / HIP types in signatures (streams and
  *     device buffers cross as void*).
  *   - every call returns SG_OK (0) or a negative error code; the message is
- *     available from sg_last_error().
+ *     available from sg_last_error().  A call that fails leaves the handle as
+ *     it was.
  *   - one host thread drives a handle.  The handle owns its device memory;
  *     host buffers are caller-owned and copied synchronously.
  *   - there is NO CPU fallback: sg_create fails if no HIP device is usable.

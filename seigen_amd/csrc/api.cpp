@@ -8,44 +8,18 @@
 #include "handle.hpp"
 #include "sponge_tables.hpp"
 
-static void free_affine_sponge(sg_handle* h);
-
 extern "C" {
 
 const char* sg_last_error(const sg_handle* h) { return h ? h->err.c_str() : g_create_err.c_str(); }
 
+// device memory is released by the owners (DevBuf) when `delete h` runs; streams, events and graphs here, in order
 void sg_destroy(sg_handle* h) {
   if (!h) return;
   (void)hipSetDevice(h->cfg.device);
   if (h->stream) (void)sync_all(h);
-  for (int f = 0; f < 4; ++f)
-    if (h->field[f]) (void)hipFree(h->field[f]);
-  if (h->md_dev) (void)hipFree(h->md_dev);
-  comm_release(h);
-  if (h->mk_dev) (void)hipFree(h->mk_dev);
-  if (h->ftab_dev) (void)hipFree(h->ftab_dev);
-  if (h->fragQ) (void)hipFree(h->fragQ);
-  if (h->fragP) (void)hipFree(h->fragP);
-  if (h->nbr_tab) (void)hipFree(h->nbr_tab);
-  if (h->Dt) (void)hipFree(h->Dt);
-  if (h->Lt) (void)hipFree(h->Lt);
-  if (h->fragF) (void)hipFree(h->fragF);
-  if (h->fragG) (void)hipFree(h->fragG);
-  if (h->fragL) (void)hipFree(h->fragL);
-  if (h->staging) (void)hipFree(h->staging);
-  for (int i = 0; i < 2; ++i) {
-    if (h->pin[i]) (void)hipHostFree(h->pin[i]);
-    if (h->dstage[i]) (void)hipFree(h->dstage[i]);
-    if (h->xfer_ev[i]) (void)hipEventDestroy(h->xfer_ev[i]);
-  }
-  if (h->sym_flag) (void)hipFree(h->sym_flag);
-  if (h->graph1) (void)hipGraphExecDestroy(h->graph1);
-  if (h->graph8) (void)hipGraphExecDestroy(h->graph8);
-  for (int r = 0; r < 5; ++r)
-    if (h->region_items[r]) (void)hipFree(h->region_items[r]);
-  if (h->dbg) {
+  if (h->dbg.get()) {
     unsigned long long v[32];
-    if (hipMemcpy(v, h->dbg, sizeof(v), hipMemcpyDeviceToHost) == hipSuccess)
+    if (hipMemcpy(v, h->dbg.get(), sizeof(v), hipMemcpyDeviceToHost) == hipSuccess)
       for (int k = 0; k < 4; ++k)
         std::fprintf(stderr, "[seigen_hip stamps] %s mode %d: items %llu  cycles/item: setup %.0f volume %.0f lifts %.0f epilogue %.0f"
                              "   (lifts: neighbour set-up %.0f, facet 0 %.0f, facets 1-3 %.0f)\n",
@@ -53,33 +27,23 @@ void sg_destroy(sg_handle* h) {
                      v[8 * k + 4] ? (double)v[8 * k + 1] / v[8 * k + 4] : 0.0, v[8 * k + 4] ? (double)v[8 * k + 2] / v[8 * k + 4] : 0.0,
                      v[8 * k + 4] ? (double)v[8 * k + 3] / v[8 * k + 4] : 0.0, v[8 * k + 4] ? (double)v[8 * k + 5] / v[8 * k + 4] : 0.0,
                      v[8 * k + 4] ? (double)v[8 * k + 6] / v[8 * k + 4] : 0.0, v[8 * k + 4] ? (double)v[8 * k + 7] / v[8 * k + 4] : 0.0);
-    (void)hipFree(h->dbg);
   }
-  if (h->lam_d) (void)hipFree(h->lam_d);
-  if (h->mu_d) (void)hipFree(h->mu_d);
-  if (h->rho2_d) (void)hipFree(h->rho2_d);
-  if (h->sponge_slot) (void)hipFree(h->sponge_slot);
-  if (h->sponge_B) (void)hipFree(h->sponge_B);
-  if (h->sponge_sigma) (void)hipFree(h->sponge_sigma);
-  if (h->sponge_cells) (void)hipFree(h->sponge_cells);
-  if (h->sponge_mat) (void)hipFree(h->sponge_mat);
-  if (h->sponge_pre) (void)hipFree(h->sponge_pre);
-  free_affine_sponge(h);
-  if (h->src_nodes) (void)hipFree(h->src_nodes);
-  if (h->src_values) (void)hipFree(h->src_values);
-  if (h->src_slot_d) (void)hipFree(h->src_slot_d);
-  if (h->src_idx_d) (void)hipFree(h->src_idx_d);
-  if (h->src_ctr_d) (void)hipFree(h->src_ctr_d);
-  if (h->src_weights_d) (void)hipFree(h->src_weights_d);
+  comm_release(h);
+  if (h->graph1) (void)hipGraphExecDestroy(h->graph1);
+  if (h->graph8) (void)hipGraphExecDestroy(h->graph8);
+  for (int i = 0; i < 2; ++i) {
+    if (h->pin[i]) (void)hipHostFree(h->pin[i]);
+    if (h->xfer_ev[i]) (void)hipEventDestroy(h->xfer_ev[i]);
+  }
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
+  if (h->ev_stage) (void)hipEventDestroy(h->ev_stage);
+  if (h->ev_second) (void)hipEventDestroy(h->ev_second);
   if (h->stream2) {
     (void)hipStreamSynchronize(h->stream2);
     (void)hipStreamDestroy(h->stream2);
   }
-  if (h->ev_stage) (void)hipEventDestroy(h->ev_stage);
-  if (h->ev_second) (void)hipEventDestroy(h->ev_second);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -207,29 +171,23 @@ static int create_impl(const sg_config* cfg, sg_handle* h) {
         }
     for (size_t i = 0; i < Lt.size(); ++i) Lt[i] = h->re.L[i];
   }
-  HIPCHECK(h, hipMalloc((void**)&h->Dt, Dt.size() * sizeof(double)));
-  HIPCHECK(h, hipMalloc((void**)&h->Lt, Lt.size() * sizeof(double)));
-  HIPCHECK(h, hipMalloc((void**)&h->md_dev, sizeof(MeshDev)));
-  HIPCHECK(h, hipMemcpy(h->Dt, Dt.data(), Dt.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHECK(h, hipMemcpy(h->Lt, Lt.data(), Lt.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHECK(h, hipMemcpy(h->md_dev, &h->md, sizeof(MeshDev), hipMemcpyHostToDevice));
+  HIPCHECK(h, h->Dt.upload(Dt.data(), Dt.size()));
+  HIPCHECK(h, h->Lt.upload(Lt.data(), Lt.size()));
+  HIPCHECK(h, h->md_dev.upload(&h->md, 1));
   if (h->use_mfma) {
     const MfmaConst mk = mfma_const(h->md);
-    HIPCHECK(h, hipMalloc((void**)&h->mk_dev, sizeof(MfmaConst)));
-    HIPCHECK(h, hipMemcpy(h->mk_dev, &mk, sizeof(MfmaConst), hipMemcpyHostToDevice));
+    HIPCHECK(h, h->mk_dev.upload(&mk, 1));
     {
       std::vector<int32_t> ft;
       mfma_trace_offsets(h->md, 9, ft);
-      HIPCHECK(h, hipMalloc((void**)&h->ftab_dev, ft.size() * sizeof(int32_t)));
-      HIPCHECK(h, hipMemcpy(h->ftab_dev, ft.data(), ft.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+      HIPCHECK(h, h->ftab_dev.upload(ft.data(), ft.size()));
     }
     if ((h->md.ncube_pad / 16) * 6 * 16 >= ((int64_t)1 << 31))     // cell slots are int32 (288 GB hold far fewer cells)
       return fail(h, SG_ERR_ARG, "block too large for the MFMA path's neighbour table");
     {
       std::vector<int32_t> tab;
       build_nbr_table(h->md, tab);
-      HIPCHECK(h, hipMalloc((void**)&h->nbr_tab, tab.size() * sizeof(int32_t)));
-      HIPCHECK(h, hipMemcpy(h->nbr_tab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+      HIPCHECK(h, h->nbr_tab.upload(tab.data(), tab.size()));
     }
   }
 
@@ -237,10 +195,9 @@ static int create_impl(const sg_config* cfg, sg_handle* h) {
     size_t comps = field_is_stress(f) ? (size_t)d * d : (size_t)d;
     h->field_len[f] = (size_t)h->ncells * nd * comps;
     h->field_alloc[f] = (size_t)h->md.ncube_pad * h->ncls * nd * comps;
-    const size_t es = h->f32 ? sizeof(float) : sizeof(double);
-    if (hipMalloc((void**)&h->field[f], h->field_alloc[f] * es) != hipSuccess)
-      return fail(h, SG_ERR_NOMEM, "hipMalloc of a field buffer failed");
-    HIPCHECK(h, hipMemset(h->field[f], 0, h->field_alloc[f] * es));
+    const size_t n = h->f32 ? (h->field_alloc[f] + 1) / 2 : h->field_alloc[f];   // in doubles
+    if (h->field[f].alloc(n) != hipSuccess) return fail(h, SG_ERR_NOMEM, "hipMalloc of a field buffer failed");
+    HIPCHECK(h, hipMemset(h->field[f].get(), 0, n * sizeof(double)));
   }
   if ((h->use_mfma || h->use_tile) && h->f32) {
     std::vector<float> fF, fG, fL;
@@ -253,12 +210,11 @@ static int create_impl(const sg_config* cfg, sg_handle* h) {
       fG = mfma32_frags_G(h->re);
       fL = mfma32_frags_L(h->re);
     }
-    HIPCHECK(h, hipMalloc((void**)&h->fragF, fF.size() * sizeof(float)));
-    HIPCHECK(h, hipMalloc((void**)&h->fragG, fG.size() * sizeof(float)));
-    HIPCHECK(h, hipMalloc((void**)&h->fragL, fL.size() * sizeof(float)));
-    HIPCHECK(h, hipMemcpy(h->fragF, fF.data(), fF.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHECK(h, hipMemcpy(h->fragG, fG.data(), fG.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHECK(h, hipMemcpy(h->fragL, fL.data(), fL.size() * sizeof(float), hipMemcpyHostToDevice));
+    // float tables in double owners (StageArgs::fragV / fragL are double pointers, as the fields are)
+    for (auto [buf, v] : {std::make_pair(&h->fragF, &fF), std::make_pair(&h->fragG, &fG), std::make_pair(&h->fragL, &fL)}) {
+      HIPCHECK(h, buf->alloc((v->size() + 1) / 2));
+      HIPCHECK(h, hipMemcpy(buf->get(), v->data(), v->size() * sizeof(float), hipMemcpyHostToDevice));
+    }
   } else if (h->use_mfma || h->use_tile) {
     std::vector<double> fF, fG, fL;
     if (h->use_tile) {
@@ -270,12 +226,9 @@ static int create_impl(const sg_config* cfg, sg_handle* h) {
       fG = mfma_frags_G(h->re);
       fL = mfma_frags_L(h->re);
     }
-    HIPCHECK(h, hipMalloc((void**)&h->fragF, fF.size() * sizeof(double)));
-    HIPCHECK(h, hipMalloc((void**)&h->fragG, fG.size() * sizeof(double)));
-    HIPCHECK(h, hipMalloc((void**)&h->fragL, fL.size() * sizeof(double)));
-    HIPCHECK(h, hipMemcpy(h->fragF, fF.data(), fF.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHECK(h, hipMemcpy(h->fragG, fG.data(), fG.size() * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHECK(h, hipMemcpy(h->fragL, fL.data(), fL.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHECK(h, h->fragF.upload(fF.data(), fF.size()));
+    HIPCHECK(h, h->fragG.upload(fG.data(), fG.size()));
+    HIPCHECK(h, h->fragL.upload(fL.data(), fL.size()));
     // factorised G volume (mfma_tables.hpp): D_r = P_r Q
     const char* gq = std::getenv("SEIGEN_HIP_GQ");
     // default: degree 4 only (G<4,0> -2 %, step -0.7 .. -1 %; at degree 3, rank 10 of 20 on 4-row tiles, it is 12 % slower:
@@ -288,10 +241,8 @@ static int create_impl(const sg_config* cfg, sg_handle* h) {
       } catch (const std::exception& e) {
         return fail(h, SG_ERR_ARG, e.what());
       }
-      HIPCHECK(h, hipMalloc((void**)&h->fragQ, fQ.size() * sizeof(double)));
-      HIPCHECK(h, hipMalloc((void**)&h->fragP, fP.size() * sizeof(double)));
-      HIPCHECK(h, hipMemcpy(h->fragQ, fQ.data(), fQ.size() * sizeof(double), hipMemcpyHostToDevice));
-      HIPCHECK(h, hipMemcpy(h->fragP, fP.data(), fP.size() * sizeof(double), hipMemcpyHostToDevice));
+      HIPCHECK(h, h->fragQ.upload(fQ.data(), fQ.size()));
+      HIPCHECK(h, h->fragP.upload(fP.data(), fP.size()));
     }
   }
   if (h->use_mfma || h->use_lane || h->use_tile || h->use_hexm) {
@@ -299,12 +250,12 @@ static int create_impl(const sg_config* cfg, sg_handle* h) {
     // left for good as soon as the user uploads a non-symmetric stress or source (SEIGEN_HIP_SYM=0: never entered)
     const char* sym_env = std::getenv("SEIGEN_HIP_SYM");
     h->sym = !(sym_env && std::strcmp(sym_env, "0") == 0);
-    HIPCHECK(h, hipMalloc((void**)&h->sym_flag, sizeof(int)));
-    HIPCHECK(h, hipMemset(h->sym_flag, 0, sizeof(int)));
+    const int zero = 0;
+    HIPCHECK(h, h->sym_flag.upload(&zero, 1));
   }
   if (std::getenv("SEIGEN_HIP_STAMPS")) {
-    HIPCHECK(h, hipMalloc((void**)&h->dbg, 32 * sizeof(unsigned long long)));
-    HIPCHECK(h, hipMemset(h->dbg, 0, 32 * sizeof(unsigned long long)));
+    const std::vector<unsigned long long> zeros(32, 0);
+    HIPCHECK(h, h->dbg.upload(zeros.data(), zeros.size()));
   }
   {
     // Persistent grid of the MFMA stage kernels: two blocks per CU fill every CU (registers and
@@ -438,334 +389,285 @@ int sg_node_coords(const sg_handle* h, int degree, double* out, size_t nbytes) {
   return sg_block_node_coords(&h->cfg, degree, out, nbytes);
 }
 
+// Every setter below computes and uploads into locals first and assigns to the handle only once nothing can fail any more:
+// a call that fails leaves the handle as it was.  (The handle's old tables may still be read by queued work: sync_all
+// before they are replaced.)
+
 int sg_set_params(sg_handle* h, double density, double dt, const double* lambda, const double* mu, int per_cell) {
-  if (h) h->epoch += 1;
   if (!h || !lambda || !mu) return SG_ERR_ARG;
   HIPCHECK(h, hipSetDevice(h->cfg.device));
+  DevBuf<double> lam_d, mu_d;
+  if (per_cell) {
+    HIPCHECK(h, lam_d.upload(lambda, (size_t)h->ncells));
+    HIPCHECK(h, mu_d.upload(mu, (size_t)h->ncells));
+  }
+  HIPCHECK(h, sync_all(h));
   h->rho = density;
   h->rho_physical = 0;
-  if (h->rho2_d) {
-    HIPCHECK(h, sync_all(h));
-    (void)hipFree(h->rho2_d);
-    h->rho2_d = nullptr;
-  }
+  h->rho2_d.reset();
   h->dt = dt;
   h->per_cell = per_cell ? 1 : 0;
   if (per_cell) {
-    size_t nb = (size_t)h->ncells * sizeof(double);
-    if (!h->lam_d) HIPCHECK(h, hipMalloc((void**)&h->lam_d, nb));
-    if (!h->mu_d) HIPCHECK(h, hipMalloc((void**)&h->mu_d, nb));
-    HIPCHECK(h, sync_all(h));
-    HIPCHECK(h, hipMemcpy(h->lam_d, lambda, nb, hipMemcpyHostToDevice));
-    HIPCHECK(h, hipMemcpy(h->mu_d, mu, nb, hipMemcpyHostToDevice));
-    h->lam0 = lambda[0];
-    h->mu0 = mu[0];
-  } else {
-    h->lam0 = lambda[0];
-    h->mu0 = mu[0];
+    h->lam_d = std::move(lam_d);
+    h->mu_d = std::move(mu_d);
   }
+  h->lam0 = lambda[0];
+  h->mu0 = mu[0];
   h->params_set = true;
+  h->epoch += 1;
   return SG_OK;
 }
 
 int sg_set_density(sg_handle* h, const double* rho, int per_cell, int physical) {
-  if (h) h->epoch += 1;
   if (!h || !rho) return SG_ERR_ARG;
   HIPCHECK(h, hipSetDevice(h->cfg.device));
-  HIPCHECK(h, sync_all(h));
-  if (h->rho2_d) {
-    (void)hipFree(h->rho2_d);
-    h->rho2_d = nullptr;
-  }
-  h->rho_physical = physical ? 1 : 0;
-  if (!per_cell) {
-    if (physical && rho[0] == 0.0) return fail(h, SG_ERR_ARG, "sg_set_density: zero density");
-    h->rho = rho[0];
-    return SG_OK;
-  }
-  std::vector<double> r2((size_t)h->ncells * 2);
-  for (int64_t e = 0; e < h->ncells; ++e) {
+  DevBuf<double> rho2_d;
+  const int64_t n = per_cell ? h->ncells : 1;
+  std::vector<double> r2((size_t)n * 2);
+  for (int64_t e = 0; e < n; ++e) {
     if (physical && rho[e] == 0.0) return fail(h, SG_ERR_ARG, "sg_set_density: zero density");
     r2[2 * (size_t)e] = physical ? 1.0 : rho[e];
     r2[2 * (size_t)e + 1] = physical ? 1.0 / rho[e] : 1.0;
   }
+  if (per_cell) HIPCHECK(h, rho2_d.upload(r2.data(), r2.size()));
+  HIPCHECK(h, sync_all(h));
+  h->rho2_d = std::move(rho2_d);
+  h->rho_physical = physical ? 1 : 0;
   h->rho = rho[0];
-  HIPCHECK(h, hipMalloc((void**)&h->rho2_d, r2.size() * sizeof(double)));
-  HIPCHECK(h, hipMemcpy(h->rho2_d, r2.data(), r2.size() * sizeof(double), hipMemcpyHostToDevice));
+  h->epoch += 1;
   return SG_OK;
 }
 
-static void free_affine_sponge(sg_handle* h) {
-  for (void** p : {(void**)&h->sponge_mat_slots, (void**)&h->sponge_aff_items, (void**)&h->sponge_aff_slots, (void**)&h->sponge_aff_coef,
-                   (void**)&h->sponge_aff_X, (void**)&h->sponge_aff_col, (void**)&h->sponge_aff_frag})
-    if (*p) {
-      (void)hipFree(*p);
-      *p = nullptr;
+// What each cell gets - nothing, a scalar, dim + 1 numbers, a matrix - is decided by plan_sponge (sponge_tables.cpp: plain
+// C++, under the CPU sanitizers); this function checks the plan against the device, uploads it and puts it in place.
+int sg_set_absorption(sg_handle* h, const double* sigma_nodes, int sigma_degree) {
+  if (!h) return SG_ERR_ARG;
+  if (sigma_nodes && (sigma_degree < 1 || sigma_degree > 6)) return fail(h, SG_ERR_ARG, "sigma_degree must be 1..6");
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SpongeTables sp;
+  if (sigma_nodes) {
+    const int d = h->cfg.dim, nd = h->re.nd;
+    SpongeRequest rq;
+    rq.dim = d;
+    rq.degree = h->cfg.degree;
+    rq.kind = h->re.kind;
+    rq.sigma_degree = sigma_degree;
+    rq.ncells = h->ncells;
+    rq.ncls = h->ncls;
+    rq.gw = (int)h->md.gw;
+    // 2-D tile and 3-D matrix kernels, lane kernels: a sigma that is one value on all nodes of a cell (the piecewise-constant
+    // sponges of the reference's problem scripts, explosive_source_lf4.py:42-45) is applied as sigma u at the node
+    rq.want_scalar = h->use_tile || h->use_mfma || h->use_hexm || h->use_lane;
+    // the 3-D matrix kernels and the lane kernels read B u_abs from a pre-pass (kernels.hpp launch_sponge_pre); the 2-D tile
+    // kernels work their small matrices off themselves: a launch more per F stage costs them more
+    rq.pre_family = h->use_mfma || h->use_hexm || h->use_lane;
+    // Affine cells take dim + 1 numbers (kernels.hip sponge_pre_affine_kernel, kernels_mfma.hip sponge_affine_mfma);
+    // SEIGEN_HIP_SPONGE_AFFINE=0 sends them through their matrices (tests: the two must agree).  The lane kernels' cells -
+    // hexahedra DQ_1 / DQ_2, gw = 64 - have matrices of at most 27 x 27 shared through the caches: there the matrix pre-pass
+    // is the faster one (64.5 against 61.9 G at 96^3 DQ_2, profiles/r06/affine_sponge.txt); '1' forces the affine path
+    const char* aff_env = std::getenv("SEIGEN_HIP_SPONGE_AFFINE");
+    rq.try_affine = rq.pre_family && !(aff_env && aff_env[0] == '0') && (!h->use_lane || (aff_env && aff_env[0] == '1'));
+    // 3-D MFMA family: the pre-pass results live in LINE layout like the fields (a record per cell cost the affine pre-pass
+    // scattered 24-byte stores and the F stage scattered loads)
+    rq.line_layout = h->use_mfma;
+    SpongePlan pl;
+    try {
+      pl = plan_sponge(rq, sigma_nodes);
+    } catch (const std::exception& e) {
+      return fail(h, SG_ERR_ARG, std::string("sg_set_absorption: ") + e.what());
     }
-  h->sponge_nmat_slots = 0;
-  h->sponge_aff_nitems = 0;
-  h->sponge_aff_W = 0;
+    const bool pre = rq.pre_family && pl.nslots > 0, affine = rq.pre_family && pl.naffine > 0;
+    const bool aff_mfma = affine && h->use_mfma && !h->f32 && d == 3;   // on the matrix pipe (kernels_mfma.hip sponge_affine_mfma)
+    if (affine) {
+      if (rq.gw * nd > SG_SPONGE_AFFINE_MAX_ROWS)
+        return fail(h, SG_ERR_STATE, "sg_set_absorption: the affine-sigma pre-pass takes at most " +
+                                         std::to_string(SG_SPONGE_AFFINE_MAX_ROWS) + " (cell, node) rows per item (set SEIGEN_HIP_SPONGE_AFFINE=0)");
+      const size_t lds = sponge_pre_affine_lds(pl.W, !pl.dense, nd, d, rq.gw);
+      if (lds > ((size_t)150 << 10))
+        return fail(h, SG_ERR_STATE, "sg_set_absorption: the affine-sigma tables of this element do not fit the LDS (set SEIGEN_HIP_SPONGE_AFFINE=0)");
+      int ncu = 0;
+      HIPCHECK(h, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->cfg.device));
+      sp.aff_grid = aff_mfma ? prepare_sponge_affine_mfma(h->cfg.degree, ncu) : prepare_sponge_pre_affine(d, h->f32, lds, ncu);
+      if (sp.aff_grid <= 0) return fail(h, SG_ERR_DEVICE, "sg_set_absorption: the affine-sigma pre-pass cannot be set up on this device");
+    }
+    hipError_t e = hipSuccess;
+    auto up = [&e](auto& buf, const auto& v) {
+      if (e == hipSuccess) e = buf.upload(v.data(), v.size());
+    };
+    up(sp.slot, pl.slot);
+    sp.nslots = pl.nslots;
+    sp.pre_lines = (rq.line_layout && pl.nslots > 0) ? 1 : 0;
+    if (pre) {
+      const size_t pre_bytes = (size_t)pl.nslots * nd * d * (h->f32 ? sizeof(float) : sizeof(double));
+      up(sp.cells, pl.cells);
+      up(sp.mat, pl.mat_of);
+      if (e == hipSuccess) e = sp.pre.alloc(pre_bytes);
+      if (e == hipSuccess) e = hipMemset(sp.pre.get(), 0, pre_bytes);
+      // the cells with a matrix: every slot in order, or - line layout, affine cells among them - a list
+      sp.nmat_slots = (int32_t)pl.mat_slots.size();
+      if (sp.pre_lines || pl.naffine > 0) up(sp.mat_slots, pl.mat_slots);
+    }
+    if (affine) {
+      up(sp.aff_items, pl.items);
+      up(sp.aff_slots, pl.item_slots);
+      up(sp.aff_coef, pl.aff_coef);
+      up(sp.aff_X, pl.X);
+      if (!pl.dense) up(sp.aff_col, pl.col);
+      if (aff_mfma) up(sp.aff_frag, mfma_frags_dense(h->re, pl.Xd.data(), 3));
+      sp.aff_nitems = (int32_t)pl.items.size();
+      sp.aff_W = pl.W;
+    }
+    if (!pl.sig.empty()) up(sp.sigma, pl.sig);
+    up(sp.B, pl.B);
+    if (e != hipSuccess) return fail(h, SG_ERR_NOMEM, "sg_set_absorption: hipMalloc / upload of the sponge tables failed");
+  }
+  HIPCHECK(h, sync_all(h));
+  h->sponge = std::move(sp);
+  h->epoch += 1;
+  return SG_OK;
 }
 
-// What each cell gets - nothing, a scalar, dim + 1 numbers, a matrix - is decided by plan_sponge (sponge_tables.cpp: plain
-// C++, under the CPU sanitizers); this function frees the old tables and uploads the new ones.
-int sg_set_absorption(sg_handle* h, const double* sigma_nodes, int sigma_degree) {
-  if (h) h->epoch += 1;
-  if (!h) return SG_ERR_ARG;
+// sg_set_source and sg_set_source_separable: nsteps slices of values (-1: one that holds at every step), or - weights
+// given - one slice scaled by weights[k] at step k < nsteps
+static int set_source(sg_handle* h, int64_t nnz, const int64_t* nodes, int64_t nsteps, const double* values, const double* weights) {
   HIPCHECK(h, hipSetDevice(h->cfg.device));
+  SourceTables src;
+  if (nnz != 0 && nsteps != 0) {
+    if (!nodes || !values || nsteps < -1) return SG_ERR_ARG;
+    const int d = h->cfg.dim;
+    src.is_static = nsteps == -1;
+    src.nsteps = src.is_static ? 1 : nsteps;
+    const int64_t nslices = weights ? 1 : src.nsteps;
+    int64_t nscalar = h->ncells * h->re.nd;
+    for (int64_t k = 0; k < nnz; ++k)
+      if (nodes[k] < 0 || nodes[k] >= nscalar) return fail(h, SG_ERR_ARG, "sg_set_source: node index out of range");
+    // A node listed more than once: its entries add up (in the order listed), merged here once so that every node is
+    // written by one thread - the sum is then the same on every run and on every partition of the mesh (an atomic add
+    // per entry gave the right sum in an arbitrary order, i.e. results that differed in the last bit from run to run).
+    std::vector<int64_t> merged_nodes;
+    std::vector<double> merged_values;
+    {
+      std::unordered_map<int64_t, int64_t> slot_of;
+      slot_of.reserve((size_t)nnz * 2);
+      std::vector<int64_t> to((size_t)nnz);
+      for (int64_t k = 0; k < nnz; ++k) {
+        auto it = slot_of.find(nodes[k]);
+        if (it == slot_of.end()) {
+          it = slot_of.emplace(nodes[k], (int64_t)merged_nodes.size()).first;
+          merged_nodes.push_back(nodes[k]);
+        }
+        to[(size_t)k] = it->second;
+      }
+      if ((int64_t)merged_nodes.size() != nnz) {
+        const int64_t nm = (int64_t)merged_nodes.size(), dd = (int64_t)d * d;
+        merged_values.assign((size_t)(nslices * nm * dd), 0.0);
+        for (int64_t s = 0; s < nslices; ++s)
+          for (int64_t k = 0; k < nnz; ++k)
+            for (int64_t c = 0; c < dd; ++c) merged_values[(size_t)((s * nm + to[(size_t)k]) * dd + c)] += values[(s * nnz + k) * dd + c];
+        nodes = merged_nodes.data();
+        values = merged_values.data();
+        nnz = nm;
+      }
+    }
+    src.nnz = nnz;
+    // Order the nodes so that those in cells of SG_REGION_FIRST come first: a split stage adds the
+    // source to each part right after the launch that wrote it (the traces of FIRST are packed
+    // before SECOND has run).  Then: device offset of component 0 of each node in the field layout.
+    std::vector<int64_t> order((size_t)nnz), offs((size_t)nnz);
+    {
+      const int64_t nd = h->re.nd, ncls = h->ncls, gw = h->md.gw, nc = (int64_t)d * d;
+      std::vector<Box> first;
+      region_boxes(h, SG_REGION_FIRST, first);
+      auto in_first = [&](int64_t node) {
+        const int64_t cube = node / nd / ncls;
+        const int64_t c[3] = {cube % h->cfg.n[0], (cube / h->cfg.n[0]) % h->cfg.n[1], cube / ((int64_t)h->cfg.n[0] * h->cfg.n[1])};
+        for (const Box& b : first) {
+          bool in = true;
+          for (int k = 0; k < 3; ++k) in = in && c[k] >= b.o[k] && c[k] < b.o[k] + b.n[k];
+          if (in) return true;
+        }
+        return false;
+      };
+      int64_t n1 = 0;
+      for (int64_t i = 0; i < nnz; ++i)
+        if (in_first(nodes[i])) order[(size_t)n1++] = i;
+      src.nfirst = n1;
+      for (int64_t i = 0; i < nnz; ++i)
+        if (!in_first(nodes[i])) order[(size_t)n1++] = i;
+      for (int64_t j = 0; j < nnz; ++j) {
+        const int64_t node = nodes[order[(size_t)j]];
+        int64_t e = node / nd, b = node % nd;
+        int64_t cube = e / ncls, cls = e % ncls;
+        offs[(size_t)j] = ((((cube / gw) * ncls + cls) * nd + b) * nc) * gw + cube % gw;
+      }
+    }
+    std::vector<double> vals((size_t)nslices * nnz * d * d);
+    for (int64_t k = 0; k < nslices; ++k)
+      for (int64_t j = 0; j < nnz; ++j)
+        std::memcpy(&vals[((size_t)k * nnz + j) * d * d], &values[((size_t)k * nnz + order[(size_t)j]) * d * d], sizeof(double) * d * d);
+    HIPCHECK(h, src.nodes.upload(offs.data(), offs.size()));
+    HIPCHECK(h, src.values.upload(vals.data(), vals.size()));
+    if (weights) {
+      src.weights.assign(weights, weights + nsteps);
+      HIPCHECK(h, src.weights_d.upload(weights, (size_t)nsteps));
+    }
+    if (h->use_tile && !std::getenv("SEIGEN_HIP_SOURCE_LAUNCH")) {
+      // tile kernels: item (16 squares of one class) -> slot, and per slot a dense (node, cell) -> value-row table, so
+      // that the G stages add the source themselves (one launch less per G stage).  (Nodes are unique here: entries of a
+      // node listed twice were merged above.)
+      const int64_t nd = h->re.nd, ncl = h->ncls, nitems = h->md.ncube_pad / 16 * ncl;
+      std::vector<int32_t> slot((size_t)nitems, -1), idx;
+      bool dup = false;
+      for (int64_t j = 0; j < nnz && !dup; ++j) {
+        const int64_t node = nodes[order[(size_t)j]];
+        const int64_t e = node / nd, b = node % nd, cube = e / ncl, cls = e % ncl;
+        const int64_t item = (cube / 16) * ncl + cls;
+        if (slot[(size_t)item] < 0) {
+          slot[(size_t)item] = (int32_t)(idx.size() / (size_t)(nd * 16));
+          idx.resize(idx.size() + (size_t)(nd * 16), -1);
+        }
+        int32_t& cell = idx[((size_t)slot[(size_t)item] * nd + b) * 16 + cube % 16];
+        dup = cell >= 0;
+        cell = (int32_t)j;
+      }
+      if (!dup) {
+        HIPCHECK(h, src.slot.upload(slot.data(), slot.size()));
+        HIPCHECK(h, src.idx.upload(idx.data(), idx.size()));
+        src.fused = true;
+      }
+    }
+    if (!h->src_ctr_d.get()) {   // device-side step counter for graph replay (stages.cpp sg_step), kept across sources
+      const int64_t zero = 0;
+      HIPCHECK(h, h->src_ctr_d.upload(&zero, 1));
+    }
+    if (h->sym) {
+      bool symmetric = true;
+      for (int64_t i = 0; i < nslices * nnz && symmetric; ++i)
+        for (int a = 0; a < d; ++a)
+          for (int b = a + 1; b < d; ++b) symmetric = symmetric && vals[i * d * d + a * d + b] == vals[i * d * d + b * d + a];
+      if (!symmetric) {
+        int rc = leave_sym_mode(h);
+        if (rc != SG_OK) return rc;
+      }
+    }
+  }
   HIPCHECK(h, sync_all(h));
-  for (void** p : {(void**)&h->sponge_slot, (void**)&h->sponge_B, (void**)&h->sponge_sigma, (void**)&h->sponge_cells,
-                   (void**)&h->sponge_mat, (void**)&h->sponge_pre})
-    if (*p) {
-      (void)hipFree(*p);
-      *p = nullptr;
-    }
-  h->sponge_nslots = 0;
-  h->sponge_pre_key = -1;
-  h->sponge_pre_regions = 0;
-  h->sponge_pre_ver = ~0ull;
-  h->sponge_pre_field = -1;
-  h->sponge_pre_lines = 0;
-  free_affine_sponge(h);
-  if (!sigma_nodes) return SG_OK;
-  if (sigma_degree < 1 || sigma_degree > 6) return fail(h, SG_ERR_ARG, "sigma_degree must be 1..6");
-  const int d = h->cfg.dim, nd = h->re.nd;
-  SpongeRequest rq;
-  rq.dim = d;
-  rq.degree = h->cfg.degree;
-  rq.kind = h->re.kind;
-  rq.sigma_degree = sigma_degree;
-  rq.ncells = h->ncells;
-  rq.ncls = h->ncls;
-  rq.gw = (int)h->md.gw;
-  // 2-D tile and 3-D matrix kernels, lane kernels: a sigma that is one value on all nodes of a cell (the piecewise-constant
-  // sponges of the reference's problem scripts, explosive_source_lf4.py:42-45) is applied as sigma u at the node
-  rq.want_scalar = h->use_tile || h->use_mfma || h->use_hexm || h->use_lane;
-  // the 3-D matrix kernels and the lane kernels read B u_abs from a pre-pass (kernels.hpp launch_sponge_pre); the 2-D tile
-  // kernels work their small matrices off themselves: a launch more per F stage costs them more
-  rq.pre_family = h->use_mfma || h->use_hexm || h->use_lane;
-  // Affine cells take dim + 1 numbers (kernels.hip sponge_pre_affine_kernel, kernels_mfma.hip sponge_affine_mfma);
-  // SEIGEN_HIP_SPONGE_AFFINE=0 sends them through their matrices (tests: the two must agree).  The lane kernels' cells -
-  // hexahedra DQ_1 / DQ_2, gw = 64 - have matrices of at most 27 x 27 shared through the caches: there the matrix pre-pass
-  // is the faster one (64.5 against 61.9 G at 96^3 DQ_2, profiles/r06/affine_sponge.txt); '1' forces the affine path
-  const char* aff_env = std::getenv("SEIGEN_HIP_SPONGE_AFFINE");
-  rq.try_affine = rq.pre_family && !(aff_env && aff_env[0] == '0') && (!h->use_lane || (aff_env && aff_env[0] == '1'));
-  // 3-D MFMA family: the pre-pass results live in LINE layout like the fields (a record per cell cost the affine pre-pass
-  // scattered 24-byte stores and the F stage scattered loads)
-  rq.line_layout = h->use_mfma;
-  SpongePlan pl;
-  try {
-    pl = plan_sponge(rq, sigma_nodes);
-  } catch (const std::exception& e) {
-    return fail(h, SG_ERR_ARG, std::string("sg_set_absorption: ") + e.what());
-  }
-  auto up = [&](void** dst, const void* src, size_t bytes) {
-    if (hipMalloc(dst, bytes ? bytes : 8) != hipSuccess) return false;
-    return bytes == 0 || hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
-  };
-  bool ok = up((void**)&h->sponge_slot, pl.slot.data(), pl.slot.size() * sizeof(int32_t));
-  h->sponge_nslots = pl.nslots;
-  h->sponge_pre_lines = (rq.line_layout && pl.nslots > 0) ? 1 : 0;
-  if (rq.pre_family && pl.nslots > 0) {
-    const size_t pre_bytes = (size_t)pl.nslots * nd * d * (h->f32 ? sizeof(float) : sizeof(double));
-    ok = ok && up((void**)&h->sponge_cells, pl.cells.data(), pl.cells.size() * sizeof(int32_t)) &&
-         up((void**)&h->sponge_mat, pl.mat_of.data(), pl.mat_of.size() * sizeof(int32_t)) && hipMalloc(&h->sponge_pre, pre_bytes) == hipSuccess &&
-         hipMemset(h->sponge_pre, 0, pre_bytes) == hipSuccess;
-    // the cells with a matrix: every slot in order, or - line layout, affine cells among them - a list
-    h->sponge_nmat_slots = (int32_t)pl.mat_slots.size();
-    if (h->sponge_pre_lines || pl.naffine > 0)
-      ok = ok && up((void**)&h->sponge_mat_slots, pl.mat_slots.data(), pl.mat_slots.size() * sizeof(int32_t));
-  }
-  if (rq.pre_family && pl.naffine > 0) {
-    const size_t lds = sponge_pre_affine_lds(pl.W, !pl.dense, nd, d, rq.gw);
-    if (lds > ((size_t)150 << 10))
-      return fail(h, SG_ERR_STATE, "sg_set_absorption: the affine-sigma tables of this element do not fit the LDS (set SEIGEN_HIP_SPONGE_AFFINE=0)");
-    if (prepare_sponge_pre_affine(d, h->f32, lds) != 0)
-      return fail(h, SG_ERR_DEVICE, "sg_set_absorption: the affine-sigma pre-pass cannot have its LDS");
-    ok = ok && up((void**)&h->sponge_aff_items, pl.items.data(), pl.items.size() * sizeof(int32_t)) &&
-         up((void**)&h->sponge_aff_slots, pl.item_slots.data(), pl.item_slots.size() * sizeof(int32_t)) &&
-         up((void**)&h->sponge_aff_coef, pl.aff_coef.data(), pl.aff_coef.size() * sizeof(double)) &&
-         up((void**)&h->sponge_aff_X, pl.X.data(), pl.X.size() * sizeof(double)) &&
-         (pl.dense || up((void**)&h->sponge_aff_col, pl.col.data(), pl.col.size() * sizeof(int32_t)));
-    if (h->use_mfma && !h->f32 && d == 3) {      // on the matrix pipe (kernels_mfma.hip sponge_affine_mfma)
-      const std::vector<double> fX = mfma_frags_dense(h->re, pl.Xd.data(), 3);
-      ok = ok && up((void**)&h->sponge_aff_frag, fX.data(), fX.size() * sizeof(double)) && prepare_sponge_affine_mfma(h->cfg.degree) == 0;
-    }
-    h->sponge_aff_nitems = (int32_t)pl.items.size();
-    h->sponge_aff_W = pl.W;
-  }
-  if (!pl.sig.empty()) ok = ok && up((void**)&h->sponge_sigma, pl.sig.data(), pl.sig.size() * sizeof(double));
-  ok = ok && up((void**)&h->sponge_B, pl.B.data(), pl.B.size() * sizeof(double));
-  if (!ok) return fail(h, SG_ERR_NOMEM, "sg_set_absorption: hipMalloc / upload of the sponge tables failed");
+  h->src = std::move(src);
+  h->src_step = 0;
+  h->epoch += 1;
   return SG_OK;
 }
 
 int sg_set_source(sg_handle* h, int64_t nnz, const int64_t* nodes, int64_t nsteps, const double* values) {
-  if (h) h->epoch += 1;
   if (!h || nnz < 0) return SG_ERR_ARG;
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
-  HIPCHECK(h, sync_all(h));
-  if (h->src_nodes) {
-    (void)hipFree(h->src_nodes);
-    h->src_nodes = nullptr;
-  }
-  if (h->src_values) {
-    (void)hipFree(h->src_values);
-    h->src_values = nullptr;
-  }
-  if (h->src_slot_d) {
-    (void)hipFree(h->src_slot_d);
-    h->src_slot_d = nullptr;
-  }
-  if (h->src_idx_d) {
-    (void)hipFree(h->src_idx_d);
-    h->src_idx_d = nullptr;
-  }
-  if (h->src_weights_d) {
-    (void)hipFree(h->src_weights_d);
-    h->src_weights_d = nullptr;
-  }
-  h->src_fused = false;
-  h->src_nnz = 0;
-  h->src_nsteps = 0;
-  h->src_step = 0;
-  h->src_static = false;
-  h->src_weights.clear();
-  if (nnz == 0 || nsteps == 0) return SG_OK;
-  if (!nodes || !values || nsteps < -1) return SG_ERR_ARG;
-  const bool is_static = nsteps == -1;
-  if (is_static) nsteps = 1;
-  const int d = h->cfg.dim;
-  int64_t nscalar = h->ncells * h->re.nd;
-  for (int64_t k = 0; k < nnz; ++k)
-    if (nodes[k] < 0 || nodes[k] >= nscalar) return fail(h, SG_ERR_ARG, "sg_set_source: node index out of range");
-  // A node listed more than once: its entries add up (in the order listed), merged here once so that every node is
-  // written by one thread - the sum is then the same on every run and on every partition of the mesh (an atomic add
-  // per entry gave the right sum in an arbitrary order, i.e. results that differed in the last bit from run to run).
-  std::vector<int64_t> merged_nodes;
-  std::vector<double> merged_values;
-  {
-    std::unordered_map<int64_t, int64_t> slot_of;
-    slot_of.reserve((size_t)nnz * 2);
-    std::vector<int64_t> to((size_t)nnz);
-    for (int64_t k = 0; k < nnz; ++k) {
-      auto it = slot_of.find(nodes[k]);
-      if (it == slot_of.end()) {
-        it = slot_of.emplace(nodes[k], (int64_t)merged_nodes.size()).first;
-        merged_nodes.push_back(nodes[k]);
-      }
-      to[(size_t)k] = it->second;
-    }
-    if ((int64_t)merged_nodes.size() != nnz) {
-      const int64_t nm = (int64_t)merged_nodes.size(), dd = (int64_t)d * d;
-      merged_values.assign((size_t)(nsteps * nm * dd), 0.0);
-      for (int64_t s = 0; s < nsteps; ++s)
-        for (int64_t k = 0; k < nnz; ++k)
-          for (int64_t c = 0; c < dd; ++c) merged_values[(size_t)((s * nm + to[(size_t)k]) * dd + c)] += values[(s * nnz + k) * dd + c];
-      nodes = merged_nodes.data();
-      values = merged_values.data();
-      nnz = nm;
-    }
-  }
-  if (h->sym) {
-    bool symmetric = true;
-    for (int64_t i = 0; i < nsteps * nnz && symmetric; ++i)
-      for (int a = 0; a < d; ++a)
-        for (int b = a + 1; b < d; ++b) symmetric = symmetric && values[i * d * d + a * d + b] == values[i * d * d + b * d + a];
-    if (!symmetric) {
-      int rc = leave_sym_mode(h);
-      if (rc != SG_OK) return rc;
-    }
-  }
-  size_t vbytes = (size_t)nsteps * nnz * d * d * sizeof(double);
-  HIPCHECK(h, hipMalloc((void**)&h->src_nodes, (size_t)nnz * sizeof(int64_t)));
-  HIPCHECK(h, hipMalloc((void**)&h->src_values, vbytes));
-  // Order the nodes so that those in cells of SG_REGION_FIRST come first: a split stage adds the
-  // source to each part right after the launch that wrote it (the traces of FIRST are packed
-  // before SECOND has run).  Then: device offset of component 0 of each node in the field layout.
-  std::vector<int64_t> order((size_t)nnz), offs((size_t)nnz);
-  {
-    const int64_t nd = h->re.nd, ncls = h->ncls, gw = h->md.gw, nc = (int64_t)d * d;
-    std::vector<Box> first;
-    region_boxes(h, SG_REGION_FIRST, first);
-    auto in_first = [&](int64_t node) {
-      const int64_t cube = node / nd / ncls;
-      const int64_t c[3] = {cube % h->cfg.n[0], (cube / h->cfg.n[0]) % h->cfg.n[1], cube / ((int64_t)h->cfg.n[0] * h->cfg.n[1])};
-      for (const Box& b : first) {
-        bool in = true;
-        for (int k = 0; k < 3; ++k) in = in && c[k] >= b.o[k] && c[k] < b.o[k] + b.n[k];
-        if (in) return true;
-      }
-      return false;
-    };
-    int64_t n1 = 0;
-    for (int64_t i = 0; i < nnz; ++i)
-      if (in_first(nodes[i])) order[(size_t)n1++] = i;
-    h->src_nfirst = n1;
-    for (int64_t i = 0; i < nnz; ++i)
-      if (!in_first(nodes[i])) order[(size_t)n1++] = i;
-    for (int64_t j = 0; j < nnz; ++j) {
-      const int64_t node = nodes[order[(size_t)j]];
-      int64_t e = node / nd, b = node % nd;
-      int64_t cube = e / ncls, cls = e % ncls;
-      offs[(size_t)j] = ((((cube / gw) * ncls + cls) * nd + b) * nc) * gw + cube % gw;
-    }
-  }
-  std::vector<double> vals((size_t)nsteps * nnz * d * d);
-  for (int64_t k = 0; k < nsteps; ++k)
-    for (int64_t j = 0; j < nnz; ++j)
-      std::memcpy(&vals[((size_t)k * nnz + j) * d * d], &values[((size_t)k * nnz + order[(size_t)j]) * d * d], sizeof(double) * d * d);
-  HIPCHECK(h, hipMemcpy(h->src_nodes, offs.data(), (size_t)nnz * sizeof(int64_t), hipMemcpyHostToDevice));
-  HIPCHECK(h, hipMemcpy(h->src_values, vals.data(), vbytes, hipMemcpyHostToDevice));
-  if (h->use_tile && !std::getenv("SEIGEN_HIP_SOURCE_LAUNCH")) {
-    // tile kernels: item (16 squares of one class) -> slot, and per slot a dense (node, cell) -> value-row table, so
-    // that the G stages add the source themselves (one launch less per G stage).  (Nodes are unique here: entries of a
-    // node listed twice were merged above.)
-    const int64_t nd = h->re.nd, ncl = h->ncls, nitems = h->md.ncube_pad / 16 * ncl;
-    std::vector<int32_t> slot((size_t)nitems, -1), idx;
-    bool dup = false;
-    for (int64_t j = 0; j < nnz && !dup; ++j) {
-      const int64_t node = nodes[order[(size_t)j]];
-      const int64_t e = node / nd, b = node % nd, cube = e / ncl, cls = e % ncl;
-      const int64_t item = (cube / 16) * ncl + cls;
-      if (slot[(size_t)item] < 0) {
-        slot[(size_t)item] = (int32_t)(idx.size() / (size_t)(nd * 16));
-        idx.resize(idx.size() + (size_t)(nd * 16), -1);
-      }
-      int32_t& cell = idx[((size_t)slot[(size_t)item] * nd + b) * 16 + cube % 16];
-      dup = cell >= 0;
-      cell = (int32_t)j;
-    }
-    if (!dup) {
-      HIPCHECK(h, hipMalloc((void**)&h->src_slot_d, slot.size() * sizeof(int32_t)));
-      HIPCHECK(h, hipMalloc((void**)&h->src_idx_d, idx.size() * sizeof(int32_t)));
-      HIPCHECK(h, hipMemcpy(h->src_slot_d, slot.data(), slot.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-      HIPCHECK(h, hipMemcpy(h->src_idx_d, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-      h->src_fused = true;
-    }
-  }
-  if (!h->src_ctr_d) {   // device-side step counter for graph replay (stages.cpp sg_step)
-    HIPCHECK(h, hipMalloc((void**)&h->src_ctr_d, sizeof(int64_t)));
-    HIPCHECK(h, hipMemset(h->src_ctr_d, 0, sizeof(int64_t)));
-  }
-  h->src_nnz = nnz;
-  h->src_nsteps = nsteps;
-  h->src_static = is_static;
-  return SG_OK;
+  return set_source(h, nnz, nodes, nsteps, values, nullptr);
 }
 
 int sg_set_source_separable(sg_handle* h, int64_t nnz, const int64_t* nodes, const double* pattern, int64_t nsteps,
                             const double* weights) {
   if (!h || nnz < 0 || nsteps < 0) return SG_ERR_ARG;
-  if (nnz == 0 || nsteps == 0) return sg_set_source(h, 0, nullptr, 0, nullptr);
-  if (!weights) return SG_ERR_ARG;
-  int rc = sg_set_source(h, nnz, nodes, 1, pattern);      // one slice: order, offsets, symmetry check, fused tables
-  if (rc != SG_OK) return rc;
-  h->src_weights.assign(weights, weights + nsteps);
-  h->src_nsteps = nsteps;
-  HIPCHECK(h, hipMalloc((void**)&h->src_weights_d, (size_t)nsteps * sizeof(double)));
-  HIPCHECK(h, hipMemcpy(h->src_weights_d, weights, (size_t)nsteps * sizeof(double), hipMemcpyHostToDevice));
-  return SG_OK;
+  if (nnz != 0 && nsteps != 0 && !weights) return SG_ERR_ARG;
+  return set_source(h, nnz, nodes, nsteps, pattern, weights);
 }
 
 int sg_set_source_box_ricker(sg_handle* h, const double* lo, const double* hi, double a, double t0, double t_first,

@@ -105,8 +105,8 @@ struct sg_comm_state {
   int rank = -1, nranks = 0;
   int peers[6] = {-1, -1, -1, -1, -1, -1};
   int nsides = 0, sides[6];
-  void* send[2][6];   // [0: velocity-like fields, 1: stress-like fields][side]
-  void* recv[2][6];
+  DevBuf<char> send[2][6];   // [0: velocity-like fields, 1: stress-like fields][side]
+  DevBuf<char> recv[2][6];
   size_t count[6];    // values per side (dim per facet node for either kind)
   sg_comm_stats_t stats;
   bool used = false;   // field traces have been exchanged: the ghost buffers hold data a stage may still read
@@ -160,7 +160,7 @@ static int exchange(sg_handle* h, int field, hipEvent_t* recv_done, bool pack = 
   int rc = SG_OK;
   if (pack) {
     void* outs[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    for (int i = 0; i < c->nsides; ++i) outs[c->sides[i]] = c->send[kind][c->sides[i]];
+    for (int i = 0; i < c->nsides; ++i) outs[c->sides[i]] = c->send[kind][c->sides[i]].get();
     rc = sg_halo_pack_sides(h, field, outs);
     if (rc != SG_OK) return rc;
   }
@@ -182,7 +182,7 @@ static int exchange(sg_handle* h, int field, hipEvent_t* recv_done, bool pack = 
   // sends in the order of my sides ...
   for (int s = 0; s < 6; ++s) {
     if (c->peers[s] < 0) continue;
-    NCCLCHECK(h, nc.Send(c->send[kind][s], c->count[s], ty, c->peers[s], c->comm, h->stream));
+    NCCLCHECK(h, nc.Send(c->send[kind][s].get(), c->count[s], ty, c->peers[s], c->comm, h->stream));
     c->stats.bytes_sent += (int64_t)(c->count[s] * (h->f32 ? sizeof(float) : sizeof(double)));
   }
   // ... receives in the order of the FACING sides: RCCL pairs the sends and receives between two ranks in posting
@@ -192,7 +192,7 @@ static int exchange(sg_handle* h, int field, hipEvent_t* recv_done, bool pack = 
   for (int t = 0; t < 6; ++t) {
     const int s = t ^ 1;
     if (c->peers[s] < 0) continue;
-    NCCLCHECK(h, nc.Recv(c->recv[kind][s], c->count[s], ty, c->peers[s], c->comm, h->stream));
+    NCCLCHECK(h, nc.Recv(c->recv[kind][s].get(), c->count[s], ty, c->peers[s], c->comm, h->stream));
   }
   NCCLCHECK(h, nc.GroupEnd());
   c->stats.exchanges += 1;
@@ -250,11 +250,6 @@ void comm_release(sg_handle* h) {
   sg_comm_state* c = h->comm;
   if (!c) return;
   (void)sync_all(h);
-  for (int k = 0; k < 2; ++k)
-    for (int s = 0; s < 6; ++s) {
-      if (c->send[k][s]) (void)hipFree(c->send[k][s]);
-      if (c->recv[k][s]) (void)hipFree(c->recv[k][s]);
-    }
   for (hipEvent_t e : c->wait_events) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
   if (c->comm && rccl().ok) (void)rccl().CommDestroy(c->comm);
@@ -330,8 +325,6 @@ int sg_comm_init(sg_handle* h, const void* id, size_t nbytes, int rank, int nran
   const int d = h->cfg.dim;
   HIPCHECK(h, hipSetDevice(h->cfg.device));
   sg_comm_state* c = new sg_comm_state();
-  std::memset(c->send, 0, sizeof(c->send));
-  std::memset(c->recv, 0, sizeof(c->recv));
   std::memset(&c->stats, 0, sizeof(c->stats));
   h->comm = c;
   c->rank = rank;
@@ -353,17 +346,17 @@ int sg_comm_init(sg_handle* h, const void* id, size_t nbytes, int rank, int nran
     (void)sg_halo_bytes(h, SG_FIELD_U, s, &nb);
     c->count[s] = nb / es;
     for (int k = 0; k < 2; ++k) {
-      if (hipMalloc(&c->send[k][s], nb) != hipSuccess || hipMalloc(&c->recv[k][s], nb) != hipSuccess) {
+      if (c->send[k][s].alloc(nb) != hipSuccess || c->recv[k][s].alloc(nb) != hipSuccess) {
         comm_release(h);
         return fail(h, SG_ERR_NOMEM, "hipMalloc of a halo buffer failed");
       }
-      (void)hipMemset(c->send[k][s], 0, nb);
-      (void)hipMemset(c->recv[k][s], 0, nb);
+      (void)hipMemset(c->send[k][s].get(), 0, nb);
+      (void)hipMemset(c->recv[k][s].get(), 0, nb);
     }
     // both fields of a kind read the same ghost buffer: it is consumed by the stage that follows its exchange
     // before the next exchange of that kind starts
-    h->ghost[SG_FIELD_U][s] = h->ghost[SG_FIELD_UH][s] = (const double*)c->recv[0][s];
-    h->ghost[SG_FIELD_S][s] = h->ghost[SG_FIELD_SH][s] = (const double*)c->recv[1][s];
+    h->ghost[SG_FIELD_U][s] = h->ghost[SG_FIELD_UH][s] = (const double*)c->recv[0][s].get();
+    h->ghost[SG_FIELD_S][s] = h->ghost[SG_FIELD_SH][s] = (const double*)c->recv[1][s].get();
   }
   HIPCHECK(h, hipDeviceSynchronize());
   return SG_OK;
@@ -430,8 +423,8 @@ int sg_comm_selftest(sg_handle* h, int64_t* mismatches) {
         hd[i] = selftest_value(c->rank, s, kind, i, h->f32 != 0);
         hf[i] = (float)hd[i];
       }
-      HIPCHECK(h, hipMemcpy(c->send[kind][s], h->f32 ? (const void*)hf.data() : (const void*)hd.data(), n * es, hipMemcpyHostToDevice));
-      HIPCHECK(h, hipMemset(c->recv[kind][s], 0xff, n * es));
+      HIPCHECK(h, hipMemcpy(c->send[kind][s].get(), h->f32 ? (const void*)hf.data() : (const void*)hd.data(), n * es, hipMemcpyHostToDevice));
+      HIPCHECK(h, hipMemset(c->recv[kind][s].get(), 0xff, n * es));
     }
     int rc = exchange(h, kind ? SG_FIELD_S : SG_FIELD_U, nullptr, false);
     if (rc != SG_OK) return rc;
@@ -441,14 +434,14 @@ int sg_comm_selftest(sg_handle* h, int64_t* mismatches) {
       const size_t n = c->count[s];
       hd.resize(n);
       hf.resize(n);
-      HIPCHECK(h, hipMemcpy(h->f32 ? (void*)hf.data() : (void*)hd.data(), c->recv[kind][s], n * es, hipMemcpyDeviceToHost));
+      HIPCHECK(h, hipMemcpy(h->f32 ? (void*)hf.data() : (void*)hd.data(), c->recv[kind][s].get(), n * es, hipMemcpyDeviceToHost));
       for (size_t i = 0; i < n; ++i) {
         const double want = selftest_value(c->peers[s], s ^ 1, kind, i, h->f32 != 0);
         const double got = h->f32 ? (double)hf[i] : hd[i];
         if (!(got == want)) *mismatches += 1;
       }
-      HIPCHECK(h, hipMemset(c->send[kind][s], 0, n * es));
-      HIPCHECK(h, hipMemset(c->recv[kind][s], 0, n * es));
+      HIPCHECK(h, hipMemset(c->send[kind][s].get(), 0, n * es));
+      HIPCHECK(h, hipMemset(c->recv[kind][s].get(), 0, n * es));
     }
   }
   c->stats = keep;
@@ -459,8 +452,8 @@ int sg_comm_selftest(sg_handle* h, int64_t* mismatches) {
 int sg_comm_buffers(sg_handle* h, int kind, int side, void** send, void** recv, size_t* nbytes) {
   if (!h || kind < 0 || kind > 1 || side < 0 || side > 5) return SG_ERR_ARG;
   if (!h->comm) return fail(h, SG_ERR_STATE, "no communicator (sg_comm_init)");
-  if (send) *send = h->comm->send[kind][side];
-  if (recv) *recv = h->comm->recv[kind][side];
+  if (send) *send = h->comm->send[kind][side].get();
+  if (recv) *recv = h->comm->recv[kind][side].get();
   if (nbytes) *nbytes = h->comm->count[side] * (h->f32 ? sizeof(float) : sizeof(double));
   return SG_OK;
 }

@@ -25,42 +25,118 @@ using namespace sg;
 
 struct sg_comm_state;   // comm.cpp: RCCL communicator, peers and halo buffers of the native exchange
 
+// The one owner of a hipMalloc'ed array: freed by its destructor, moved but never copied.  A setter builds its new
+// tables in locals and moves them into the handle only once everything has succeeded, so that a call which fails
+// leaves the handle as it was.
+template <typename T>
+struct DevBuf {
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      reset();
+      std::swap(p_, o.p_);
+    }
+    return *this;
+  }
+  ~DevBuf() { reset(); }
+  T* get() const { return p_; }
+  void reset() {
+    if (p_) (void)hipFree(p_);
+    p_ = nullptr;
+  }
+  hipError_t alloc(size_t n) {   // (an empty array still gets an address: 8 bytes)
+    reset();
+    return hipMalloc((void**)&p_, std::max<size_t>(n * sizeof(T), 8));
+  }
+  hipError_t upload(const T* src, size_t n) {
+    hipError_t e = alloc(n);
+    return (e != hipSuccess || n == 0) ? e : hipMemcpy(p_, src, n * sizeof(T), hipMemcpyHostToDevice);
+  }
+
+ private:
+  T* p_ = nullptr;
+};
+
+// What sg_set_absorption derived from the nodal sigma (sponge_tables.cpp plan_sponge), on the device
+struct SpongeTables {
+  DevBuf<int32_t> slot;    // [cell] -> slot or -1
+  DevBuf<double> B;        // [matrix][nd][nd]
+  DevBuf<double> sigma;    // 2-D tile and 3-D MFMA kernels only (kernels.hpp StageArgs::sponge_sigma)
+  int32_t nslots = 0;      // cells with a sponge matrix of their own
+  DevBuf<int32_t> cells;   // [slot] -> cell: the pre-pass of the F stages (kernels.hpp launch_sponge_pre)
+  DevBuf<int32_t> mat;     // [slot] -> matrix in B (cells with the same nodal sigma share one)
+  DevBuf<char> pre;        // [slot][nd][dim] in the field type
+  int pre_lines = 0;       // pre in line layout, slot = item * gw + w (3-D MFMA family), else a record per slot
+  // cells whose sigma is affine in the reference coordinates take dim + 1 numbers instead of a matrix (kernels.hpp
+  // launch_sponge_pre_affine); the cells that keep a matrix are then a LIST of slots
+  int32_t nmat_slots = 0;  // slots with a matrix (all of them where no cell is affine: mat_slots stays empty)
+  DevBuf<int32_t> mat_slots;
+  int32_t aff_nitems = 0, aff_W = 0;
+  DevBuf<int32_t> aff_items;  // [item] -> (cube group) * ncls + class
+  DevBuf<int32_t> aff_slots;  // [item][gw] -> slot or -1
+  DevBuf<double> aff_coef;    // [slot][dim + 1]
+  DevBuf<double> aff_X;       // [dim][nd][W]
+  DevBuf<int32_t> aff_col;    // [nd][W], empty where the rows are dense
+  DevBuf<double> aff_frag;    // 3-D MFMA family in double: the X_k as row tiles (mfma_frags_dense)
+  int aff_grid = 0;           // persistent grid of the affine pre-pass (sponge_affine_mfma where aff_frag is set), on the handle's device
+  // The pre-pass is B_e u_abs of a FIELD STATE: stages UH1 and U1 both absorb u0 (elastic.py:206-208 in form_uh1 and form_uh2),
+  // UTEMP absorbs the u1 that U1 wrote, and the next step's UH1 and U1 absorb that same u1 - so in the steady state UH1 finds
+  // UTEMP's pre-pass and a step runs ONE pre-pass (UTEMP's); a captured graph computes it afresh at its own first step.
+  // pre_ver / pre_field name the state the buffer holds (sg_handle::fver; ~0: none), pre_key the F stage (output field,
+  // mode) whose pre-pass ran last, pre_regions the regions launched since.
+  int pre_key = -1, pre_regions = 0;
+  uint64_t pre_ver = ~0ull;
+  int pre_field = -1;
+};
+
+// The source of sg_set_source / sg_set_source_separable, on the device
+struct SourceTables {
+  int64_t nnz = 0;
+  int64_t nfirst = 0;       // source nodes are stored with those in cells of SG_REGION_FIRST first
+  DevBuf<int64_t> nodes;    // device offset of component 0 of each node in the field layout
+  DevBuf<double> values;    // [nsteps][nnz][dim*dim]
+  int64_t nsteps = 0;
+  bool is_static = false;   // one time slice that holds at every step
+  std::vector<double> weights;   // separable source: values is one slice, scaled by weights[src_step]
+  DevBuf<double> weights_d;
+  // 2-D tile path: the source is added inside the G stage kernels (StageArgs::src_slot / src_idx)
+  bool fused = false;
+  DevBuf<int32_t> slot, idx;
+};
+
 struct sg_handle {
   sg_config cfg;
   sg_comm_state* comm = nullptr;
   RefElem re;
   MeshDev md;
-  MeshDev* md_dev = nullptr;
-  double* Dt = nullptr;
-  double* Lt = nullptr;
-  double* field[4] = {nullptr, nullptr, nullptr, nullptr};
+  DevBuf<MeshDev> md_dev;
+  DevBuf<double> Dt, Lt;
+  DevBuf<double> field[4];               // double, or float where f32
   size_t field_len[4] = {0, 0, 0, 0};    // doubles, host layout (ncells * nd * comps)
-  size_t field_alloc[4] = {0, 0, 0, 0};  // doubles allocated on the device (layout padding included)
+  size_t field_alloc[4] = {0, 0, 0, 0};  // values allocated on the device (layout padding included)
   bool use_mfma = false;
   bool use_lane = false;
   bool use_tile = false;    // 2-D MFMA tile kernels (kernels_tile2d.hip), gw = 16
   bool use_hexm = false;    // hexahedra DQ_3 / DQ_4 (kernels_hexm.hip), gw = 16
   int f32 = 0;              // sg_config.dtype = 1: fields, halo buffers, operator tiles and arithmetic are float (MFMA path)
   bool sym = false;         // MFMA path: all stress fields symmetric -> kernels touch only the i <= j lines
-  int* sym_flag = nullptr;  // device word set by an upload that is not symmetric
+  DevBuf<int> sym_flag;     // device word set by an upload that is not symmetric
   // active (cell group, class) items of each region of a split stage (MFMA / lane paths), by sg_region
-  int32_t* region_items[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  DevBuf<int32_t> region_items[5];
   int32_t region_nitems[5] = {-1, -1, -1, -1, -1};  // -1: not built yet
   bool region_whole[5] = {false, false, false, false, false};  // no listed cell group is cut by the region's boxes
-  double* fragF = nullptr;  // MFMA operator fragment tables (device)
-  double* fragG = nullptr;
-  double* fragL = nullptr;
+  DevBuf<double> fragF, fragG, fragL;  // MFMA operator fragment tables (float where f32)
   // G stages with the factorised volume term (kernels_mfma.hip mfma_stage_G<.., FACT = 1>; double, degrees 3 and 4;
-  // SEIGEN_HIP_GQ): the Q tiles and the P_r tiles, or null
-  double* fragQ = nullptr;
-  double* fragP = nullptr;
-  double* staging = nullptr;  // host-layout staging buffer for layout conversion
+  // SEIGEN_HIP_GQ): the Q tiles and the P_r tiles, or empty
+  DevBuf<double> fragQ, fragP;
+  DevBuf<double> staging;  // host-layout staging buffer for layout conversion
   // large transfers: two pinned host slots + two device slots, so that the DMA of one chunk, the
   // layout kernel of the next and the host-side copy of the previous one overlap
   double* pin[2] = {nullptr, nullptr};
-  double* dstage[2] = {nullptr, nullptr};
+  DevBuf<double> dstage[2];
   hipEvent_t xfer_ev[2] = {nullptr, nullptr};
-  unsigned long long* dbg = nullptr;  // SEIGEN_HIP_STAMPS=1 (diagnostic builds): [kind][8] cycle sums
+  DevBuf<unsigned long long> dbg;  // SEIGEN_HIP_STAMPS=1 (diagnostic builds): [kind][8] cycle sums
   size_t staging_len = 0;
   int64_t ncells = 0;
   int ncls = 0;
@@ -68,56 +144,19 @@ struct sg_handle {
   bool params_set = false;
   double rho = 1.0, dt = 0.0, lam0 = 0.0, mu0 = 0.0;
   int per_cell = 0;
-  double* lam_d = nullptr;
-  double* mu_d = nullptr;
-  double* rho2_d = nullptr;  // per-cell density factors [cell][2] (kernels.hpp), or null
+  DevBuf<double> lam_d, mu_d;
+  DevBuf<double> rho2_d;     // per-cell density factors [cell][2] (kernels.hpp), or empty
   int rho_physical = 0;      // scalar density: 0 = rho*u0 + ..., 1 = u0 + (...)/rho
-  // sponge
-  int32_t* sponge_slot = nullptr;
-  double* sponge_B = nullptr;
-  double* sponge_sigma = nullptr;   // 2-D tile and 3-D MFMA kernels only (kernels.hpp StageArgs::sponge_sigma)
-  int32_t sponge_nslots = 0;        // cells with a sponge matrix of their own
-  int32_t* sponge_cells = nullptr;  // [slot] -> cell: the pre-pass of the F stages (kernels.hpp launch_sponge_pre)
-  int32_t* sponge_mat = nullptr;    // [slot] -> matrix in sponge_B (cells with the same nodal sigma share one)
-  void* sponge_pre = nullptr;       // [slot][nd][dim] in the field type
-  // cells whose sigma is affine in the reference coordinates take dim + 1 numbers instead of a matrix (kernels.hpp
-  // launch_sponge_pre_affine); the cells that keep a matrix are then a LIST of slots
-  int sponge_pre_lines = 0;             // sponge_pre in line layout, slot = item * gw + w (3-D MFMA family), else a record per slot
-  int32_t sponge_nmat_slots = 0;        // slots with a matrix (all of them where no cell is affine: sponge_mat_slots stays null)
-  int32_t* sponge_mat_slots = nullptr;
-  int32_t sponge_aff_nitems = 0, sponge_aff_W = 0;
-  int32_t* sponge_aff_items = nullptr;  // [item] -> (cube group) * ncls + class
-  int32_t* sponge_aff_slots = nullptr;  // [item][gw] -> slot or -1
-  double* sponge_aff_coef = nullptr;    // [slot][dim + 1]
-  double* sponge_aff_X = nullptr;       // [dim][nd][W]
-  int32_t* sponge_aff_col = nullptr;    // [nd][W], null where the rows are dense
-  double* sponge_aff_frag = nullptr;    // 3-D MFMA family in double: the X_k as row tiles (mfma_frags_dense)
-  int sponge_pre_key = -1, sponge_pre_regions = 0;   // the F stage (output field, mode) whose pre-pass ran last, and the regions launched since
-  // The pre-pass is B_e u_abs of a FIELD STATE: stages UH1 and U1 both absorb u0 (elastic.py:206-208 in form_uh1 and form_uh2),
-  // so the second of them finds the first one's result - two pre-passes per step instead of three.  fver counts the writes to
-  // each field (stage outputs, uploads); sponge_pre_ver / _field name the state the buffer holds (~0: none).
-  uint64_t fver[4] = {0, 0, 0, 0};
-  uint64_t sponge_pre_ver = ~0ull;
-  int sponge_pre_field = -1;
-  // source
-  int64_t src_nnz = 0;
-  int64_t src_nfirst = 0;  // source nodes are stored with those in cells of SG_REGION_FIRST first
-  int64_t* src_nodes = nullptr;
-  double* src_values = nullptr;  // [nsteps][nnz][dim*dim]
-  int64_t src_nsteps = 0;
+  SpongeTables sponge;
+  uint64_t fver[4] = {0, 0, 0, 0};   // writes to each field (mark_field_written)
+  SourceTables src;
   int64_t src_step = 0;
-  bool src_static = false;  // one time slice that holds at every step
-  std::vector<double> src_weights;  // separable source: src_values is one slice, scaled by src_weights[src_step]
   // graph replay with a source: the step index lives in a device word that the captured launches read and a one-thread
-  // launch bumps at the end of every step (kernels.hpp SrcStep); sg_step sets it to src_step before it replays
-  int64_t* src_ctr_d = nullptr;
-  double* src_weights_d = nullptr;
+  // launch bumps at the end of every step (kernels.hpp SrcStep); sg_step sets it to src_step before it replays.
+  // Allocated by the first source and kept.
+  DevBuf<int64_t> src_ctr_d;
   bool capture_src = false;   // stage launches issued now (a capture) take slice and weight from src_ctr_d
   bool graph_src = false;     // the captured graphs contain the source launches
-  // 2-D tile path: the source is added inside the G stage kernels (StageArgs::src_slot / src_idx)
-  bool src_fused = false;
-  int32_t* src_slot_d = nullptr;
-  int32_t* src_idx_d = nullptr;
   // halo
   const double* ghost[4][6];
   // execution
@@ -131,9 +170,9 @@ struct sg_handle {
   hipStream_t stream2 = nullptr;
   hipEvent_t ev_stage = nullptr, ev_second = nullptr;
   bool second_pending = false;
-  int32_t* nbr_tab = nullptr;   // MFMA path: per-item neighbour table (StageArgs::nbr_tab)
-  MfmaConst* mk_dev = nullptr;  // MFMA path: scalar-load copy of the mesh constants (kernels.hpp MfmaConst)
-  int32_t* ftab_dev = nullptr;  // MFMA path, F stages: tabulated trace offsets (kernels.hpp mfma_trace_offsets)
+  DevBuf<int32_t> nbr_tab;   // MFMA path: per-item neighbour table (StageArgs::nbr_tab)
+  DevBuf<MfmaConst> mk_dev;  // MFMA path: scalar-load copy of the mesh constants (kernels.hpp MfmaConst)
+  DevBuf<int32_t> ftab_dev;  // MFMA path, F stages: tabulated trace offsets (kernels.hpp mfma_trace_offsets)
   int grid_blocks = 0;  // persistent grid of the MFMA stage kernels: while an exchange is in flight ...
   int order_chunk = 0;  // MFMA path: items per XCD chunk of whole-block launches (StageArgs::order_chunk)
   int grid_full = 0;    // ... and otherwise (every block slot of the device)
@@ -176,6 +215,10 @@ inline int fail(sg_handle* h, int code, const std::string& msg) {
 }
 
 inline bool field_is_stress(int f) { return f == SG_FIELD_S || f == SG_FIELD_SH; }
+
+// Every path that changes h->field[f] - stage outputs, uploads, graph replays, the mirror of leave_sym_mode - calls this:
+// the sponge pre-pass of a field state (SpongeTables::pre_ver) is reused as long as fver says the field still holds it.
+inline void mark_field_written(sg_handle* h, int f) { h->fver[f] += 1; }
 
 // work queued on `stream` from here on comes after the SECOND launch that may still run on stream2
 inline int join_second(sg_handle* h) {

@@ -661,7 +661,7 @@ __global__ __launch_bounds__(256) void sponge_pre_affine_kernel(const T* __restr
     }
     __syncthreads();
     // thread -> (cell w, node a); the results stay in registers until every thread has read its operands
-    constexpr int MAXR = 8;     // rounds of (w, a) pairs per thread: gw * nd <= MAXR * 256 (checked by the launcher)
+    constexpr int MAXR = 8;     // rounds of (w, a) pairs per thread: gw * nd <= MAXR * 256 (checked at set-up: SG_SPONGE_AFFINE_MAX_ROWS)
     double res[MAXR][DIM];
 #pragma unroll
     for (int r = 0; r < MAXR; ++r) {
@@ -715,17 +715,21 @@ __global__ __launch_bounds__(256) void sponge_pre_affine_kernel(const T* __restr
 }
 
 // the instantiations that may need more than 64 KB of dynamic LDS (hexahedra DQ_4) are told so ONCE, at set-up time
-// (sg_set_absorption) - not at the first launch, which may sit inside a stream capture
-int prepare_sponge_pre_affine(int dim, int f32, size_t lds) {
-  if (lds <= ((size_t)64 << 10)) return 0;
-  const void* k = nullptr;
-  if (f32)
-    k = dim == 1 ? (const void*)sponge_pre_affine_kernel<float, 1> : dim == 2 ? (const void*)sponge_pre_affine_kernel<float, 2>
-                                                                              : (const void*)sponge_pre_affine_kernel<float, 3>;
-  else
-    k = dim == 1 ? (const void*)sponge_pre_affine_kernel<double, 1> : dim == 2 ? (const void*)sponge_pre_affine_kernel<double, 2>
-                                                                               : (const void*)sponge_pre_affine_kernel<double, 3>;
-  return (int)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+// (sg_set_absorption) - not at the first launch, which may sit inside a stream capture.  The grid: at most four blocks per CU,
+// as many as the LDS holds.
+int prepare_sponge_pre_affine(int dim, int f32, size_t lds, int ncu) {
+  if (lds > ((size_t)64 << 10)) {
+    const void* k = nullptr;
+    if (f32)
+      k = dim == 1 ? (const void*)sponge_pre_affine_kernel<float, 1> : dim == 2 ? (const void*)sponge_pre_affine_kernel<float, 2>
+                                                                                : (const void*)sponge_pre_affine_kernel<float, 3>;
+    else
+      k = dim == 1 ? (const void*)sponge_pre_affine_kernel<double, 1> : dim == 2 ? (const void*)sponge_pre_affine_kernel<double, 2>
+                                                                                 : (const void*)sponge_pre_affine_kernel<double, 3>;
+    if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return -1;
+  }
+  const int per_cu = (int)(((size_t)160 << 10) / (lds + 512)) < 1 ? 1 : (int)(((size_t)160 << 10) / (lds + 512));
+  return ncu * (per_cu > 4 ? 4 : per_cu);
 }
 
 size_t sponge_pre_affine_lds(int W, int has_col, int nd, int dim, int gw) {
@@ -734,19 +738,11 @@ size_t sponge_pre_affine_lds(int W, int has_col, int nd, int dim, int gw) {
 }
 
 int launch_sponge_pre_affine(const void* uabs, const double* X, const int32_t* col, int W, const int32_t* items, const int32_t* item_slots,
-                             const double* coef, void* sp, int32_t nitems, int nd, int dim, int gw, int lines, int f32, void* stream) {
+                             const double* coef, void* sp, int32_t nitems, int nd, int dim, int gw, int lines, int f32, int grid,
+                             void* stream) {
   if (nitems <= 0) return 0;
   const int threads = 256;
-  if (gw * nd > 8 * threads) return (int)hipErrorInvalidValue;      // MAXR of the kernel
   const size_t lds = sponge_pre_affine_lds(W, col != nullptr, nd, dim, gw);
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-      ncu = 256;
-  }
-  const int per_cu = (int)(((size_t)160 << 10) / (lds + 512)) < 1 ? 1 : (int)(((size_t)160 << 10) / (lds + 512));
-  long grid = (long)ncu * (per_cu > 4 ? 4 : per_cu);
   if (grid > nitems) grid = nitems;
 #define SG_AFF_LAUNCH(TT, DD)                                                                                                     \
   do {                                                                                                                          \

@@ -251,13 +251,17 @@ int launch_sponge_pre(const void* uabs, const double* B, const int32_t* cells, c
 // element-constant X[k][a][j] (row a in ELL form: column col[a][j], or j itself where col is null), coef[slot][dim + 1] = s;
 // items[n] = (cube group) * ncls + class of the n-th item that holds such a cell, item_slots[n][gw] its cells' slots (-1: none)
 int launch_sponge_pre_affine(const void* uabs, const double* X, const int32_t* col, int W, const int32_t* items, const int32_t* item_slots,
-                             const double* coef, void* sp, int32_t nitems, int nd, int dim, int gw, int lines, int f32, void* stream);
+                             const double* coef, void* sp, int32_t nitems, int nd, int dim, int gw, int lines, int f32, int grid, void* stream);
+// (gw * nd <= SG_SPONGE_AFFINE_MAX_ROWS: the kernel's rounds of (cell, node) rows per thread; checked at set-up, sg_set_absorption)
+constexpr int SG_SPONGE_AFFINE_MAX_ROWS = 8 * 256;
 size_t sponge_pre_affine_lds(int W, int has_col, int nd, int dim, int gw);
-int prepare_sponge_pre_affine(int dim, int f32, size_t lds);   // once, outside any stream capture: allow that much dynamic LDS
+// once, at set-up and outside any stream capture: allow that much dynamic LDS; returns the launch's grid on a device of ncu
+// CUs (the `grid` of launch_sponge_pre_affine), <= 0 on failure
+int prepare_sponge_pre_affine(int dim, int f32, size_t lds, int ncu);
 // ... on the matrix pipe for the 3-D MFMA family in double (kernels_mfma.hip): fragX = mfma_frags_dense of the three X_k
-int prepare_sponge_affine_mfma(int P);   // once, at set-up: the occupancy query behind the launch's grid size
+int prepare_sponge_affine_mfma(int P, int ncu);   // once, at set-up: the blocks a device of ncu CUs holds (the launch's `grid`)
 int launch_sponge_affine_mfma(int P, const void* uabs, const double* fragX, const int32_t* items, const int32_t* item_slots,
-                              const double* coef, void* sp, int32_t nitems, void* stream);
+                              const double* coef, void* sp, int32_t nitems, int grid, void* stream);
 // the device-side step counter of SrcStep: *ctr = value (add = 0) or *ctr += value (add = 1), one thread
 int launch_step_counter(int64_t* ctr, int64_t value, int add, void* stream);
 

@@ -1353,39 +1353,30 @@ __global__ __launch_bounds__(512) void sponge_affine_mfma(const double* __restri
   }
 }
 
-// blocks of eight waves the device holds of the degree's instantiation (asked from the runtime once: registers and the tiles'
-// LDS decide - two per CU at degree 4).  sg_set_absorption asks at set-up (prepare_...), i.e. outside any stream capture.
-static int sponge_affine_resident(int P) {
-  static int resident[5] = {0, 0, 0, 0, 0};
-  if (P < 1 || P > 4) return 0;
-  if (resident[P] == 0) {
-    int per_cu = 0, dev = 0, ncu = 0;
-    const void* k = P == 1 ? (const void*)sponge_affine_mfma<1> : P == 2 ? (const void*)sponge_affine_mfma<2>
-                  : P == 3 ? (const void*)sponge_affine_mfma<3> : (const void*)sponge_affine_mfma<4>;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 512, 0) != hipSuccess || per_cu <= 0) per_cu = 2;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-      ncu = 256;
-    resident[P] = per_cu * ncu;
-  }
-  return resident[P];
+// blocks of eight waves a device of ncu CUs holds of the degree's instantiation (registers and the tiles' LDS decide - two per
+// CU at degree 4).  sg_set_absorption asks at set-up, i.e. outside any stream capture.
+int prepare_sponge_affine_mfma(int P, int ncu) {
+  if (P < 1 || P > 4) return -1;
+  int per_cu = 0;
+  const void* k = P == 1 ? (const void*)sponge_affine_mfma<1> : P == 2 ? (const void*)sponge_affine_mfma<2>
+                : P == 3 ? (const void*)sponge_affine_mfma<3> : (const void*)sponge_affine_mfma<4>;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 512, 0) != hipSuccess || per_cu <= 0) per_cu = 2;
+  return per_cu * ncu;
 }
-int prepare_sponge_affine_mfma(int P) { return sponge_affine_resident(P) > 0 ? 0 : -1; }
 
 int launch_sponge_affine_mfma(int P, const void* uabs, const double* fragX, const int32_t* items, const int32_t* item_slots,
-                              const double* coef, void* sp, int32_t nitems, void* stream) {
+                              const double* coef, void* sp, int32_t nitems, int grid, void* stream) {
   if (nitems <= 0) return 0;
-  // a persistent grid of exactly the resident blocks: more would run a second, partly empty round
-  const int resident = sponge_affine_resident(P);
-  if (resident <= 0) return -1;
+  // a persistent grid of exactly the resident blocks (`grid`): more would run a second, partly empty round
   long blocks = ((long)nitems * 3 + 7) / 8;
-  if (blocks > resident) blocks = resident;
-  const dim3 grid((unsigned)blocks), block(512);
+  if (blocks > grid) blocks = grid;
+  const dim3 dgrid((unsigned)blocks), block(512);
   hipStream_t s = (hipStream_t)stream;
   switch (P) {
-    case 1: hipLaunchKernelGGL(sponge_affine_mfma<1>, grid, block, 0, s, (const double*)uabs, fragX, items, item_slots, coef, (double*)sp, nitems); break;
-    case 2: hipLaunchKernelGGL(sponge_affine_mfma<2>, grid, block, 0, s, (const double*)uabs, fragX, items, item_slots, coef, (double*)sp, nitems); break;
-    case 3: hipLaunchKernelGGL(sponge_affine_mfma<3>, grid, block, 0, s, (const double*)uabs, fragX, items, item_slots, coef, (double*)sp, nitems); break;
-    case 4: hipLaunchKernelGGL(sponge_affine_mfma<4>, grid, block, 0, s, (const double*)uabs, fragX, items, item_slots, coef, (double*)sp, nitems); break;
+    case 1: hipLaunchKernelGGL(sponge_affine_mfma<1>, dgrid, block, 0, s, (const double*)uabs, fragX, items, item_slots, coef, (double*)sp, nitems); break;
+    case 2: hipLaunchKernelGGL(sponge_affine_mfma<2>, dgrid, block, 0, s, (const double*)uabs, fragX, items, item_slots, coef, (double*)sp, nitems); break;
+    case 3: hipLaunchKernelGGL(sponge_affine_mfma<3>, dgrid, block, 0, s, (const double*)uabs, fragX, items, item_slots, coef, (double*)sp, nitems); break;
+    case 4: hipLaunchKernelGGL(sponge_affine_mfma<4>, dgrid, block, 0, s, (const double*)uabs, fragX, items, item_slots, coef, (double*)sp, nitems); break;
     default: return -1;
   }
   return (int)hipGetLastError();

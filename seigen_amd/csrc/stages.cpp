@@ -5,7 +5,7 @@
 // ---- stage launches --------------------------------------------------------------------
 
 static bool source_active(const sg_handle* h) {
-  return h->src_nnz != 0 && (h->src_static || h->src_step < h->src_nsteps);
+  return h->src.nnz != 0 && (h->src.is_static || h->src_step < h->src.nsteps);
 }
 // launches of a capture: slice and weight of the step the device-side counter names (kernels.hpp SrcStep)
 static SrcStep source_stepper(const sg_handle* h) {
@@ -13,18 +13,18 @@ static SrcStep source_stepper(const sg_handle* h) {
   std::memset(&ss, 0, sizeof(ss));
   if (!h->capture_src) return ss;
   const int64_t dd = (int64_t)h->cfg.dim * h->cfg.dim;
-  ss.ctr = h->src_ctr_d;
-  ss.nsteps = h->src_nsteps;
-  ss.is_static = h->src_static ? 1 : 0;
-  ss.weights = h->src_weights.empty() ? nullptr : h->src_weights_d;
-  ss.stride = (h->src_static || !h->src_weights.empty()) ? 0 : h->src_nnz * dd;
+  ss.ctr = h->src_ctr_d.get();
+  ss.nsteps = h->src.nsteps;
+  ss.is_static = h->src.is_static ? 1 : 0;
+  ss.weights = h->src.weights.empty() ? nullptr : h->src.weights_d.get();
+  ss.stride = (h->src.is_static || !h->src.weights.empty()) ? 0 : h->src.nnz * dd;
   if (ss.stride == 0 && ss.weights == nullptr) ss.is_static = 1;
   return ss;
 }
 // separable source: the one stored slice, scaled by this step's weight
-static bool source_one_slice(const sg_handle* h) { return h->src_static || !h->src_weights.empty(); }
+static bool source_one_slice(const sg_handle* h) { return h->src.is_static || !h->src.weights.empty(); }
 static double source_scale(const sg_handle* h) {
-  return h->src_weights.empty() ? 1.0 : h->src_weights[(size_t)h->src_step];
+  return h->src.weights.empty() ? 1.0 : h->src.weights[(size_t)h->src_step];
 }
 
 static int run_op(sg_handle* h, int kind, int in_f, int out_f, int aux_f, int mode, double c_self, double c_aux,
@@ -32,94 +32,95 @@ static int run_op(sg_handle* h, int kind, int in_f, int out_f, int aux_f, int mo
                   double src_coef = 1.0) {
   StageArgs a;
   std::memset(&a, 0, sizeof(a));
-  a.in = h->field[in_f];
-  a.out = h->field[out_f];
-  a.aux = aux_f >= 0 ? h->field[aux_f] : nullptr;
-  a.uabs = h->field[uabs_f];
+  a.in = h->field[in_f].get();
+  a.out = h->field[out_f].get();
+  a.aux = aux_f >= 0 ? h->field[aux_f].get() : nullptr;
+  a.uabs = h->field[uabs_f].get();
   for (int s = 0; s < 6; ++s) {
     a.ghost[s] = h->ghost[in_f][s];
     // required for interior launches too: masked boundary lanes still form (and load through) the pointer
     if (h->md.has_nbr[s] && !a.ghost[s])
       return fail(h, SG_ERR_STATE, "stage needs a halo buffer that was not attached (sg_halo_attach)");
   }
-  a.Dt = h->Dt;
-  a.Lt = h->Lt;
-  a.md = h->md_dev;
-  a.mk = h->mk_dev;
-  a.ftab = h->ftab_dev;
-  a.nbr_tab = h->nbr_tab;
+  a.Dt = h->Dt.get();
+  a.Lt = h->Lt.get();
+  a.md = h->md_dev.get();
+  a.mk = h->mk_dev.get();
+  a.ftab = h->ftab_dev.get();
+  a.nbr_tab = h->nbr_tab.get();
   a.name_out = h->name_out;
   a.all_active = region == SG_REGION_ALL ? 1 : 0;
   a.tensor = h->re.kind == KIND_TENSOR ? 1 : 0;
-  a.fragV = (kind == 0) ? h->fragF : h->fragG;
-  a.fragL = h->fragL;
-  if (kind == 1 && h->fragQ) {      // G stages with the factorised volume term
-    a.fragV = h->fragP;
-    a.fragQ = h->fragQ;
+  a.fragV = (kind == 0) ? h->fragF.get() : h->fragG.get();
+  a.fragL = h->fragL.get();
+  if (kind == 1 && h->fragQ.get()) {      // G stages with the factorised volume term
+    a.fragV = h->fragP.get();
+    a.fragQ = h->fragQ.get();
   }
   a.sym = h->sym ? 1 : 0;
   a.f32 = h->f32;
-  a.dbg = h->dbg ? h->dbg + 8 * (kind * 2 + (mode ? 1 : 0)) : nullptr;
-  a.sponge_slot = (kind == 0) ? h->sponge_slot : nullptr;
-  a.sponge_B = h->sponge_B;
-  a.sponge_sigma = (kind == 0) ? h->sponge_sigma : nullptr;
-  a.sponge_pre = (kind == 0) ? h->sponge_pre : nullptr;
+  SpongeTables& sp = h->sponge;
+  a.dbg = h->dbg.get() ? h->dbg.get() + 8 * (kind * 2 + (mode ? 1 : 0)) : nullptr;
+  a.sponge_slot = (kind == 0) ? sp.slot.get() : nullptr;
+  a.sponge_B = sp.B.get();
+  a.sponge_sigma = (kind == 0) ? sp.sigma.get() : nullptr;
+  a.sponge_pre = (kind == 0) ? sp.pre.get() : nullptr;
   // the first launch of an F stage - whichever region the caller starts with: the same stage again, or a region it has
   // already seen, is the next instance of the stage
   bool first_of_stage = false;
-  if (kind == 0 && h->sponge_pre && !h->name_out) {
+  if (kind == 0 && sp.pre.get() && !h->name_out) {
     const int key = out_f * 4 + mode;
-    first_of_stage = key != h->sponge_pre_key || (h->sponge_pre_regions & (1 << region)) != 0 || region == SG_REGION_ALL;
-    if (first_of_stage) h->sponge_pre_regions = 0;
-    h->sponge_pre_key = key;
-    h->sponge_pre_regions |= 1 << region;
+    first_of_stage = key != sp.pre_key || (sp.pre_regions & (1 << region)) != 0 || region == SG_REGION_ALL;
+    if (first_of_stage) sp.pre_regions = 0;
+    sp.pre_key = key;
+    sp.pre_regions |= 1 << region;
   }
-  if (first_of_stage && h->sponge_pre_field == uabs_f && h->sponge_pre_ver == h->fver[uabs_f]) first_of_stage = false;   // the buffer holds it
+  if (first_of_stage && sp.pre_field == uabs_f && sp.pre_ver == h->fver[uabs_f]) first_of_stage = false;   // the buffer holds it
   if (first_of_stage) {
-    h->sponge_pre_field = uabs_f;
-    h->sponge_pre_ver = h->fver[uabs_f];
+    sp.pre_field = uabs_f;
+    sp.pre_ver = h->fver[uabs_f];
     // B_e u_abs of the cells with a sponge matrix, before anything of the stage writes
-    if (launch_sponge_pre(a.uabs, h->sponge_B, h->sponge_cells, h->sponge_mat, h->sponge_mat_slots, h->sponge_pre, h->sponge_nmat_slots,
-                          h->re.nd, h->cfg.dim, h->ncls, (int)h->md.gw, h->sponge_pre_lines, h->f32, h->stream) != 0)
+    if (launch_sponge_pre(a.uabs, sp.B.get(), sp.cells.get(), sp.mat.get(), sp.mat_slots.get(), sp.pre.get(), sp.nmat_slots, h->re.nd,
+                          h->cfg.dim, h->ncls, (int)h->md.gw, sp.pre_lines, h->f32, h->stream) != 0)
       return fail(h, SG_ERR_DEVICE, "sponge pre-pass launch failed");
     // ... and of the cells whose sigma is affine in the reference coordinates: dim + 1 numbers per cell, element-constant matrices
-    const int arc = h->sponge_aff_frag
-                        ? launch_sponge_affine_mfma(h->cfg.degree, a.uabs, h->sponge_aff_frag, h->sponge_aff_items, h->sponge_aff_slots,
-                                                    h->sponge_aff_coef, h->sponge_pre, h->sponge_aff_nitems, h->stream)
-                        : launch_sponge_pre_affine(a.uabs, h->sponge_aff_X, h->sponge_aff_col, h->sponge_aff_W, h->sponge_aff_items,
-                                                   h->sponge_aff_slots, h->sponge_aff_coef, h->sponge_pre, h->sponge_aff_nitems, h->re.nd,
-                                                   h->cfg.dim, (int)h->md.gw, h->sponge_pre_lines, h->f32, h->stream);
+    const int arc = sp.aff_frag.get()
+                        ? launch_sponge_affine_mfma(h->cfg.degree, a.uabs, sp.aff_frag.get(), sp.aff_items.get(), sp.aff_slots.get(),
+                                                    sp.aff_coef.get(), sp.pre.get(), sp.aff_nitems, sp.aff_grid, h->stream)
+                        : launch_sponge_pre_affine(a.uabs, sp.aff_X.get(), sp.aff_col.get(), sp.aff_W, sp.aff_items.get(),
+                                                   sp.aff_slots.get(), sp.aff_coef.get(), sp.pre.get(), sp.aff_nitems, h->re.nd,
+                                                   h->cfg.dim, (int)h->md.gw, sp.pre_lines, h->f32, sp.aff_grid, h->stream);
     if (arc != 0) return fail(h, SG_ERR_DEVICE, "affine-sigma sponge pre-pass launch failed");
     // SECOND runs on its own stream after ev_stage - "everything before this stage's FIRST" - and reads the pre-pass too
     if (region == SG_REGION_FIRST && h->overlap && h->first_recorded_stage >= 0) HIPCHECK(h, hipEventRecord(h->ev_stage, h->stream));
   }
-  if (!h->name_out) h->fver[out_f] += 1;     // (after the pre-pass decision: an in-place stage absorbs the state it overwrites)
-  a.lam = h->lam_d;
-  a.mu = h->mu_d;
+  if (!h->name_out) mark_field_written(h, out_f);     // (after the pre-pass decision: an in-place stage absorbs the state it overwrites)
+  a.lam = h->lam_d.get();
+  a.mu = h->mu_d.get();
   a.lam0 = h->lam0;
   a.mu0 = h->mu0;
   a.per_cell = h->per_cell;
-  a.rho2 = (kind == 0 && mode == 1 && density) ? h->rho2_d : nullptr;   // stage U1 only
+  a.rho2 = (kind == 0 && mode == 1 && density) ? h->rho2_d.get() : nullptr;   // stage U1 only
   a.src_coef = src_coef;
   a.mode = mode;
   a.c_self = c_self;
   a.c_aux = c_aux;
   a.c_new = c_new;
-  if (kind == 0 && in_f == SG_FIELD_S && mode == 0 && h->capture_src && h->src_fused) {
+  if (kind == 0 && in_f == SG_FIELD_S && mode == 0 && h->capture_src && h->src.fused) {
     // stage UH1 of a captured step on the tile path: the launch that opens the step also names it
     a.src_step = source_stepper(h);
     a.src_bump = 1;
   }
-  if (with_source && h->src_fused && h->capture_src) {     // ... of the step the device-side counter names
-    a.src_slot = h->src_slot_d;
-    a.src_idx = h->src_idx_d;
-    a.src_vals = h->src_values;
+  if (with_source && h->src.fused && h->capture_src) {     // ... of the step the device-side counter names
+    a.src_slot = h->src.slot.get();
+    a.src_idx = h->src.idx.get();
+    a.src_vals = h->src.values.get();
     a.src_scale = 1.0;
     a.src_step = source_stepper(h);
-  } else if (with_source && h->src_fused && source_active(h)) {  // tile path: the G kernel adds this step's source values
-    a.src_slot = h->src_slot_d;
-    a.src_idx = h->src_idx_d;
-    a.src_vals = h->src_values + (size_t)(source_one_slice(h) ? 0 : h->src_step) * h->src_nnz * h->cfg.dim * h->cfg.dim;
+  } else if (with_source && h->src.fused && source_active(h)) {  // tile path: the G kernel adds this step's source values
+    a.src_slot = h->src.slot.get();
+    a.src_idx = h->src.idx.get();
+    a.src_vals = h->src.values.get() + (size_t)(source_one_slice(h) ? 0 : h->src_step) * h->src.nnz * h->cfg.dim * h->cfg.dim;
     a.src_scale = source_scale(h);
   }
   std::vector<Box> boxes;
@@ -142,7 +143,7 @@ static int run_op(sg_handle* h, int kind, int in_f, int out_f, int aux_f, int mo
     a.grid_blocks = (region == SG_REGION_INTERIOR || region == SG_REGION_SECOND) ? h->grid_blocks : h->grid_full;
     // (the sponge is part of F only, and only cells with a matrix of their own make items differ in cost: then one item per
     // wave on the prime-strided grid)
-    if (h->use_tile) a.grid_blocks = (h->sponge_nslots > 0 && kind == 0) ? h->tile_grid_sponge : h->tile_grid;
+    if (h->use_tile) a.grid_blocks = (sp.nslots > 0 && kind == 0) ? h->tile_grid_sponge : h->tile_grid;
     a.item_list = nullptr;
     a.nlist = 0;
     a.order_chunk = (h->use_mfma && !a.spread && kind == 0) ? h->order_chunk : 0;
@@ -152,9 +153,7 @@ static int run_op(sg_handle* h, int kind, int in_f, int out_f, int aux_f, int mo
       // (a shell is whole z-layers of groups, i.e. the first items of XCD 0 and the last of XCD 7:
       // skipping them inside an even split of all items would leave the launch as long as before);
       // the shell launch deals its few items round-robin over all waves.
-      int32_t*& list = h->region_items[region];
-      int32_t& nlist = h->region_nitems[region];
-      if (nlist < 0) {
+      if (h->region_nitems[region] < 0) {
         const int64_t gw = h->md.gw, ngroups = h->md.ncube_pad / gw;
         std::vector<char> hit((size_t)ngroups, 0);
         std::vector<int32_t> cnt((size_t)ngroups, 0);
@@ -172,19 +171,18 @@ static int run_op(sg_handle* h, int kind, int in_f, int out_f, int aux_f, int mo
         bool whole = true;
         for (int64_t g = 0; g < ngroups; ++g)
           if (hit[(size_t)g] && cnt[(size_t)g] != std::min<int64_t>(gw, h->md.ncube - g * gw)) whole = false;
-        h->region_whole[region] = whole;
         std::vector<int32_t> items;
         for (int64_t g = 0; g < ngroups; ++g)
           if (hit[(size_t)g])
             for (int k = 0; k < h->ncls; ++k) items.push_back((int32_t)(g * h->ncls + k));
-        nlist = (int32_t)items.size();
-        if (!items.empty()) {
-          HIPCHECK(h, hipMalloc((void**)&list, items.size() * sizeof(int32_t)));
-          HIPCHECK(h, hipMemcpy(list, items.data(), items.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-        }
+        DevBuf<int32_t> list;
+        if (!items.empty()) HIPCHECK(h, list.upload(items.data(), items.size()));
+        h->region_items[region] = std::move(list);
+        h->region_nitems[region] = (int32_t)items.size();
+        h->region_whole[region] = whole;
       }
-      a.item_list = list;
-      a.nlist = nlist;
+      a.item_list = h->region_items[region].get();
+      a.nlist = h->region_nitems[region];
       if ((h->use_mfma || h->use_hexm) && h->region_whole[region] && !h->no_whole) a.all_active = 1;
     }
     a.nitems = a.item_list ? a.nlist : (int32_t)std::min<int64_t>((h->md.ncube_pad / h->md.gw) * h->ncls, INT32_MAX);
@@ -212,20 +210,20 @@ static int run_op(sg_handle* h, int kind, int in_f, int out_f, int aux_f, int mo
 // the source lives on single nodes: added to each part of a split stage right after the launch
 // that wrote it (INTERIOR + BOUNDARY: all of it after the second launch)
 static int add_source(sg_handle* h, int field, double coef, int region = SG_REGION_ALL) {
-  if (h->src_fused || h->name_out) return SG_OK;  // added by the stage kernel (run_op with_source) / a naming pass launches nothing
-  if (h->src_nnz == 0 || region == SG_REGION_INTERIOR) return SG_OK;
-  if (!h->capture_src && !h->src_static && h->src_step >= h->src_nsteps) return SG_OK;
+  if (h->src.fused || h->name_out) return SG_OK;  // added by the stage kernel (run_op with_source) / a naming pass launches nothing
+  if (h->src.nnz == 0 || region == SG_REGION_INTERIOR) return SG_OK;
+  if (!h->capture_src && !h->src.is_static && h->src_step >= h->src.nsteps) return SG_OK;
   const int d = h->cfg.dim;
-  int64_t off = 0, cnt = h->src_nnz;
-  if (region == SG_REGION_FIRST) cnt = h->src_nfirst;
+  int64_t off = 0, cnt = h->src.nnz;
+  if (region == SG_REGION_FIRST) cnt = h->src.nfirst;
   if (region == SG_REGION_SECOND) {
-    off = h->src_nfirst;
-    cnt = h->src_nnz - h->src_nfirst;
+    off = h->src.nfirst;
+    cnt = h->src.nnz - h->src.nfirst;
   }
   if (cnt == 0) return SG_OK;
   const SrcStep ss = source_stepper(h);
-  const double* vals = h->src_values + ((size_t)((source_one_slice(h) || ss.ctr) ? 0 : h->src_step) * h->src_nnz + off) * d * d;
-  int rc = launch_source(h->field[field], d * d, h->md.gw, cnt, h->src_nodes + off, vals, coef, ss.ctr ? 1.0 : source_scale(h), ss,
+  const double* vals = h->src.values.get() + ((size_t)((source_one_slice(h) || ss.ctr) ? 0 : h->src_step) * h->src.nnz + off) * d * d;
+  int rc = launch_source(h->field[field].get(), d * d, h->md.gw, cnt, h->src.nodes.get() + off, vals, coef, ss.ctr ? 1.0 : source_scale(h), ss,
                          h->f32, h->stream);
   if (rc != 0) return fail(h, SG_ERR_DEVICE, "source kernel launch failed");
   return SG_OK;
@@ -244,7 +242,7 @@ static int run_stage_impl(sg_handle* h, int stage, int region) {
     case SG_STAGE_U1:
       // explicit mode keeps only rhs(form_u1): u1 = rho*u0 + dt*uh1 + dt^3/24*uh2 (elastic.py:341-345, :354-356);
       // sg_set_density(physical = 1): u1 = u0 + (dt*uh1 + dt^3/24*uh2)/rho; per-cell density: factors in rho2
-      if (h->rho2_d) return run_op(h, 0, SG_FIELD_SH, SG_FIELD_U, SG_FIELD_UH, 1, 1.0, dt, c3, region, SG_FIELD_U, false, true);
+      if (h->rho2_d.get()) return run_op(h, 0, SG_FIELD_SH, SG_FIELD_U, SG_FIELD_UH, 1, 1.0, dt, c3, region, SG_FIELD_U, false, true);
       if (h->rho_physical) return run_op(h, 0, SG_FIELD_SH, SG_FIELD_U, SG_FIELD_UH, 1, 1.0, dt / h->rho, c3 / h->rho, region);
       return run_op(h, 0, SG_FIELD_SH, SG_FIELD_U, SG_FIELD_UH, 1, h->rho, dt, c3, region);
     case SG_STAGE_SH1:
@@ -368,7 +366,7 @@ static int enqueue_step(sg_handle* h) {
     if (rc != SG_OK) return rc;
   }
   // the next step's slice (tile path: stage UH1 bumps the counter itself, run_op)
-  if (h->capture_src && !h->src_fused && launch_step_counter(h->src_ctr_d, 1, 1, h->stream) != 0)
+  if (h->capture_src && !h->src.fused && launch_step_counter(h->src_ctr_d.get(), 1, 1, h->stream) != 0)
     return fail(h, SG_ERR_DEVICE, "step counter launch failed");
   return SG_OK;
 }
@@ -388,9 +386,9 @@ static hipGraphExec_t capture_steps(sg_handle* h, int steps, bool with_src) {
   if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return nullptr;
   int rc = SG_OK;
   h->capture_src = with_src;
-  h->sponge_pre_ver = ~0ull;      // a replay starts from whatever the buffer holds: the captured step computes its own
+  h->sponge.pre_ver = ~0ull;      // a replay starts from whatever the buffer holds: the captured step computes its own
   for (int k = 0; k < steps && rc == SG_OK; ++k) rc = enqueue_step(h);
-  h->sponge_pre_ver = ~0ull;      // nothing was launched: the buffer holds what it held
+  h->sponge.pre_ver = ~0ull;      // nothing was launched: the buffer holds what it held
   h->capture_src = false;
   hipError_t e = hipStreamEndCapture(h->stream, &g);
   if (rc == SG_OK && e == hipSuccess && g) {
@@ -416,7 +414,7 @@ int sg_step(sg_handle* h, int64_t nsteps) {
   // graphs: its launches take this step's slice and weight from a device-side step counter (kernels.hpp SrcStep),
   // set here to the step the replay starts from; one that has run out (or none) gives graphs without source launches.
   const bool graphs = h->graph_ok && !h->timing && nsteps >= 2;
-  const bool with_src = source_active(h) && h->src_ctr_d != nullptr;
+  const bool with_src = source_active(h) && h->src_ctr_d.get() != nullptr;
   if (graphs && source_active(h) && !with_src) return fail(h, SG_ERR_STATE, "source without a device-side step counter");
   if (graphs && (h->graph_epoch != h->epoch || h->graph_src != with_src)) {
     if (h->graph1) (void)hipGraphExecDestroy(h->graph1);
@@ -430,7 +428,7 @@ int sg_step(sg_handle* h, int64_t nsteps) {
   HIPCHECK(h, hipEventRecord(h->ev0, h->stream));
   if (graphs && h->graph_ok) {
     // (tile path: the counter is bumped by the launch that OPENS a step, so it starts one short)
-    if (with_src && launch_step_counter(h->src_ctr_d, h->src_step - (h->src_fused ? 1 : 0), 0, h->stream) != 0)
+    if (with_src && launch_step_counter(h->src_ctr_d.get(), h->src_step - (h->src.fused ? 1 : 0), 0, h->stream) != 0)
       return fail(h, SG_ERR_DEVICE, "step counter launch failed");
     for (; k + 8 <= nsteps; k += 8) HIPCHECK(h, hipGraphLaunch(h->graph8, h->stream));
     for (; k < nsteps; ++k) HIPCHECK(h, hipGraphLaunch(h->graph1, h->stream));
@@ -438,8 +436,8 @@ int sg_step(sg_handle* h, int64_t nsteps) {
     h->counters.steps += nsteps;
     h->src_step += nsteps;
     if (nsteps > 0) {
-      for (int f = 0; f < 4; ++f) h->fver[f] += 1;
-      h->sponge_pre_ver = ~0ull;
+      for (int f = 0; f < 4; ++f) mark_field_written(h, f);
+      h->sponge.pre_ver = ~0ull;
     }
   }
   for (; k < nsteps; ++k) {
@@ -542,7 +540,7 @@ int sg_halo_pack(sg_handle* h, int field, int side, void* dev_out) {
   size_t k = 0, nb = 0;
   int rc = pack_begin(h, k);
   if (rc != SG_OK) return rc;
-  rc = launch_pack(h->md_dev, h->md, h->field[field], comps, 1, &side, &out,
+  rc = launch_pack(h->md_dev.get(), h->md, h->field[field].get(), comps, 1, &side, &out,
                    (h->sym && field_is_stress(field)) ? 1 : 0, h->f32, h->stream);
   if (rc != 0) return fail(h, SG_ERR_DEVICE, "pack kernel launch failed");
   (void)sg_halo_bytes(h, field, side, &nb);
@@ -565,7 +563,7 @@ int sg_halo_pack_sides(sg_handle* h, int field, void* const* dev_out) {
   size_t k = 0, total = 0;
   int rc = pack_begin(h, k);
   if (rc != SG_OK) return rc;
-  rc = launch_pack(h->md_dev, h->md, h->field[field], comps, n, sides, outs,
+  rc = launch_pack(h->md_dev.get(), h->md, h->field[field].get(), comps, n, sides, outs,
                    (h->sym && field_is_stress(field)) ? 1 : 0, h->f32, h->stream);
   if (rc != 0) return fail(h, SG_ERR_DEVICE, "pack kernel launch failed");
   for (int i = 0; i < n; ++i) {

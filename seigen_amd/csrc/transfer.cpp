@@ -7,8 +7,10 @@
 int leave_sym_mode(sg_handle* h) {
   h->epoch += 1;
   if (!h->sym) return SG_OK;
-  for (int f : {SG_FIELD_S, SG_FIELD_SH})
-    if (launch_mirror(h->md, h->field[f], h->f32, h->stream) != 0) return fail(h, SG_ERR_DEVICE, "mirror kernel launch failed");
+  for (int f : {SG_FIELD_S, SG_FIELD_SH}) {
+    mark_field_written(h, f);
+    if (launch_mirror(h->md, h->field[f].get(), h->f32, h->stream) != 0) return fail(h, SG_ERR_DEVICE, "mirror kernel launch failed");
+  }
   HIPCHECK(h, sync_all(h));
   h->sym = false;
   return SG_OK;
@@ -47,7 +49,7 @@ static int download_pipelined(sg_handle* h, int field, int64_t cell0, int64_t nc
   const size_t slot_len = chunk_cells * per_cell;
   for (int i = 0; i < 2; ++i) {
     if (!h->pin[i]) HIPCHECK(h, hipHostMalloc((void**)&h->pin[i], slot_len * sizeof(double), hipHostMallocDefault));
-    if (!h->dstage[i] && h->md.gw != 1) HIPCHECK(h, hipMalloc((void**)&h->dstage[i], slot_len * sizeof(double)));
+    if (!h->dstage[i].get() && h->md.gw != 1) HIPCHECK(h, h->dstage[i].alloc(slot_len));
     if (!h->xfer_ev[i]) HIPCHECK(h, hipEventCreateWithFlags(&h->xfer_ev[i], hipEventDisableTiming));
   }
   const int64_t nchunks = (ncells + (int64_t)chunk_cells - 1) / (int64_t)chunk_cells;
@@ -63,11 +65,11 @@ static int download_pipelined(sg_handle* h, int field, int64_t cell0, int64_t nc
       range(c, c0, n);
       const size_t nb = (size_t)n * per_cell * sizeof(double);
       if (h->md.gw == 1) {
-        HIPCHECK(h, hipMemcpyAsync(h->pin[sl], h->field[field] + (size_t)(cell0 + c0) * per_cell, nb, hipMemcpyDeviceToHost, h->stream));
+        HIPCHECK(h, hipMemcpyAsync(h->pin[sl], h->field[field].get() + (size_t)(cell0 + c0) * per_cell, nb, hipMemcpyDeviceToHost, h->stream));
       } else {
-        if (launch_layout(h->md, comps, 1, h->field[field], h->dstage[sl], cell0 + c0, n, symdl, nullptr, h->f32, h->stream) != 0)
+        if (launch_layout(h->md, comps, 1, h->field[field].get(), h->dstage[sl].get(), cell0 + c0, n, symdl, nullptr, h->f32, h->stream) != 0)
           return fail(h, SG_ERR_DEVICE, "layout kernel launch failed");
-        HIPCHECK(h, hipMemcpyAsync(h->pin[sl], h->dstage[sl], nb, hipMemcpyDeviceToHost, h->stream));
+        HIPCHECK(h, hipMemcpyAsync(h->pin[sl], h->dstage[sl].get(), nb, hipMemcpyDeviceToHost, h->stream));
       }
       HIPCHECK(h, hipEventRecord(h->xfer_ev[sl], h->stream));
     }
@@ -87,7 +89,7 @@ static int transfer(sg_handle* h, int field, int64_t cell0, int64_t ncells, doub
   HIPCHECK(h, hipSetDevice(h->cfg.device));
   if (int rc = join_second(h)) return rc;
   HIPCHECK(h, sync_all(h));
-  if (to_device) h->fver[field] += 1;      // what was derived from the field's old state (the sponge pre-pass) is stale
+  if (to_device) mark_field_written(h, field);
   const size_t per_cell = h->field_len[field] / (size_t)h->ncells;
   // downloads only: uploads from pageable memory already run at 47 GB/s inside the runtime (measured,
   // tools/transfer_rate.py: 35 GB/s through this pipeline)
@@ -95,7 +97,7 @@ static int transfer(sg_handle* h, int field, int64_t cell0, int64_t ncells, doub
     return download_pipelined(h, field, cell0, ncells, host);
   }
   if (h->md.gw == 1) {
-    double* dev = h->field[field] + (size_t)cell0 * per_cell;
+    double* dev = h->field[field].get() + (size_t)cell0 * per_cell;
     size_t nb = (size_t)ncells * per_cell * sizeof(double);
     if (to_device)
       HIPCHECK(h, hipMemcpy(dev, host, nb, hipMemcpyHostToDevice));
@@ -107,9 +109,10 @@ static int transfer(sg_handle* h, int field, int64_t cell0, int64_t ncells, doub
   // or a velocity-sized buffer of a one-cell block holds no whole cell of a stress field (chunk = 0: no progress).
   const size_t per_cell_max = (size_t)h->re.nd * h->cfg.dim * h->cfg.dim;
   const size_t cap_cells = std::max<size_t>(1, ((size_t)32 << 20) / per_cell_max);  // 256 MB staging
-  if (!h->staging) {
-    h->staging_len = std::min(cap_cells, (size_t)h->ncells) * per_cell_max;
-    HIPCHECK(h, hipMalloc((void**)&h->staging, h->staging_len * sizeof(double)));
+  if (!h->staging.get()) {
+    const size_t len = std::min(cap_cells, (size_t)h->ncells) * per_cell_max;
+    HIPCHECK(h, h->staging.alloc(len));
+    h->staging_len = len;
   }
   const size_t chunk = h->staging_len / per_cell;
   if (chunk == 0) return fail(h, SG_ERR_STATE, "staging buffer smaller than one cell");
@@ -118,22 +121,22 @@ static int transfer(sg_handle* h, int field, int64_t cell0, int64_t ncells, doub
     int64_t n = std::min<int64_t>((int64_t)chunk, ncells - done);
     size_t nb = (size_t)n * per_cell * sizeof(double);
     if (to_device) {
-      HIPCHECK(h, hipMemcpy(h->staging, host + (size_t)done * per_cell, nb, hipMemcpyHostToDevice));
-      int* flag = (h->sym && field_is_stress(field)) ? h->sym_flag : nullptr;
-      if (launch_layout(h->md, comps, 0, h->field[field], h->staging, cell0 + done, n, 0, flag, h->f32, h->stream) != 0)
+      HIPCHECK(h, hipMemcpy(h->staging.get(), host + (size_t)done * per_cell, nb, hipMemcpyHostToDevice));
+      int* flag = (h->sym && field_is_stress(field)) ? h->sym_flag.get() : nullptr;
+      if (launch_layout(h->md, comps, 0, h->field[field].get(), h->staging.get(), cell0 + done, n, 0, flag, h->f32, h->stream) != 0)
         return fail(h, SG_ERR_DEVICE, "layout kernel launch failed");
       HIPCHECK(h, sync_all(h));
     } else {
       const int symdl = (h->sym && field_is_stress(field)) ? 1 : 0;
-      if (launch_layout(h->md, comps, 1, h->field[field], h->staging, cell0 + done, n, symdl, nullptr, h->f32, h->stream) != 0)
+      if (launch_layout(h->md, comps, 1, h->field[field].get(), h->staging.get(), cell0 + done, n, symdl, nullptr, h->f32, h->stream) != 0)
         return fail(h, SG_ERR_DEVICE, "layout kernel launch failed");
       HIPCHECK(h, sync_all(h));
-      HIPCHECK(h, hipMemcpy(host + (size_t)done * per_cell, h->staging, nb, hipMemcpyDeviceToHost));
+      HIPCHECK(h, hipMemcpy(host + (size_t)done * per_cell, h->staging.get(), nb, hipMemcpyDeviceToHost));
     }
   }
   if (to_device && h->sym && field_is_stress(field)) {
     int flag = 0;
-    HIPCHECK(h, hipMemcpy(&flag, h->sym_flag, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHECK(h, hipMemcpy(&flag, h->sym_flag.get(), sizeof(int), hipMemcpyDeviceToHost));
     if (flag) {
       // a non-symmetric stress arrived: make every (i > j) line of both stress buffers valid (they
       // are stale wherever kernels ran in symmetric mode), then repeat this upload in full mode

@@ -80,7 +80,7 @@ def test_graph_replay_with_a_source_is_not_slower(gpu, monkeypatch):
 @pytest.mark.parametrize("calls", [(19,), (9, 1, 12), (1, 1, 8, 3)])
 def test_graph_replay_with_a_sponge_pre_pass_is_bitwise_the_plain_run(gpu, monkeypatch, dim, degree, n, diagonal, calls):
     """Round 6: the sponge pre-pass of the 3-D families belongs to a STATE of the velocity field and is launched only when
-    the buffer is stale (once per step, in stage UTEMP; stages.cpp fver / sponge_pre_ver).  That decision is made on the host
+    the buffer is stale (once per step, in stage UTEMP; handle.hpp SpongeTables::pre_ver).  That decision is made on the host
     while a graph is captured and replayed on the device: replayed runs (graphs of eight steps and of one, runs continued by
     further sg_step calls, an upload of the velocity in between) must equal the launch-by-launch runs bit for bit - with cells
     of every kind: no sponge, constant, affine, general."""

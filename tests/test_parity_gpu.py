@@ -319,7 +319,7 @@ def test_3d_sponge_constant_and_matrix_cells(gpu, monkeypatch, degree, n, diagon
     (launch_sponge_pre) - cells of all three kinds (none, constant, varying) side by side inside one 16-cell item, three
     whole steps (the in-place stage U1 reads u_abs = its own output buffer) against the generic kernels (every sponge cell
     through its matrix, in the kernel) and against the oracle.  (The same mix of cells on SPLIT stages - the SECOND region
-    reads the pre-pass the FIRST region launched, stages.cpp sponge_pre_key / sponge_pre_regions - is checked bitwise
+    reads the pre-pass the FIRST region launched, handle.hpp SpongeTables::pre_key / pre_regions - is checked bitwise
     against the single block by test_harness_gpu.py::_multiblock_case(extras=True) for every family, tetrahedra and
     hexahedra, and over the native exchange by test_native_exchange_gpu.py's "source" cases.)"""
     from seigen_amd import _lib
@@ -458,6 +458,63 @@ def test_error_behaviour(gpu):
         nb.run_stage(0, _lib.REGION_FIRST)
     with pytest.raises(_lib.SeigenHipError):
         HipBlock(3, 7, (2, 2, 2), (0.5, 0.5, 0.5), (0.0, 0.0, 0.0))   # unsupported degree
+
+
+@pytest.mark.parametrize("degree,n,diagonal,path", [
+    (4, (17, 3, 2), "left", ""), (4, (3, 2, 2), "quadrilateral", ""), (2, (5, 3, 2), "quadrilateral", "lane"),
+])
+def test_failed_setters_leave_the_handle_as_it_was(gpu, monkeypatch, degree, n, diagonal, path):
+    """A setter that fails leaves the handle as it was (include/seigen_hip.h): twin blocks with the same per-cell physical
+    density, affine ramp sponge (the pre-pass families: MFMA tetrahedra, hexahedra DQ_4, the lane kernels' DQ_2), multi-step
+    source and fields; one of them also sees three calls that are refused.  One step launch by launch and eight through
+    graph replay give bitwise the same fields on both."""
+    from seigen_amd import _lib
+    from seigen_amd.backend import HipBlock
+    L = tuple(0.4 * k for k in n)
+    h = [L[a] / n[a] for a in range(3)]
+    m = oracle_mesh(3, n, L, diagonal)
+    Xq = m.node_coords(4)
+    sigma = 4.0 + 11.0 * Xq[..., 0] + 7.0 * Xq[..., 1] + 23.0 * Xq[..., 2]
+    dt = 0.04 * min(h) / degree ** 2
+    r = np.random.default_rng(81)
+    rho = r.uniform(1.0, 2.0, size=m.ncells)
+    nodes = r.choice(m.ncells * 8, size=12, replace=False)
+    vals = r.standard_normal((20, nodes.size, 3, 3))
+    vals = 0.5 * (vals + np.swapaxes(vals, -1, -2))
+    if path:
+        monkeypatch.setenv("SEIGEN_HIP_PATH", path)
+    monkeypatch.setenv("SEIGEN_HIP_SPONGE_AFFINE", "1")
+    twins = []
+    for _ in range(2):
+        blk = HipBlock(3, degree, n, h, [0.0] * 3, diagonal)
+        blk.set_params(1.0, dt, 0.6, 0.3)
+        blk.set_density(rho, physical=True)
+        blk.set_absorption(sigma, 4)
+        blk.set_source(nodes, vals)
+        u0 = seeded(blk.field_shape(_lib.FIELD_U), 91)
+        s0 = seeded(blk.field_shape(_lib.FIELD_S), 92)
+        blk.set_field(_lib.FIELD_U, u0)
+        blk.set_field(_lib.FIELD_S, 0.5 * (s0 + np.swapaxes(s0, -1, -2)))
+        twins.append(blk)
+    blk = twins[1]
+    with pytest.raises(_lib.SeigenHipError, match="sigma_degree"):
+        blk.set_absorption(sigma, 7)
+    bad_rho = rho.copy()
+    bad_rho[m.ncells // 2] = 0.0
+    with pytest.raises(_lib.SeigenHipError, match="zero density"):
+        blk.set_density(bad_rho, physical=True)
+    with pytest.raises(_lib.SeigenHipError, match="out of range"):
+        blk.set_source(np.append(nodes, m.ncells * 10 ** 4), np.zeros((3, nodes.size + 1, 3, 3)))
+    for k in (1, 8):
+        for t in twins:
+            t.step(k)
+        for f in (_lib.FIELD_U, _lib.FIELD_UH, _lib.FIELD_S, _lib.FIELD_SH):
+            a, b = (t.get_field(f) for t in twins)
+            assert np.isfinite(a).all()
+            assert np.array_equal(a, b), (k, f)
+    assert rel_err(twins[0].get_field(_lib.FIELD_U), u0) > 1e-4
+    for t in twins:
+        t.close()
 
 
 @pytest.mark.parametrize("seed", range(int(os.environ.get("SEIGEN_TEST_RANDOM_CASES", "10"))))
