@@ -8,6 +8,291 @@
 #include "handle.hpp"
 #include "sponge_tables.hpp"
 
+// the configuration, the reference element and the mesh tables
+static int init_element(const sg_config* cfg, sg_handle* h) {
+  if (cfg->dim < 1 || cfg->dim > 3) return fail(h, SG_ERR_ARG, "dim must be 1, 2 or 3");
+  if (cfg->degree < 1 || cfg->degree > 4) return fail(h, SG_ERR_ARG, "degree must be 1..4");
+  for (int a = 0; a < cfg->dim; ++a) {
+    if (cfg->n[a] < 1) return fail(h, SG_ERR_ARG, "n[axis] must be >= 1");
+    if (!(cfg->h[a] > 0.0)) return fail(h, SG_ERR_ARG, "h[axis] must be > 0");
+  }
+  h->cfg = *cfg;
+  for (int a = cfg->dim; a < 3; ++a) {
+    h->cfg.n[a] = 1;
+    h->cfg.h[a] = 1.0;
+    h->cfg.origin[a] = 0.0;
+    h->cfg.cube0[a] = 0;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+    return fail(h, SG_ERR_DEVICE, "no HIP device available (libseigen_hip has no CPU fallback)");
+  if (cfg->device < 0 || cfg->device >= ndev) return fail(h, SG_ERR_ARG, "device ordinal out of range");
+  HIPCHECK(h, hipSetDevice(cfg->device));
+
+  if (cfg->diagonal == SG_DIAGONAL_QUAD && cfg->dim == 1) return fail(h, SG_ERR_ARG, "tensor-product cells need dim 2 or 3");
+  try {
+    h->re = make_refelem(cfg->dim, cfg->degree, cfg->diagonal == SG_DIAGONAL_QUAD ? KIND_TENSOR : KIND_SIMPLEX);
+    std::memset(&h->md, 0, sizeof(MeshDev));
+    h->md.nd = h->re.nd;
+    h->md.nf = h->re.nf;
+    build_mesh_tables(cfg->dim, cfg->degree, cfg->diagonal, h->cfg.h, h->re.fnode.data(), h->re.lattice.data(), h->md);
+  } catch (const std::exception& e) {
+    return fail(h, SG_ERR_ARG, e.what());
+  }
+  for (int a = 0; a < 3; ++a) h->md.n[a] = h->cfg.n[a];
+  for (int s = 0; s < 6; ++s) h->md.has_nbr[s] = (s < 2 * cfg->dim) ? ((cfg->nbr_mask >> s) & 1) : 0;
+  h->ncls = h->md.ncls;
+  h->ncells = (int64_t)h->cfg.n[0] * h->cfg.n[1] * h->cfg.n[2] * h->ncls;
+  return SG_OK;
+}
+
+// the kernel family, and with it the precision and the layout
+static int init_family(sg_handle* h) {
+  h->family = choose_kernel_path(h->cfg);
+  if (h->cfg.dtype != 0 && h->cfg.dtype != 1) return fail(h, SG_ERR_ARG, "dtype must be 0 (f64) or 1 (f32)");
+  h->f32 = h->cfg.dtype;
+  if (h->f32 && !family_f32(h->family))
+    return fail(h, SG_ERR_ARG, "dtype f32 is implemented on the MFMA paths (3-D blocks: degree 1 from 65536 cells; 2-D "
+                               "blocks on the tile kernels)");
+  h->md.gw = family_gw(h->family);
+  h->md.ncube = (int64_t)h->cfg.n[0] * h->cfg.n[1] * h->cfg.n[2];
+  h->md.ncube_pad = (h->md.ncube + h->md.gw - 1) / h->md.gw * h->md.gw;
+  return SG_OK;
+}
+
+// hexahedra, every family (kernels_lane.hip hex_stage, kernels_hexm.hip, kernels.hip stage_kernel TP = 2): the 1-D
+// factors D1 [n1][n1] and lift1 [2][n1], read off the full tables along the first axis and checked against ALL of D_r, L_f
+static int hex_factors(sg_handle* h, std::vector<double>& Dt) {
+  const RefElem& re = h->re;
+  const int nd = re.nd, nf = re.nf, n1 = h->cfg.degree + 1;
+  auto node = [&](int a0, int a1, int a2) { return a0 + n1 * (a1 + n1 * a2); };
+  Dt.assign((size_t)n1 * n1 + 2 * n1, 0.0);
+  for (int m = 0; m < n1; ++m) {
+    for (int n = 0; n < n1; ++n) Dt[(size_t)m * n1 + n] = re.D[((size_t)0 * nd + node(m, 0, 0)) * nd + node(n, 0, 0)];
+    for (int s = 0; s < 2; ++s) Dt[(size_t)n1 * n1 + s * n1 + m] = re.L[((size_t)s * nd + node(m, 0, 0)) * nf + 0];
+  }
+  double worst = 0.0;
+  for (int a = 0; a < nd; ++a) {
+    const int ai[3] = {a % n1, (a / n1) % n1, a / (n1 * n1)};
+    for (int r = 0; r < 3; ++r) {
+      for (int b = 0; b < nd; ++b) {
+        const int bi[3] = {b % n1, (b / n1) % n1, b / (n1 * n1)};
+        const bool line = ai[(r + 1) % 3] == bi[(r + 1) % 3] && ai[(r + 2) % 3] == bi[(r + 2) % 3];
+        const double want = line ? Dt[(size_t)ai[r] * n1 + bi[r]] : 0.0;
+        worst = std::max(worst, std::fabs(re.D[((size_t)r * nd + a) * nd + b] - want));
+      }
+      for (int s = 0; s < 2; ++s)
+        for (int bp = 0; bp < nf; ++bp) {
+          const int b = re.fnode[(size_t)(2 * r + s) * nf + bp];
+          const int bi[3] = {b % n1, (b / n1) % n1, b / (n1 * n1)};
+          // facet nodes in ascending order: bp = lower transverse index + n1 * the upper one
+          const int lo = r == 0 ? 1 : 0, hi = r == 2 ? 1 : 2;
+          // ... and the neighbour's matching node is the one across the cube, at the same place of its facet list
+          int ni[3] = {bi[0], bi[1], bi[2]};
+          ni[r] = s ? 0 : n1 - 1;
+          if (bp != bi[lo] + n1 * bi[hi] || bi[r] != (s ? n1 - 1 : 0) || h->md.fnode[2 * r + s][bp] != b ||
+              h->md.nb_node[0][2 * r + s][bp] != node(ni[0], ni[1], ni[2]) || h->md.nb_fnode[0][2 * r + s][bp] != bp ||
+              h->md.nb_face[0][2 * r + s] != 2 * r + (1 - s) || h->md.nb_axis[0][2 * r + s] != r)
+            return fail(h, SG_ERR_ARG, "hexahedral element: unexpected facet node order");
+          const bool same = ai[lo] == bi[lo] && ai[hi] == bi[hi];
+          const double want = same ? Dt[(size_t)n1 * n1 + s * n1 + ai[r]] : 0.0;
+          worst = std::max(worst, std::fabs(re.L[((size_t)(2 * r + s) * nd + a) * nf + bp] - want));
+        }
+    }
+  }
+  if (worst > 1e-11) return fail(h, SG_ERR_ARG, "hexahedral element: the operator tables do not factorise");
+  return SG_OK;
+}
+
+// The operator fragments of the matrix-pipe families, F, G, L (and Q, P: the factorised G volume), as the device holds
+// them: float tables two values to a double where f32 (StageArgs::fragV / fragL are double pointers, as the fields are)
+using Frags = std::vector<double>[5];
+template <typename T>
+static void set_frags(Frags& fr, const std::vector<T>& fF, const std::vector<T>& fG, const std::vector<T>& fL) {
+  for (auto [i, v] : {std::make_pair(0, &fF), std::make_pair(1, &fG), std::make_pair(2, &fL)}) {
+    fr[i].assign((v->size() * sizeof(T) + sizeof(double) - 1) / sizeof(double), 0.0);
+    std::memcpy(fr[i].data(), v->data(), v->size() * sizeof(T));
+  }
+}
+
+// The tables of the family: StageArgs::Dt / Lt and the mesh tables on the device, the MFMA constants on the device, the
+// fragments in `fr` (uploaded after the fields, init_fields: the device allocations keep their order)
+static int family_tables(sg_handle* h, Frags& fr) {
+  const sg_config* cfg = &h->cfg;
+  const RefElem& re = h->re;
+  const int d = cfg->dim, nd = re.nd, nf = re.nf, nfaces = re.nfaces;
+  // transposed operators: Dt[r][b][a], Lt[f][b'][a]
+  std::vector<double> Dt((size_t)d * nd * nd), Lt((size_t)nfaces * nf * nd);
+  for (int r = 0; r < d; ++r)
+    for (int a = 0; a < nd; ++a)
+      for (int b = 0; b < nd; ++b) Dt[((size_t)r * nd + b) * nd + a] = re.D[((size_t)r * nd + a) * nd + b];
+  for (int f = 0; f < nfaces; ++f)
+    for (int a = 0; a < nd; ++a)
+      for (int b = 0; b < nf; ++b) Lt[((size_t)f * nf + b) * nd + a] = re.L[((size_t)f * nd + a) * nf + b];
+  const bool hex = re.kind == KIND_TENSOR && d == 3;
+  if (int rc = hex ? hex_factors(h, Dt) : SG_OK) return rc;
+  switch (h->family) {
+    case Family::Generic: break;
+    case Family::Hexm: {   // kernels_hexm.hip: line operators with the own-trace half folded in, x-pass A operands
+      Dt = hexm_table(cfg->degree, Dt.data(), Dt.data() + (size_t)(cfg->degree + 1) * (cfg->degree + 1), h->md);
+      break;
+    }
+    case Family::Lane: {
+      if (hex) break;
+      // E_r = D_r - (L_0 R_0 - L_{r+1} R_{r+1}) / (2 (d-1)!) row-major (own-trace half of the central flux folded into the
+      // volume operator, see mfma_tables.cpp), and L_f row-major
+      double fact = 1.0;
+      for (int i = 2; i <= d - 1; ++i) fact *= i;
+      const double cfold = 1.0 / (2.0 * fact);
+      for (int r = 0; r < d; ++r)
+        for (int a = 0; a < nd; ++a)
+          for (int b = 0; b < nd; ++b) {
+            double v = re.D[((size_t)r * nd + a) * nd + b];
+            for (int bf = 0; bf < nf; ++bf) {
+              if (re.fnode[(size_t)0 * nf + bf] == b) v -= cfold * re.L[((size_t)0 * nd + a) * nf + bf];
+              if (re.fnode[(size_t)(r + 1) * nf + bf] == b) v += cfold * re.L[((size_t)(r + 1) * nd + a) * nf + bf];
+            }
+            Dt[((size_t)r * nd + a) * nd + b] = v;
+          }
+      Lt = re.L;
+      break;
+    }
+    case Family::Mfma: {
+      if (h->f32) set_frags(fr, mfma32_frags_F(re), mfma32_frags_G(re), mfma32_frags_L(re));
+      else set_frags(fr, mfma_frags_F(re), mfma_frags_G(re), mfma_frags_L(re));
+      // factorised G volume (mfma_tables.hpp): D_r = P_r Q
+      const char* gq = std::getenv("SEIGEN_HIP_GQ");
+      // default: degree 4 only (G<4,0> -2 %, step -0.7 .. -1 %; at degree 3, rank 10 of 20 on 4-row tiles, it is 12 % slower:
+      // profiles/r04/kernel_experiments.txt); SEIGEN_HIP_GQ=0 / 1 forces it off / on for degrees 3 and 4
+      if (!h->f32 && cfg->degree >= 3 && (gq ? std::atoi(gq) != 0 : cfg->degree >= SG_GQ_FROM_DEGREE)) {
+        try {
+          fr[3] = mfma_frags_Q(re);
+          fr[4] = mfma_frags_P(re);
+        } catch (const std::exception& e) {
+          return fail(h, SG_ERR_ARG, e.what());
+        }
+      }
+      break;
+    }
+    case Family::Tile2d: {
+      h->t2c = tile2d_const(h->md);
+      if (h->f32) set_frags(fr, tile2d_frags32_V(re, -1.0), tile2d_frags32_V(re, 1.0), tile2d_frags32_L(re));
+      else set_frags(fr, tile2d_frags_V(re, -1.0), tile2d_frags_V(re, 1.0), tile2d_frags_L(re));
+      break;
+    }
+  }
+  HIPCHECK(h, h->Dt.upload(Dt.data(), Dt.size()));
+  HIPCHECK(h, h->Lt.upload(Lt.data(), Lt.size()));
+  HIPCHECK(h, h->md_dev.upload(&h->md, 1));
+  if (h->family == Family::Mfma) {
+    const MfmaConst mk = mfma_const(h->md);
+    HIPCHECK(h, h->mk_dev.upload(&mk, 1));
+    std::vector<int32_t> ft, tab;
+    mfma_trace_offsets(h->md, 9, ft);
+    HIPCHECK(h, h->ftab_dev.upload(ft.data(), ft.size()));
+    if ((h->md.ncube_pad / 16) * 6 * 16 >= ((int64_t)1 << 31))     // cell slots are int32 (288 GB hold far fewer cells)
+      return fail(h, SG_ERR_ARG, "block too large for the MFMA path's neighbour table");
+    build_nbr_table(h->md, tab);
+    HIPCHECK(h, h->nbr_tab.upload(tab.data(), tab.size()));
+  }
+  return SG_OK;
+}
+
+// the four fields (zero), the operator fragments, the symmetric-stress flag, the diagnostic stamps
+static int init_fields(sg_handle* h, const Frags& fr) {
+  const int d = h->cfg.dim, nd = h->re.nd;
+  for (int f = 0; f < 4; ++f) {
+    size_t comps = field_is_stress(f) ? (size_t)d * d : (size_t)d;
+    h->field_len[f] = (size_t)h->ncells * nd * comps;
+    h->field_alloc[f] = (size_t)h->md.ncube_pad * h->ncls * nd * comps;
+    const size_t n = h->f32 ? (h->field_alloc[f] + 1) / 2 : h->field_alloc[f];   // in doubles
+    if (h->field[f].alloc(n) != hipSuccess) return fail(h, SG_ERR_NOMEM, "hipMalloc of a field buffer failed");
+    HIPCHECK(h, hipMemset(h->field[f].get(), 0, n * sizeof(double)));
+  }
+  DevBuf<double>* frag[5] = {&h->fragF, &h->fragG, &h->fragL, &h->fragQ, &h->fragP};
+  for (int i = 0; i < 5; ++i)
+    if (!fr[i].empty()) HIPCHECK(h, frag[i]->upload(fr[i].data(), fr[i].size()));
+  if (family_interleaved(h->family)) {
+    // symmetric-stress mode (DESIGN.md): fields start at zero, g only produces symmetric tensors;
+    // left for good as soon as the user uploads a non-symmetric stress or source (SEIGEN_HIP_SYM=0: never entered)
+    const char* sym_env = std::getenv("SEIGEN_HIP_SYM");
+    h->sym = !(sym_env && std::strcmp(sym_env, "0") == 0);
+    const int zero = 0;
+    HIPCHECK(h, h->sym_flag.upload(&zero, 1));
+  }
+  if (std::getenv("SEIGEN_HIP_STAMPS")) {
+    const std::vector<unsigned long long> zeros(32, 0);
+    HIPCHECK(h, h->dbg.upload(zeros.data(), zeros.size()));
+  }
+  return SG_OK;
+}
+
+// block slots per CU of the family's stage kernels (registers and LDS)
+static int blocks_per_cu(const sg_handle* h) {
+  const int P = h->cfg.degree;
+  return h->family == Family::Mfma ? mfma_blocks_per_cu(P, h->f32) : (h->family == Family::Hexm ? hexm_blocks_per_cu(P) : 2);
+}
+
+// persistent grids, graph replay, the streams and events
+static int init_launch(sg_handle* h) {
+  const sg_config* cfg = &h->cfg;
+  // Persistent grid of the MFMA stage kernels: two blocks per CU fill every CU (registers and
+  // LDS allow exactly two).  A block with halo neighbours leaves 1/16 of those slots empty, so
+  // that RCCL's send/receive kernels can start WHILE an interior launch runs: behind a full
+  // grid they only start when it drains (tools/overlap_probe.py), and a stage kernel that found
+  // some of its own slots taken would run the late blocks' static shares one after the other.
+  hipDeviceProp_t prop;
+  HIPCHECK(h, hipGetDeviceProperties(&prop, cfg->device));
+  const int slots = blocks_per_cu(h) * prop.multiProcessorCount;
+  h->grid_full = slots / 8 * 8;
+  h->grid_blocks = (cfg->nbr_mask != 0 ? slots - slots / 16 : slots) / 8 * 8;
+  if (const char* gb = std::getenv("SEIGEN_HIP_GRID_BLOCKS")) h->grid_blocks = std::max(8, std::atoi(gb) / 8 * 8);
+  if (cfg->nbr_mask == 0) h->grid_full = h->grid_blocks;
+  // F stages of a whole 3-D block: items dealt to the XCDs in chunks of 1/8 of a z-layer of cubes, so that all XCDs
+  // sweep the block layer by layer together (the z-neighbour traces then meet the own rows of the next layer in the
+  // Infinity Cache: F stages -3 %, profiles/r03/order_chunk_sweep.txt; the G stages do not gain and keep one
+  // contiguous range per XCD).  SEIGEN_HIP_ORDER_CHUNK overrides (0 = off).
+  h->order_chunk = 0;
+  if (h->family == Family::Mfma) {
+    const int64_t per_layer = ((int64_t)cfg->n[0] * cfg->n[1] + 15) / 16 * 6;
+    if (cfg->n[2] >= 16) h->order_chunk = (int)std::max<int64_t>(6, (per_layer + 7) / 8);
+  }
+  if (const char* oc = std::getenv("SEIGEN_HIP_ORDER_CHUNK")) h->order_chunk = std::max(0, std::atoi(oc));
+  h->no_whole = std::getenv("SEIGEN_HIP_NO_WHOLE") != nullptr;
+  // 2-D tile kernels: a persistent grid of exactly the blocks the device holds of the stage's kernel (0 = the launcher
+  // asks the runtime per instantiation, kernels_tile2d.hip) - a wave sets up once and works through its share of the
+  // items: 2-D P4 at N = 256 (the reference's benchmark protocol) 84.5 -> 93.4 G DoF-updates/s against one item per
+  // wave, P3 +8 %, level elsewhere (profiles/r05/tile_grid_sweep.txt).  With a sponge the items differ in cost and a
+  // static share can collect the expensive ones: then 251 blocks per XCD label - with an odd (prime) stride of 4 * 251
+  // items a wave's items do not keep falling on the same column of the mesh, i.e. on the sponge strips at both ends of
+  // every row (config 2: 0.228 ms per step with 768 blocks, 0.213 with 2008).
+  h->tile_grid = 0;
+  h->tile_grid_sponge = 2008;
+  if (const char* tg = std::getenv("SEIGEN_HIP_TILE_GRID")) h->tile_grid = h->tile_grid_sponge = std::max(8, std::atoi(tg) / 8 * 8);
+  const char* ge = std::getenv("SEIGEN_HIP_GRAPH");  // 0/1 overrides (measurements)
+  const int64_t dofs = h->ncells * (int64_t)h->re.nd * (cfg->dim + cfg->dim * cfg->dim);
+  h->graph_ok = ge ? (std::strcmp(ge, "0") != 0) : (dofs <= (int64_t)1 << 23);
+  const char* ov = std::getenv("SEIGEN_HIP_OVERLAP");
+  h->overlap = cfg->nbr_mask != 0 && !(ov && std::strcmp(ov, "0") == 0);
+  int prio_lo = 0, prio_hi = 0;
+  HIPCHECK(h, hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
+  if (cfg->stream) {
+    h->stream = (hipStream_t)cfg->stream;
+  } else {
+    HIPCHECK(h, hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, h->overlap ? prio_hi : 0));
+    h->own_stream = true;
+  }
+  if (h->overlap) {
+    HIPCHECK(h, hipStreamCreateWithPriority(&h->stream2, hipStreamNonBlocking, prio_lo));
+    HIPCHECK(h, hipEventCreateWithFlags(&h->ev_stage, hipEventDisableTiming));
+    HIPCHECK(h, hipEventCreateWithFlags(&h->ev_second, hipEventDisableTiming));
+  }
+  HIPCHECK(h, hipEventCreate(&h->ev0));
+  HIPCHECK(h, hipEventCreate(&h->ev1));
+  HIPCHECK(h, hipDeviceSynchronize());
+  return SG_OK;
+}
+
 extern "C" {
 
 const char* sg_last_error(const sg_handle* h) { return h ? h->err.c_str() : g_create_err.c_str(); }
@@ -48,279 +333,6 @@ void sg_destroy(sg_handle* h) {
   delete h;
 }
 
-static int create_impl(const sg_config* cfg, sg_handle* h) {
-  if (cfg->dim < 1 || cfg->dim > 3) return fail(h, SG_ERR_ARG, "dim must be 1, 2 or 3");
-  if (cfg->degree < 1 || cfg->degree > 4) return fail(h, SG_ERR_ARG, "degree must be 1..4");
-  for (int a = 0; a < cfg->dim; ++a) {
-    if (cfg->n[a] < 1) return fail(h, SG_ERR_ARG, "n[axis] must be >= 1");
-    if (!(cfg->h[a] > 0.0)) return fail(h, SG_ERR_ARG, "h[axis] must be > 0");
-  }
-  h->cfg = *cfg;
-  for (int a = cfg->dim; a < 3; ++a) {
-    h->cfg.n[a] = 1;
-    h->cfg.h[a] = 1.0;
-    h->cfg.origin[a] = 0.0;
-    h->cfg.cube0[a] = 0;
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(h, SG_ERR_DEVICE, "no HIP device available (libseigen_hip has no CPU fallback)");
-  if (cfg->device < 0 || cfg->device >= ndev) return fail(h, SG_ERR_ARG, "device ordinal out of range");
-  HIPCHECK(h, hipSetDevice(cfg->device));
-
-  if (cfg->diagonal == SG_DIAGONAL_QUAD && cfg->dim == 1) return fail(h, SG_ERR_ARG, "tensor-product cells need dim 2 or 3");
-  try {
-    h->re = make_refelem(cfg->dim, cfg->degree, cfg->diagonal == SG_DIAGONAL_QUAD ? KIND_TENSOR : KIND_SIMPLEX);
-    std::memset(&h->md, 0, sizeof(MeshDev));
-    h->md.nd = h->re.nd;
-    h->md.nf = h->re.nf;
-    build_mesh_tables(cfg->dim, cfg->degree, cfg->diagonal, h->cfg.h, h->re.fnode.data(), h->re.lattice.data(), h->md);
-  } catch (const std::exception& e) {
-    return fail(h, SG_ERR_ARG, e.what());
-  }
-  for (int a = 0; a < 3; ++a) h->md.n[a] = h->cfg.n[a];
-  for (int s = 0; s < 6; ++s) h->md.has_nbr[s] = (s < 2 * cfg->dim) ? ((cfg->nbr_mask >> s) & 1) : 0;
-  h->ncls = h->md.ncls;
-  h->ncells = (int64_t)h->cfg.n[0] * h->cfg.n[1] * h->cfg.n[2] * h->ncls;
-  const KernelPath kp = choose_kernel_path(*cfg);
-  h->use_mfma = kp.mfma;
-  h->use_lane = kp.lane;
-  h->use_tile = kp.tile;
-  h->use_hexm = kp.hexm;
-  if (cfg->dtype != 0 && cfg->dtype != 1) return fail(h, SG_ERR_ARG, "dtype must be 0 (f64) or 1 (f32)");
-  h->f32 = cfg->dtype;
-  if (h->f32 && !h->use_mfma && !h->use_tile)
-    return fail(h, SG_ERR_ARG, "dtype f32 is implemented on the MFMA paths (3-D blocks: degree 1 from 65536 cells; 2-D "
-                               "blocks on the tile kernels)");
-  h->md.gw = kp.gw;
-  h->md.ncube = (int64_t)h->cfg.n[0] * h->cfg.n[1] * h->cfg.n[2];
-  h->md.ncube_pad = (h->md.ncube + h->md.gw - 1) / h->md.gw * h->md.gw;
-  if (h->use_tile) h->t2c = tile2d_const(h->md);
-  for (int f = 0; f < 4; ++f)
-    for (int s = 0; s < 6; ++s) h->ghost[f][s] = nullptr;
-  std::memset(&h->counters, 0, sizeof(h->counters));
-
-  const int d = cfg->dim, nd = h->re.nd, nf = h->re.nf, nfaces = h->re.nfaces;
-  // transposed operators: Dt[r][b][a], Lt[f][b'][a]
-  std::vector<double> Dt((size_t)d * nd * nd), Lt((size_t)nfaces * nf * nd);
-  for (int r = 0; r < d; ++r)
-    for (int a = 0; a < nd; ++a)
-      for (int b = 0; b < nd; ++b) Dt[((size_t)r * nd + b) * nd + a] = h->re.D[((size_t)r * nd + a) * nd + b];
-  for (int f = 0; f < nfaces; ++f)
-    for (int a = 0; a < nd; ++a)
-      for (int b = 0; b < nf; ++b) Lt[((size_t)f * nf + b) * nd + a] = h->re.L[((size_t)f * nd + a) * nf + b];
-  if (h->re.kind == KIND_TENSOR && cfg->dim == 3) {
-    // hexahedra, both kernel families (kernels_lane.hip hex_stage, kernels.hip stage_kernel TP = 2): the 1-D factors D1 [n1][n1] and lift1 [2][n1] of the
-    // tensor-product operators, read off the full tables along the first axis and checked against ALL of D_r, L_f
-    const int n1 = cfg->degree + 1;
-    auto node = [&](int a0, int a1, int a2) { return a0 + n1 * (a1 + n1 * a2); };
-    Dt.assign((size_t)n1 * n1 + 2 * n1, 0.0);
-    for (int m = 0; m < n1; ++m) {
-      for (int n = 0; n < n1; ++n) Dt[(size_t)m * n1 + n] = h->re.D[((size_t)0 * nd + node(m, 0, 0)) * nd + node(n, 0, 0)];
-      for (int s = 0; s < 2; ++s) Dt[(size_t)n1 * n1 + s * n1 + m] = h->re.L[((size_t)s * nd + node(m, 0, 0)) * nf + 0];
-    }
-    double worst = 0.0;
-    for (int a = 0; a < nd; ++a) {
-      const int ai[3] = {a % n1, (a / n1) % n1, a / (n1 * n1)};
-      for (int r = 0; r < 3; ++r) {
-        for (int b = 0; b < nd; ++b) {
-          const int bi[3] = {b % n1, (b / n1) % n1, b / (n1 * n1)};
-          const bool line = ai[(r + 1) % 3] == bi[(r + 1) % 3] && ai[(r + 2) % 3] == bi[(r + 2) % 3];
-          const double want = line ? Dt[(size_t)ai[r] * n1 + bi[r]] : 0.0;
-          worst = std::max(worst, std::fabs(h->re.D[((size_t)r * nd + a) * nd + b] - want));
-        }
-        for (int s = 0; s < 2; ++s)
-          for (int bp = 0; bp < nf; ++bp) {
-            const int b = h->re.fnode[(size_t)(2 * r + s) * nf + bp];
-            const int bi[3] = {b % n1, (b / n1) % n1, b / (n1 * n1)};
-            // facet nodes in ascending order: bp = lower transverse index + n1 * the upper one
-            const int lo = r == 0 ? 1 : 0, hi = r == 2 ? 1 : 2;
-            // ... and the neighbour's matching node is the one across the cube, at the same place of its facet list
-            int ni[3] = {bi[0], bi[1], bi[2]};
-            ni[r] = s ? 0 : n1 - 1;
-            if (bp != bi[lo] + n1 * bi[hi] || bi[r] != (s ? n1 - 1 : 0) || h->md.fnode[2 * r + s][bp] != b ||
-                h->md.nb_node[0][2 * r + s][bp] != node(ni[0], ni[1], ni[2]) || h->md.nb_fnode[0][2 * r + s][bp] != bp ||
-                h->md.nb_face[0][2 * r + s] != 2 * r + (1 - s) || h->md.nb_axis[0][2 * r + s] != r)
-              return fail(h, SG_ERR_ARG, "hexahedral element: unexpected facet node order");
-            const bool same = ai[lo] == bi[lo] && ai[hi] == bi[hi];
-            const double want = same ? Dt[(size_t)n1 * n1 + s * n1 + ai[r]] : 0.0;
-            worst = std::max(worst, std::fabs(h->re.L[((size_t)(2 * r + s) * nd + a) * nf + bp] - want));
-          }
-      }
-    }
-    if (worst > 1e-11) return fail(h, SG_ERR_ARG, "hexahedral element: the operator tables do not factorise");
-    if (h->use_hexm) {     // kernels_hexm.hip: line operators with the own-trace half folded in, x-pass A operands
-      const std::vector<double> d1l(Dt);
-      Dt = hexm_table(cfg->degree, d1l.data(), d1l.data() + (size_t)n1 * n1, h->md);
-    }
-  } else if (h->use_lane) {
-    // lane path: E_r = D_r - (L_0 R_0 - L_{r+1} R_{r+1}) / (2 (d-1)!) row-major (own-trace half of the
-    // central flux folded into the volume operator, see mfma_tables.cpp), and L_f row-major
-    double fact = 1.0;
-    for (int i = 2; i <= d - 1; ++i) fact *= i;
-    const double cfold = 1.0 / (2.0 * fact);
-    for (int r = 0; r < d; ++r)
-      for (int a = 0; a < nd; ++a)
-        for (int b = 0; b < nd; ++b) {
-          double v = h->re.D[((size_t)r * nd + a) * nd + b];
-          for (int bf = 0; bf < nf; ++bf) {
-            if (h->re.fnode[(size_t)0 * nf + bf] == b) v -= cfold * h->re.L[((size_t)0 * nd + a) * nf + bf];
-            if (h->re.fnode[(size_t)(r + 1) * nf + bf] == b) v += cfold * h->re.L[((size_t)(r + 1) * nd + a) * nf + bf];
-          }
-          Dt[((size_t)r * nd + a) * nd + b] = v;
-        }
-    for (size_t i = 0; i < Lt.size(); ++i) Lt[i] = h->re.L[i];
-  }
-  HIPCHECK(h, h->Dt.upload(Dt.data(), Dt.size()));
-  HIPCHECK(h, h->Lt.upload(Lt.data(), Lt.size()));
-  HIPCHECK(h, h->md_dev.upload(&h->md, 1));
-  if (h->use_mfma) {
-    const MfmaConst mk = mfma_const(h->md);
-    HIPCHECK(h, h->mk_dev.upload(&mk, 1));
-    {
-      std::vector<int32_t> ft;
-      mfma_trace_offsets(h->md, 9, ft);
-      HIPCHECK(h, h->ftab_dev.upload(ft.data(), ft.size()));
-    }
-    if ((h->md.ncube_pad / 16) * 6 * 16 >= ((int64_t)1 << 31))     // cell slots are int32 (288 GB hold far fewer cells)
-      return fail(h, SG_ERR_ARG, "block too large for the MFMA path's neighbour table");
-    {
-      std::vector<int32_t> tab;
-      build_nbr_table(h->md, tab);
-      HIPCHECK(h, h->nbr_tab.upload(tab.data(), tab.size()));
-    }
-  }
-
-  for (int f = 0; f < 4; ++f) {
-    size_t comps = field_is_stress(f) ? (size_t)d * d : (size_t)d;
-    h->field_len[f] = (size_t)h->ncells * nd * comps;
-    h->field_alloc[f] = (size_t)h->md.ncube_pad * h->ncls * nd * comps;
-    const size_t n = h->f32 ? (h->field_alloc[f] + 1) / 2 : h->field_alloc[f];   // in doubles
-    if (h->field[f].alloc(n) != hipSuccess) return fail(h, SG_ERR_NOMEM, "hipMalloc of a field buffer failed");
-    HIPCHECK(h, hipMemset(h->field[f].get(), 0, n * sizeof(double)));
-  }
-  if ((h->use_mfma || h->use_tile) && h->f32) {
-    std::vector<float> fF, fG, fL;
-    if (h->use_tile) {
-      fF = tile2d_frags32_V(h->re, -1.0);
-      fG = tile2d_frags32_V(h->re, 1.0);
-      fL = tile2d_frags32_L(h->re);
-    } else {
-      fF = mfma32_frags_F(h->re);
-      fG = mfma32_frags_G(h->re);
-      fL = mfma32_frags_L(h->re);
-    }
-    // float tables in double owners (StageArgs::fragV / fragL are double pointers, as the fields are)
-    for (auto [buf, v] : {std::make_pair(&h->fragF, &fF), std::make_pair(&h->fragG, &fG), std::make_pair(&h->fragL, &fL)}) {
-      HIPCHECK(h, buf->alloc((v->size() + 1) / 2));
-      HIPCHECK(h, hipMemcpy(buf->get(), v->data(), v->size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-  } else if (h->use_mfma || h->use_tile) {
-    std::vector<double> fF, fG, fL;
-    if (h->use_tile) {
-      fF = tile2d_frags_V(h->re, -1.0);
-      fG = tile2d_frags_V(h->re, 1.0);
-      fL = tile2d_frags_L(h->re);
-    } else {
-      fF = mfma_frags_F(h->re);
-      fG = mfma_frags_G(h->re);
-      fL = mfma_frags_L(h->re);
-    }
-    HIPCHECK(h, h->fragF.upload(fF.data(), fF.size()));
-    HIPCHECK(h, h->fragG.upload(fG.data(), fG.size()));
-    HIPCHECK(h, h->fragL.upload(fL.data(), fL.size()));
-    // factorised G volume (mfma_tables.hpp): D_r = P_r Q
-    const char* gq = std::getenv("SEIGEN_HIP_GQ");
-    // default: degree 4 only (G<4,0> -2 %, step -0.7 .. -1 %; at degree 3, rank 10 of 20 on 4-row tiles, it is 12 % slower:
-    // profiles/r04/kernel_experiments.txt); SEIGEN_HIP_GQ=0 / 1 forces it off / on for degrees 3 and 4
-    if (h->use_mfma && cfg->degree >= 3 && (gq ? std::atoi(gq) != 0 : cfg->degree >= SG_GQ_FROM_DEGREE)) {
-      std::vector<double> fQ, fP;
-      try {
-        fQ = mfma_frags_Q(h->re);
-        fP = mfma_frags_P(h->re);
-      } catch (const std::exception& e) {
-        return fail(h, SG_ERR_ARG, e.what());
-      }
-      HIPCHECK(h, h->fragQ.upload(fQ.data(), fQ.size()));
-      HIPCHECK(h, h->fragP.upload(fP.data(), fP.size()));
-    }
-  }
-  if (h->use_mfma || h->use_lane || h->use_tile || h->use_hexm) {
-    // symmetric-stress mode (DESIGN.md): fields start at zero, g only produces symmetric tensors;
-    // left for good as soon as the user uploads a non-symmetric stress or source (SEIGEN_HIP_SYM=0: never entered)
-    const char* sym_env = std::getenv("SEIGEN_HIP_SYM");
-    h->sym = !(sym_env && std::strcmp(sym_env, "0") == 0);
-    const int zero = 0;
-    HIPCHECK(h, h->sym_flag.upload(&zero, 1));
-  }
-  if (std::getenv("SEIGEN_HIP_STAMPS")) {
-    const std::vector<unsigned long long> zeros(32, 0);
-    HIPCHECK(h, h->dbg.upload(zeros.data(), zeros.size()));
-  }
-  {
-    // Persistent grid of the MFMA stage kernels: two blocks per CU fill every CU (registers and
-    // LDS allow exactly two).  A block with halo neighbours leaves 1/16 of those slots empty, so
-    // that RCCL's send/receive kernels can start WHILE an interior launch runs: behind a full
-    // grid they only start when it drains (tools/overlap_probe.py), and a stage kernel that found
-    // some of its own slots taken would run the late blocks' static shares one after the other.
-    hipDeviceProp_t prop;
-    HIPCHECK(h, hipGetDeviceProperties(&prop, cfg->device));
-    const int slots = (h->use_mfma ? mfma_blocks_per_cu(cfg->degree, h->f32) : (h->use_hexm ? hexm_blocks_per_cu(cfg->degree) : 2)) *
-                      prop.multiProcessorCount;
-    h->grid_full = slots / 8 * 8;
-    h->grid_blocks = (cfg->nbr_mask != 0 ? slots - slots / 16 : slots) / 8 * 8;
-    if (const char* gb = std::getenv("SEIGEN_HIP_GRID_BLOCKS")) h->grid_blocks = std::max(8, std::atoi(gb) / 8 * 8);
-    if (cfg->nbr_mask == 0) h->grid_full = h->grid_blocks;
-    // F stages of a whole 3-D block: items dealt to the XCDs in chunks of 1/8 of a z-layer of cubes, so that all XCDs
-    // sweep the block layer by layer together (the z-neighbour traces then meet the own rows of the next layer in the
-    // Infinity Cache: F stages -3 %, profiles/r03/order_chunk_sweep.txt; the G stages do not gain and keep one
-    // contiguous range per XCD).  SEIGEN_HIP_ORDER_CHUNK overrides (0 = off).
-    h->order_chunk = 0;
-    if (h->use_mfma && cfg->dim == 3) {
-      const int64_t per_layer = ((int64_t)cfg->n[0] * cfg->n[1] + 15) / 16 * 6;
-      if (cfg->n[2] >= 16) h->order_chunk = (int)std::max<int64_t>(6, (per_layer + 7) / 8);
-    }
-    if (const char* oc = std::getenv("SEIGEN_HIP_ORDER_CHUNK")) h->order_chunk = std::max(0, std::atoi(oc));
-    h->no_whole = std::getenv("SEIGEN_HIP_NO_WHOLE") != nullptr;
-    // 2-D tile kernels: a persistent grid of exactly the blocks the device holds of the stage's kernel (0 = the launcher
-    // asks the runtime per instantiation, kernels_tile2d.hip) - a wave sets up once and works through its share of the
-    // items: 2-D P4 at N = 256 (the reference's benchmark protocol) 84.5 -> 93.4 G DoF-updates/s against one item per
-    // wave, P3 +8 %, level elsewhere (profiles/r05/tile_grid_sweep.txt).  With a sponge the items differ in cost and a
-    // static share can collect the expensive ones: then 251 blocks per XCD label - with an odd (prime) stride of 4 * 251
-    // items a wave's items do not keep falling on the same column of the mesh, i.e. on the sponge strips at both ends of
-    // every row (config 2: 0.228 ms per step with 768 blocks, 0.213 with 2008).
-    h->tile_grid = 0;
-    h->tile_grid_sponge = 2008;
-    if (const char* tg = std::getenv("SEIGEN_HIP_TILE_GRID")) h->tile_grid = h->tile_grid_sponge = std::max(8, std::atoi(tg) / 8 * 8);
-  }
-  {
-    const char* ge = std::getenv("SEIGEN_HIP_GRAPH");  // 0/1 overrides (measurements)
-    const int64_t dofs = h->ncells * (int64_t)h->re.nd * (cfg->dim + cfg->dim * cfg->dim);
-    h->graph_ok = ge ? (std::strcmp(ge, "0") != 0) : (dofs <= (int64_t)1 << 23);
-  }
-  {
-    const char* ov = std::getenv("SEIGEN_HIP_OVERLAP");
-    h->overlap = cfg->nbr_mask != 0 && !(ov && std::strcmp(ov, "0") == 0);
-  }
-  int prio_lo = 0, prio_hi = 0;
-  HIPCHECK(h, hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-  if (cfg->stream) {
-    h->stream = (hipStream_t)cfg->stream;
-  } else {
-    HIPCHECK(h, hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, h->overlap ? prio_hi : 0));
-    h->own_stream = true;
-  }
-  if (h->overlap) {
-    HIPCHECK(h, hipStreamCreateWithPriority(&h->stream2, hipStreamNonBlocking, prio_lo));
-    HIPCHECK(h, hipEventCreateWithFlags(&h->ev_stage, hipEventDisableTiming));
-    HIPCHECK(h, hipEventCreateWithFlags(&h->ev_second, hipEventDisableTiming));
-  }
-  HIPCHECK(h, hipEventCreate(&h->ev0));
-  HIPCHECK(h, hipEventCreate(&h->ev1));
-  HIPCHECK(h, hipDeviceSynchronize());
-  return SG_OK;
-}
-
 int sg_create(const sg_config* cfg, sg_handle** out) {
   if (!cfg || !out) {
     g_create_err = "null argument";
@@ -328,7 +340,12 @@ int sg_create(const sg_config* cfg, sg_handle** out) {
   }
   *out = nullptr;
   sg_handle* h = new sg_handle();
-  int rc = create_impl(cfg, h);
+  Frags fr;
+  int rc = init_element(cfg, h);
+  if (rc == SG_OK) rc = init_family(h);
+  if (rc == SG_OK) rc = family_tables(h, fr);
+  if (rc == SG_OK) rc = init_fields(h, fr);
+  if (rc == SG_OK) rc = init_launch(h);
   if (rc != SG_OK) {
     g_create_err = h->err;
     sg_destroy(h);
@@ -455,21 +472,17 @@ int sg_set_absorption(sg_handle* h, const double* sigma_nodes, int sigma_degree)
     rq.ncells = h->ncells;
     rq.ncls = h->ncls;
     rq.gw = (int)h->md.gw;
-    // 2-D tile and 3-D matrix kernels, lane kernels: a sigma that is one value on all nodes of a cell (the piecewise-constant
-    // sponges of the reference's problem scripts, explosive_source_lf4.py:42-45) is applied as sigma u at the node
-    rq.want_scalar = h->use_tile || h->use_mfma || h->use_hexm || h->use_lane;
-    // the 3-D matrix kernels and the lane kernels read B u_abs from a pre-pass (kernels.hpp launch_sponge_pre); the 2-D tile
-    // kernels work their small matrices off themselves: a launch more per F stage costs them more
-    rq.pre_family = h->use_mfma || h->use_hexm || h->use_lane;
+    // a sigma that is one value on all nodes of a cell (the piecewise-constant sponges of the reference's problem scripts,
+    // explosive_source_lf4.py:42-45) is applied as sigma u at the node
+    rq.want_scalar = family_interleaved(h->family);
+    rq.pre_family = family_sponge_pre(h->family);
     // Affine cells take dim + 1 numbers (kernels.hip sponge_pre_affine_kernel, kernels_mfma.hip sponge_affine_mfma);
     // SEIGEN_HIP_SPONGE_AFFINE=0 sends them through their matrices (tests: the two must agree).  The lane kernels' cells -
     // hexahedra DQ_1 / DQ_2, gw = 64 - have matrices of at most 27 x 27 shared through the caches: there the matrix pre-pass
     // is the faster one (64.5 against 61.9 G at 96^3 DQ_2, profiles/r06/affine_sponge.txt); '1' forces the affine path
     const char* aff_env = std::getenv("SEIGEN_HIP_SPONGE_AFFINE");
-    rq.try_affine = rq.pre_family && !(aff_env && aff_env[0] == '0') && (!h->use_lane || (aff_env && aff_env[0] == '1'));
-    // 3-D MFMA family: the pre-pass results live in LINE layout like the fields (a record per cell cost the affine pre-pass
-    // scattered 24-byte stores and the F stage scattered loads)
-    rq.line_layout = h->use_mfma;
+    rq.try_affine = rq.pre_family && !(aff_env && aff_env[0] == '0') && (h->family != Family::Lane || (aff_env && aff_env[0] == '1'));
+    rq.line_layout = family_pre_lines(h->family);
     SpongePlan pl;
     try {
       pl = plan_sponge(rq, sigma_nodes);
@@ -477,7 +490,7 @@ int sg_set_absorption(sg_handle* h, const double* sigma_nodes, int sigma_degree)
       return fail(h, SG_ERR_ARG, std::string("sg_set_absorption: ") + e.what());
     }
     const bool pre = rq.pre_family && pl.nslots > 0, affine = rq.pre_family && pl.naffine > 0;
-    const bool aff_mfma = affine && h->use_mfma && !h->f32 && d == 3;   // on the matrix pipe (kernels_mfma.hip sponge_affine_mfma)
+    const bool aff_mfma = affine && h->family == Family::Mfma && !h->f32;   // on the matrix pipe (kernels_mfma.hip sponge_affine_mfma)
     if (affine) {
       if (rq.gw * nd > SG_SPONGE_AFFINE_MAX_ROWS)
         return fail(h, SG_ERR_STATE, "sg_set_absorption: the affine-sigma pre-pass takes at most " +
@@ -611,7 +624,7 @@ static int set_source(sg_handle* h, int64_t nnz, const int64_t* nodes, int64_t n
       src.weights.assign(weights, weights + nsteps);
       HIPCHECK(h, src.weights_d.upload(weights, (size_t)nsteps));
     }
-    if (h->use_tile && !std::getenv("SEIGEN_HIP_SOURCE_LAUNCH")) {
+    if (family_fused_source(h->family) && !std::getenv("SEIGEN_HIP_SOURCE_LAUNCH")) {
       // tile kernels: item (16 squares of one class) -> slot, and per slot a dense (node, cell) -> value-row table, so
       // that the G stages add the source themselves (one launch less per G stage).  (Nodes are unique here: entries of a
       // node listed twice were merged above.)

@@ -115,10 +115,7 @@ struct sg_handle {
   DevBuf<double> field[4];               // double, or float where f32
   size_t field_len[4] = {0, 0, 0, 0};    // doubles, host layout (ncells * nd * comps)
   size_t field_alloc[4] = {0, 0, 0, 0};  // values allocated on the device (layout padding included)
-  bool use_mfma = false;
-  bool use_lane = false;
-  bool use_tile = false;    // 2-D MFMA tile kernels (kernels_tile2d.hip), gw = 16
-  bool use_hexm = false;    // hexahedra DQ_3 / DQ_4 (kernels_hexm.hip), gw = 16
+  Family family = Family::Generic;   // the kernels that run the block (hostlogic.hpp); md.gw = family_gw(family)
   int f32 = 0;              // sg_config.dtype = 1: fields, halo buffers, operator tiles and arithmetic are float (MFMA path)
   bool sym = false;         // MFMA path: all stress fields symmetric -> kernels touch only the i <= j lines
   DevBuf<int> sym_flag;     // device word set by an upload that is not symmetric
@@ -158,7 +155,7 @@ struct sg_handle {
   bool capture_src = false;   // stage launches issued now (a capture) take slice and weight from src_ctr_d
   bool graph_src = false;     // the captured graphs contain the source launches
   // halo
-  const double* ghost[4][6];
+  const double* ghost[4][6] = {};
   // execution
   hipStream_t stream = nullptr;
   bool own_stream = false;
@@ -192,7 +189,7 @@ struct sg_handle {
   std::vector<int> ev_stage_ids;
   double first_ms_pending[6] = {-1, -1, -1, -1, -1, -1};
   int first_recorded_stage = -1;         // stage whose FIRST launch recorded ev_stage last (SECOND must follow it)
-  sg_counters_t counters;
+  sg_counters_t counters = {};
   std::string* name_out = nullptr;   // sg_stage_kernel_name: stage launches only name their kernel (StageArgs::name_out)
   bool no_whole = false;             // SEIGEN_HIP_NO_WHOLE (diagnostic): region launches always test the boxes
   std::string err;
@@ -242,7 +239,7 @@ inline hipError_t sync_all(sg_handle* h) {
 // transfer.cpp: make the (i > j) lines of both stress buffers valid again and continue with the full-tensor kernels
 int leave_sym_mode(sg_handle* h);
 
-// hostapi.cpp (hostlogic.hpp): kernel-family choice and the regions of a split stage
+// hostapi.cpp (hostlogic.hpp): the regions of a split stage
 inline void region_boxes(const sg_handle* h, int region, std::vector<Box>& out) {
   region_boxes(h->cfg.dim, h->cfg.n, h->md.has_nbr, region, out,
                shell_width_x(h->md.gw, h->cfg.n[0], h->md.has_nbr[0] != 0, h->md.has_nbr[1] != 0));

@@ -6,75 +6,52 @@
 #include <cstdlib>
 
 #include "hostlogic.hpp"
-#include "kernels.hpp"
 
 using namespace sg;
 
 std::string g_create_err;
 
-// Which kernel family runs a block (and with it the layout's group width gw: 16 cubes per 128-byte line for the
-// MFMA and tile kernels, 64 for the lane kernels, 1 = host layout for the generic kernel).
-KernelPath choose_kernel_path(const sg_config& cfg) {
-  KernelPath kp;
-  if (cfg.diagonal == SG_DIAGONAL_QUAD) {
-    // quadrilateral cells: the MFMA tile kernels (DQ_4: two 16-row tiles), or on request the table-driven generic
-    // kernels (host layout); same size threshold and SEIGEN_HIP_PATH overrides as for triangles
-    const char* pe = std::getenv("SEIGEN_HIP_PATH");
-    const bool fg = pe && std::strcmp(pe, "generic") == 0, ft = pe && std::strcmp(pe, "tile") == 0;
-    kp.tile = cfg.dim == 2 && tile2d_supported_quad(cfg.degree) && !fg &&
-              (ft || (int64_t)cfg.n[0] * cfg.n[1] >= SG_TILE2D_MIN_CELLS / 2);
-    // hexahedra (DQ_1, DQ_2): the sum-factorised lane-per-cell kernels (kernels_lane.hip hex_stage) from
-    // SG_HEX_LANE_MIN_CELLS(degree) cubes up (below that the thread-per-node generic kernel has more parallelism);
-    // SEIGEN_HIP_PATH=lane / generic forces one or the other
-    const bool fl = pe && std::strcmp(pe, "lane") == 0;
-    kp.lane = cfg.dim == 3 && lane_supported_hex(cfg.dim, cfg.degree) && !fg &&
-              (fl || (int64_t)cfg.n[0] * cfg.n[1] * cfg.n[2] >= SG_HEX_LANE_MIN_CELLS(cfg.degree));
-    // hexahedra DQ_3 / DQ_4: lines in registers, x lines on the matrix pipe (kernels_hexm.hip) at every size;
-    // SEIGEN_HIP_PATH=generic: the thread-per-node kernel
-    kp.hexm = cfg.dim == 3 && hexm_supported(cfg.dim, cfg.degree) && !fg;
-    kp.gw = (kp.tile || kp.hexm) ? 16 : (kp.lane ? 64 : 1);
-    return kp;
-  }
-  const int ncls = cfg.dim == 1 ? 1 : (cfg.dim == 2 ? 2 : 6);
-  // kernel path: MFMA kernels (interleaved layout) where they exist, unless SEIGEN_HIP_PATH=generic
-  const char* path_env = std::getenv("SEIGEN_HIP_PATH");
-  const bool force_generic = path_env && std::strcmp(path_env, "generic") == 0;
-  // 3-D: the MFMA kernels at every degree (degrees 1 and 2 use 4x4x4 tiles only); measured with
-  // tools/path_sweep.py they beat the lane and generic kernels everywhere except degree 1 on blocks
-  // under 65536 cells (SEIGEN_HIP_PATH=mfma forces them)
-  const bool force_mfma = path_env && std::strcmp(path_env, "mfma") == 0;
-  const int64_t ncube_all = (int64_t)cfg.n[0] * (cfg.dim > 1 ? cfg.n[1] : 1) * (cfg.dim > 2 ? cfg.n[2] : 1);
-  const int64_t ncells_all = ncube_all * ncls;
-  kp.mfma = mfma_supported(cfg.dim, cfg.degree) && !force_generic &&
-            !(path_env && std::strcmp(path_env, "lane") == 0) &&
-            (cfg.degree >= 2 || ncells_all >= 65536 || force_mfma);
-  // lane-per-cell kernels need enough 64-cell groups to fill the chip; below that the
-  // thread-per-node generic kernel has more parallelism (SEIGEN_HIP_PATH=lane forces them)
-  const bool force_lane = path_env && std::strcmp(path_env, "lane") == 0;
-  kp.lane = !kp.mfma && lane_supported(cfg.dim, cfg.degree) && !force_generic &&
-            (force_lane || ncells_all >= (cfg.degree == 1 ? 196608 : 120000));  // crossovers measured
-                                                                 // (tools/path_sweep.py, profiles/r02/small_2d_configs_negative_results.txt)
-  // 2-D: the MFMA tile kernels (16 cells per wave, operators in registers) from SG_TILE2D_MIN_CELLS cells up
-  // (measured crossover against the generic kernel, tools/path_sweep.py); SEIGEN_HIP_PATH=tile forces them
-  const bool force_tile = path_env && std::strcmp(path_env, "tile") == 0;
-  kp.tile = tile2d_supported(cfg.dim, cfg.degree) && !force_generic && !force_lane &&
-            (force_tile || ncells_all >= SG_TILE2D_MIN_CELLS);
-  if (kp.tile) kp.lane = false;
-  kp.gw = (kp.mfma || kp.tile) ? 16 : (kp.lane ? 64 : 1);
-  return kp;
-}
-
-namespace sg {
-// which (dim, degree) each kernel family is instantiated for (kernels_mfma.hip, kernels_lane.hip, kernels_tile2d.hip)
-bool mfma_supported(int dim, int P) { return dim == 3 && P >= 1 && P <= 4; }
+// which (dim, degree) each kernel family is instantiated for (kernels_mfma.hip, kernels_lane.hip, kernels_tile2d.hip,
+// kernels_hexm.hip)
+static bool mfma_supported(int dim, int P) { return dim == 3 && P >= 1 && P <= 4; }
 // 3-D: only P1/P2 fit a lane's registers (P3/P4 take the MFMA path)
-bool lane_supported(int dim, int P) { return ((dim == 1 || dim == 2) && P >= 1 && P <= 4) || (dim == 3 && (P == 1 || P == 2)); }
+static bool lane_supported(int dim, int P) { return ((dim == 1 || dim == 2) && P >= 1 && P <= 4) || (dim == 3 && (P == 1 || P == 2)); }
 // hexahedra: DQ_1 and DQ_2 (27 nodes) fit a lane's registers one component at a time
-bool lane_supported_hex(int dim, int P) { return dim == 3 && (P == 1 || P == 2); }
-bool hexm_supported(int dim, int P) { return dim == 3 && (P == 3 || P == 4); }
-bool tile2d_supported(int dim, int P) { return dim == 2 && P >= 1 && P <= 4; }
-bool tile2d_supported_quad(int P) { return P >= 1 && P <= 4; }   // DQ_4 has 25 rows: two row tiles, one after the other
-}  // namespace sg
+static bool lane_supported_hex(int dim, int P) { return dim == 3 && (P == 1 || P == 2); }
+static bool hexm_supported(int dim, int P) { return dim == 3 && (P == 3 || P == 4); }
+static bool tile2d_supported(int dim, int P) { return dim == 2 && P >= 1 && P <= 4; }   // DQ_4 has 25 rows: two row tiles
+
+// SEIGEN_HIP_PATH=generic: the generic kernels everywhere; =lane / =mfma / =tile: that family below its size threshold
+// where it exists (an unknown value: as unset)
+Family choose_kernel_path(const sg_config& cfg) {
+  const char* pe = std::getenv("SEIGEN_HIP_PATH");
+  const std::string path = pe ? pe : "";
+  if (path == "generic") return Family::Generic;
+  const bool force_lane = path == "lane";
+  const int d = cfg.dim, P = cfg.degree;
+  const int64_t ncube = (int64_t)cfg.n[0] * (d > 1 ? cfg.n[1] : 1) * (d > 2 ? cfg.n[2] : 1);
+  if (cfg.diagonal == SG_DIAGONAL_QUAD) {
+    // quadrilaterals: the MFMA tile kernels (DQ_4: two 16-row tiles) at every size, SEIGEN_HIP_PATH=lane included
+    if (tile2d_supported(d, P)) return Family::Tile2d;
+    // hexahedra DQ_3 / DQ_4: lines in registers, x lines on the matrix pipe (kernels_hexm.hip) at every size
+    if (hexm_supported(d, P)) return Family::Hexm;
+    // hexahedra DQ_1 / DQ_2: the sum-factorised lane-per-cell kernels (kernels_lane.hip hex_stage) from
+    // SG_HEX_LANE_MIN_CELLS(degree) cubes up (below that the thread-per-node generic kernel has more parallelism)
+    if (lane_supported_hex(d, P) && (force_lane || ncube >= SG_HEX_LANE_MIN_CELLS(P))) return Family::Lane;
+    return Family::Generic;
+  }
+  const int64_t ncells = ncube * (d == 1 ? 1 : (d == 2 ? 2 : 6));
+  // 3-D: the MFMA kernels at every degree (degrees 1 and 2 use 4x4x4 tiles only); measured with tools/path_sweep.py they
+  // beat the lane and generic kernels everywhere except degree 1 on blocks under 65536 cells
+  if (mfma_supported(d, P) && !force_lane && (P >= 2 || ncells >= 65536 || path == "mfma")) return Family::Mfma;
+  // 2-D: the MFMA tile kernels (16 cells per wave, operators in registers) at every size: they win at every size measured,
+  // 40 x 40 squares included (tools/path_sweep2d.py, profiles/r02/path_sweep2d_tile_v2.txt)
+  if (tile2d_supported(d, P) && !force_lane) return Family::Tile2d;
+  // lane-per-cell kernels need enough 64-cell groups to fill the chip; below that the thread-per-node generic kernel has
+  // more parallelism (crossovers measured: tools/path_sweep.py, profiles/r02/small_2d_configs_negative_results.txt)
+  if (lane_supported(d, P) && (force_lane || ncells >= (P == 1 ? 196608 : 120000))) return Family::Lane;
+  return Family::Generic;
+}
 
 void region_boxes(int d, const int32_t n[3], const int32_t has_nbr[6], int region, std::vector<Box>& out, int xw) {
   out.clear();
@@ -245,7 +222,7 @@ int sg_region_boxes(const sg_config* cfg, int region, int32_t* boxes, int max_bo
   for (int a = 0; a < cfg->dim; ++a) n[a] = cfg->n[a];
   for (int s2 = 0; s2 < 2 * cfg->dim; ++s2) has_nbr[s2] = (cfg->nbr_mask >> s2) & 1;
   std::vector<Box> out;
-  region_boxes(cfg->dim, n, has_nbr, region, out, shell_width_x(choose_kernel_path(*cfg).gw, n[0], has_nbr[0] != 0, has_nbr[1] != 0));
+  region_boxes(cfg->dim, n, has_nbr, region, out, shell_width_x(family_gw(choose_kernel_path(*cfg)), n[0], has_nbr[0] != 0, has_nbr[1] != 0));
   int cnt = 0;
   for (const Box& b : out) {
     if (b.n[0] <= 0 || b.n[1] <= 0 || b.n[2] <= 0) continue;

@@ -13,18 +13,42 @@
 
 extern std::string g_create_err;   // message of the last failed sg_create / device-free query
 
-// smallest 2-D block (cells) that takes the MFMA tile kernels instead of the generic kernel: they win at every
-// size measured, 40 x 40 squares included (tools/path_sweep2d.py, profiles/r02/path_sweep2d_tile_v2.txt)
-static constexpr int64_t SG_TILE2D_MIN_CELLS = 0;
+// Which kernel family runs a block (choose_kernel_path, hostapi.cpp):
+//   Generic  thread-per-node, table-driven kernels on the host layout (kernels.hip); every element
+//   Lane     lane-per-cell (kernels_lane.hip): 1-D / 2-D simplices and 3-D P1 / P2 on request, hexahedra DQ_1 / DQ_2
+//   Mfma     3-D simplices on the matrix pipe (kernels_mfma.hip)
+//   Tile2d   2-D MFMA tiles (kernels_tile2d.hip): triangles and quadrilaterals
+//   Hexm     hexahedra DQ_3 / DQ_4, lines in registers, x lines on the matrix pipe (kernels_hexm.hip)
+enum class Family { Generic, Lane, Mfma, Tile2d, Hexm };
+Family choose_kernel_path(const sg_config& cfg);
+// measured crossover of the (sum-factorised) generic and the lane kernels on hexahedra (tools/experiments/
+// hex_crossover.py, profiles/r04/hexahedra.txt): between 24^3 and 32^3 cubes at both degrees
+#ifndef SG_HEX_LANE_MIN_CELLS
+#define SG_HEX_LANE_MIN_CELLS(degree) 24000
+#endif
+
+// What the host code asks about a family.  The layout's group width (MeshDev::gw): 16 cubes per 128-byte line for the
+// matrix-pipe families, 64 for the lane kernels, 1 = host layout for the generic kernels.
+inline int family_gw(Family f) { return f == Family::Generic ? 1 : (f == Family::Lane ? 64 : 16); }
+// Every family but the generic one: interleaved layout, one launch per region over (cell group, class) items, the
+// symmetric-stress mode, and a sigma that is one value on all nodes of a cell applied as sigma u at the node.
+inline bool family_interleaved(Family f) { return f != Family::Generic; }
+// sg_config.dtype = 1 (fields, halo buffers, operator tiles and arithmetic in float)
+inline bool family_f32(Family f) { return f == Family::Mfma || f == Family::Tile2d; }
+// F stages read B u_abs of the sponge cells from a pre-pass (kernels.hpp launch_sponge_pre); the 2-D tile kernels work
+// their small matrices off themselves: a launch more per F stage costs them more
+inline bool family_sponge_pre(Family f) { return f == Family::Mfma || f == Family::Hexm || f == Family::Lane; }
+// ... and the pre-pass results live in line layout like the fields (3-D MFMA: a record per cell cost the affine
+// pre-pass scattered 24-byte stores and the F stage scattered loads)
+inline bool family_pre_lines(Family f) { return f == Family::Mfma; }
+// the G stage kernels add the source themselves (StageArgs::src_slot / src_idx; SEIGEN_HIP_SOURCE_LAUNCH: a launch of its own)
+inline bool family_fused_source(Family f) { return f == Family::Tile2d; }
+// a region of whole cell groups runs as a whole-block launch: no cube coordinates, no box tests (StageArgs::all_active)
+inline bool family_whole_groups(Family f) { return f == Family::Mfma || f == Family::Hexm; }
 
 struct Box {
   int o[3], n[3];
 };
-struct KernelPath {
-  bool mfma = false, lane = false, tile = false, hexm = false;
-  int gw = 1;
-};
-KernelPath choose_kernel_path(const sg_config& cfg);
 // shell thickness along x: the interleaved layouts put gw consecutive cubes of an x-row on the lanes of one item, so a
 // one-cube shell next to an x side would use one lane in gw of every item it touches AND make the launch that owns the
 // other gw - 1 lanes run the same item again.  With whole groups in the shell no item is cut (2 x 2 x 2).

@@ -175,26 +175,17 @@ std::string kernel_name_of(const void* host_fn);
 int launch_stage(int kind, int dim, int P, const StageArgs& a, void* stream);
 
 // MFMA path (3-D, degree >= 3; fields in the gw = 16 interleaved layout)
-bool mfma_supported(int dim, int P);
 int mfma_blocks_per_cu(int P, int f32);
 int launch_stage_mfma(int kind, int P, const StageArgs& a, void* stream);
 
 // lane-per-cell path (1-D / 2-D; fields in the gw = 64 interleaved layout; a.Dt = E[r][a][b],
-// a.Lt = L[f][a][b'] row-major)
-bool lane_supported(int dim, int P);
-// measured crossover of the (sum-factorised) generic and the lane kernels on hexahedra (tools/experiments/
-// hex_crossover.py, profiles/r04/hexahedra.txt): between 24^3 and 32^3 cubes at both degrees
-#ifndef SG_HEX_LANE_MIN_CELLS
-#define SG_HEX_LANE_MIN_CELLS(degree) 24000
-#endif
-bool lane_supported_hex(int dim, int P);   // a.tensor: hexahedra (sum-factorised; a.Dt = {D1, lift1})
+// a.Lt = L[f][a][b'] row-major; a.tensor: hexahedra, sum-factorised, a.Dt = {D1, lift1})
+int launch_stage_lane(int kind, int dim, int P, const StageArgs& a, long nitems, void* stream);
 // hexahedra DQ_3 / DQ_4 with the lines of a cube in registers and the x lines on the matrix pipe (kernels_hexm.hip; fields
 // in the gw = 16 interleaved layout; a.Dt = hexm_table(): line operators E_k, trace lifts, x-pass A operands)
-bool hexm_supported(int dim, int P);
 int hexm_blocks_per_cu(int P);
 std::vector<double> hexm_table(int P, const double* D1, const double* lift1, const MeshDev& md_host);
 int launch_stage_hexm(int kind, int P, const StageArgs& a, long nitems, void* stream);
-int launch_stage_lane(int kind, int dim, int P, const StageArgs& a, long nitems, void* stream);
 
 // 2-D MFMA tile path (P1..P4; fields in the gw = 16 interleaved layout; a.fragV / a.fragL = tile2d_frags_*).
 // T2Const is the part of MeshDev these kernels use, passed by value in the kernarg segment so that no load
@@ -218,8 +209,6 @@ struct T2Const {
   T2Class cls[2];
 };
 T2Const tile2d_const(const MeshDev& md_host);
-bool tile2d_supported(int dim, int P);
-bool tile2d_supported_quad(int P);   // quadrilateral cells (StageArgs::tensor): DQ_1..4
 int launch_stage_tile2d(int kind, int P, const StageArgs& a, const T2Const& c, long nitems, void* stream);
 
 // host layout [cell][node][comp] <-> device layout (MeshDev::gw) for `ncells` cells from `cell0`

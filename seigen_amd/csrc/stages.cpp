@@ -27,10 +27,9 @@ static double source_scale(const sg_handle* h) {
   return h->src.weights.empty() ? 1.0 : h->src.weights[(size_t)h->src_step];
 }
 
-static int run_op(sg_handle* h, int kind, int in_f, int out_f, int aux_f, int mode, double c_self, double c_aux,
-                  double c_new, int region, int uabs_f = SG_FIELD_U, bool with_source = false, bool density = false,
-                  double src_coef = 1.0) {
-  StageArgs a;
+// the arguments of a stage launch (kernels.hpp StageArgs) but for the region's boxes and items
+static int stage_args(sg_handle* h, StageArgs& a, int kind, int in_f, int out_f, int aux_f, int mode, double c_self, double c_aux,
+                      double c_new, int region, int uabs_f, bool with_source, bool density, double src_coef) {
   std::memset(&a, 0, sizeof(a));
   a.in = h->field[in_f].get();
   a.out = h->field[out_f].get();
@@ -59,42 +58,12 @@ static int run_op(sg_handle* h, int kind, int in_f, int out_f, int aux_f, int mo
   }
   a.sym = h->sym ? 1 : 0;
   a.f32 = h->f32;
-  SpongeTables& sp = h->sponge;
+  const SpongeTables& sp = h->sponge;
   a.dbg = h->dbg.get() ? h->dbg.get() + 8 * (kind * 2 + (mode ? 1 : 0)) : nullptr;
   a.sponge_slot = (kind == 0) ? sp.slot.get() : nullptr;
   a.sponge_B = sp.B.get();
   a.sponge_sigma = (kind == 0) ? sp.sigma.get() : nullptr;
   a.sponge_pre = (kind == 0) ? sp.pre.get() : nullptr;
-  // the first launch of an F stage - whichever region the caller starts with: the same stage again, or a region it has
-  // already seen, is the next instance of the stage
-  bool first_of_stage = false;
-  if (kind == 0 && sp.pre.get() && !h->name_out) {
-    const int key = out_f * 4 + mode;
-    first_of_stage = key != sp.pre_key || (sp.pre_regions & (1 << region)) != 0 || region == SG_REGION_ALL;
-    if (first_of_stage) sp.pre_regions = 0;
-    sp.pre_key = key;
-    sp.pre_regions |= 1 << region;
-  }
-  if (first_of_stage && sp.pre_field == uabs_f && sp.pre_ver == h->fver[uabs_f]) first_of_stage = false;   // the buffer holds it
-  if (first_of_stage) {
-    sp.pre_field = uabs_f;
-    sp.pre_ver = h->fver[uabs_f];
-    // B_e u_abs of the cells with a sponge matrix, before anything of the stage writes
-    if (launch_sponge_pre(a.uabs, sp.B.get(), sp.cells.get(), sp.mat.get(), sp.mat_slots.get(), sp.pre.get(), sp.nmat_slots, h->re.nd,
-                          h->cfg.dim, h->ncls, (int)h->md.gw, sp.pre_lines, h->f32, h->stream) != 0)
-      return fail(h, SG_ERR_DEVICE, "sponge pre-pass launch failed");
-    // ... and of the cells whose sigma is affine in the reference coordinates: dim + 1 numbers per cell, element-constant matrices
-    const int arc = sp.aff_frag.get()
-                        ? launch_sponge_affine_mfma(h->cfg.degree, a.uabs, sp.aff_frag.get(), sp.aff_items.get(), sp.aff_slots.get(),
-                                                    sp.aff_coef.get(), sp.pre.get(), sp.aff_nitems, sp.aff_grid, h->stream)
-                        : launch_sponge_pre_affine(a.uabs, sp.aff_X.get(), sp.aff_col.get(), sp.aff_W, sp.aff_items.get(),
-                                                   sp.aff_slots.get(), sp.aff_coef.get(), sp.pre.get(), sp.aff_nitems, h->re.nd,
-                                                   h->cfg.dim, (int)h->md.gw, sp.pre_lines, h->f32, sp.aff_grid, h->stream);
-    if (arc != 0) return fail(h, SG_ERR_DEVICE, "affine-sigma sponge pre-pass launch failed");
-    // SECOND runs on its own stream after ev_stage - "everything before this stage's FIRST" - and reads the pre-pass too
-    if (region == SG_REGION_FIRST && h->overlap && h->first_recorded_stage >= 0) HIPCHECK(h, hipEventRecord(h->ev_stage, h->stream));
-  }
-  if (!h->name_out) mark_field_written(h, out_f);     // (after the pre-pass decision: an in-place stage absorbs the state it overwrites)
   a.lam = h->lam_d.get();
   a.mu = h->mu_d.get();
   a.lam0 = h->lam0;
@@ -123,88 +92,144 @@ static int run_op(sg_handle* h, int kind, int in_f, int out_f, int aux_f, int mo
     a.src_vals = h->src.values.get() + (size_t)(source_one_slice(h) ? 0 : h->src_step) * h->src.nnz * h->cfg.dim * h->cfg.dim;
     a.src_scale = source_scale(h);
   }
+  return SG_OK;
+}
+
+// The sponge pre-pass of an F stage (SpongeTables::pre): B_e u_abs of the sponge cells, queued before anything of the stage
+// writes, at the first launch of the stage - whichever region the caller starts with: the same stage again, or a region it
+// has already seen, is the next instance of the stage - unless the buffer already holds it.  A naming pass changes nothing.
+static int sponge_pre_pass(sg_handle* h, int kind, int out_f, int mode, int region, int uabs_f) {
+  SpongeTables& sp = h->sponge;
+  if (kind != 0 || !sp.pre.get() || h->name_out) return SG_OK;
+  const int key = out_f * 4 + mode;
+  bool first_of_stage = key != sp.pre_key || (sp.pre_regions & (1 << region)) != 0 || region == SG_REGION_ALL;
+  if (first_of_stage) sp.pre_regions = 0;
+  sp.pre_key = key;
+  sp.pre_regions |= 1 << region;
+  if (!first_of_stage || (sp.pre_field == uabs_f && sp.pre_ver == h->fver[uabs_f])) return SG_OK;   // the buffer holds it
+  sp.pre_field = uabs_f;
+  sp.pre_ver = h->fver[uabs_f];
+  const void* uabs = h->field[uabs_f].get();
+  // the cells with a sponge matrix
+  if (launch_sponge_pre(uabs, sp.B.get(), sp.cells.get(), sp.mat.get(), sp.mat_slots.get(), sp.pre.get(), sp.nmat_slots, h->re.nd,
+                        h->cfg.dim, h->ncls, (int)h->md.gw, sp.pre_lines, h->f32, h->stream) != 0)
+    return fail(h, SG_ERR_DEVICE, "sponge pre-pass launch failed");
+  // ... and the cells whose sigma is affine in the reference coordinates: dim + 1 numbers per cell, element-constant matrices
+  const int arc = sp.aff_frag.get()
+                      ? launch_sponge_affine_mfma(h->cfg.degree, uabs, sp.aff_frag.get(), sp.aff_items.get(), sp.aff_slots.get(),
+                                                  sp.aff_coef.get(), sp.pre.get(), sp.aff_nitems, sp.aff_grid, h->stream)
+                      : launch_sponge_pre_affine(uabs, sp.aff_X.get(), sp.aff_col.get(), sp.aff_W, sp.aff_items.get(),
+                                                 sp.aff_slots.get(), sp.aff_coef.get(), sp.pre.get(), sp.aff_nitems, h->re.nd,
+                                                 h->cfg.dim, (int)h->md.gw, sp.pre_lines, h->f32, sp.aff_grid, h->stream);
+  if (arc != 0) return fail(h, SG_ERR_DEVICE, "affine-sigma sponge pre-pass launch failed");
+  // SECOND runs on its own stream after ev_stage - "everything before this stage's FIRST" - and reads the pre-pass too
+  if (region == SG_REGION_FIRST && h->overlap && h->first_recorded_stage >= 0) HIPCHECK(h, hipEventRecord(h->ev_stage, h->stream));
+  return SG_OK;
+}
+
+// The (cell group, class) items with an active cube of a region of a split stage, listed once per region (both regions
+// are static).  The interior launch then splits ACTIVE items evenly over the XCDs (a shell is whole z-layers of groups,
+// i.e. the first items of XCD 0 and the last of XCD 7: skipping them inside an even split of all items would leave the
+// launch as long as before); the shell launch deals its few items round-robin over all waves.
+static int region_items(sg_handle* h, int region, const StageArgs& a) {
+  if (h->region_nitems[region] >= 0) return SG_OK;
+  const int64_t gw = h->md.gw, ngroups = h->md.ncube_pad / gw;
+  std::vector<char> hit((size_t)ngroups, 0);
+  std::vector<int32_t> cnt((size_t)ngroups, 0);
+  for (int bx = 0; bx < a.nbox; ++bx)
+    for (int ck = a.boxes_o[bx][2]; ck < a.boxes_o[bx][2] + a.boxes_n[bx][2]; ++ck)
+      for (int cj = a.boxes_o[bx][1]; cj < a.boxes_o[bx][1] + a.boxes_n[bx][1]; ++cj)
+        for (int ci = a.boxes_o[bx][0]; ci < a.boxes_o[bx][0] + a.boxes_n[bx][0]; ++ci) {
+          int64_t cube = ci + (int64_t)h->cfg.n[0] * (cj + (int64_t)h->cfg.n[1] * ck);
+          hit[(size_t)(cube / gw)] = 1;
+          cnt[(size_t)(cube / gw)] += 1;
+        }
+  // Whole groups only (always, on meshes whose rows are a multiple of the group width: a shell in x is one
+  // group thick): the kernels then skip the cube coordinates and the box tests, as in a whole-block launch.
+  // (The boxes of a region are disjoint, so the count of a group tells.)
+  bool whole = true;
+  for (int64_t g = 0; g < ngroups; ++g)
+    if (hit[(size_t)g] && cnt[(size_t)g] != std::min<int64_t>(gw, h->md.ncube - g * gw)) whole = false;
+  std::vector<int32_t> items;
+  for (int64_t g = 0; g < ngroups; ++g)
+    if (hit[(size_t)g])
+      for (int k = 0; k < h->ncls; ++k) items.push_back((int32_t)(g * h->ncls + k));
+  DevBuf<int32_t> list;
+  if (!items.empty()) HIPCHECK(h, list.upload(items.data(), items.size()));
+  h->region_items[region] = std::move(list);
+  h->region_nitems[region] = (int32_t)items.size();
+  h->region_whole[region] = whole;
+  return SG_OK;
+}
+
+// one launch of the family's stage kernel (a naming pass: its name, kernels.hpp SG_LAUNCH)
+static int launch_family(sg_handle* h, int kind, const StageArgs& a) {
+  const int P = h->cfg.degree;
+  const long ngroups = (long)(h->md.ncube_pad / h->md.gw);
+  int rc = 0;
+  switch (h->family) {
+    case Family::Generic: rc = launch_stage(kind, h->cfg.dim, P, a, h->stream); break;
+    case Family::Lane: rc = launch_stage_lane(kind, h->cfg.dim, P, a, ngroups * h->ncls, h->stream); break;
+    case Family::Mfma: rc = launch_stage_mfma(kind, P, a, h->stream); break;
+    case Family::Tile2d: rc = launch_stage_tile2d(kind, P, a, h->t2c, ngroups * h->ncls, h->stream); break;
+    case Family::Hexm: rc = launch_stage_hexm(kind, P, a, ngroups, h->stream); break;
+  }
+  return rc != 0 ? fail(h, SG_ERR_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString((hipError_t)rc)) : SG_OK;
+}
+
+// the launches of a region: one per box for the generic kernels; the other families scan all cell groups and mask lanes
+// by box in one launch
+static int launch_region(sg_handle* h, int kind, int region, StageArgs& a) {
   std::vector<Box> boxes;
   region_boxes(h, region, boxes);
-  if (h->use_mfma || h->use_lane || h->use_tile || h->use_hexm) {
-    // one launch for the whole region: the kernels scan all cell groups and mask lanes by box
-    a.nbox = 0;
+  if (!family_interleaved(h->family)) {
     for (const Box& b : boxes) {
       if (b.n[0] <= 0 || b.n[1] <= 0 || b.n[2] <= 0) continue;
-      if (a.nbox >= SG_MAX_BOXES) return fail(h, SG_ERR_STATE, "region has more boxes than a launch can carry");
-      for (int k = 0; k < 3; ++k) {
-        a.boxes_o[a.nbox][k] = b.o[k];
-        a.boxes_n[a.nbox][k] = b.n[k];
-      }
-      a.nbox += 1;
+      std::memcpy(a.box_o, b.o, sizeof(a.box_o));
+      std::memcpy(a.box_n, b.n, sizeof(a.box_n));
+      if (int rc = launch_family(h, kind, a)) return rc;
     }
-    if (a.nbox == 0) return SG_OK;
-    a.spread = (region == SG_REGION_BOUNDARY) ? 1 : 0;
-    // only launches that run while an exchange is in flight leave block slots to RCCL
-    a.grid_blocks = (region == SG_REGION_INTERIOR || region == SG_REGION_SECOND) ? h->grid_blocks : h->grid_full;
-    // (the sponge is part of F only, and only cells with a matrix of their own make items differ in cost: then one item per
-    // wave on the prime-strided grid)
-    if (h->use_tile) a.grid_blocks = (sp.nslots > 0 && kind == 0) ? h->tile_grid_sponge : h->tile_grid;
-    a.item_list = nullptr;
-    a.nlist = 0;
-    a.order_chunk = (h->use_mfma && !a.spread && kind == 0) ? h->order_chunk : 0;
-    if (region != SG_REGION_ALL) {
-      // Both regions of a split stage are static: list the (cell group, class) items that have
-      // an active cube once.  The interior launch then splits ACTIVE items evenly over the XCDs
-      // (a shell is whole z-layers of groups, i.e. the first items of XCD 0 and the last of XCD 7:
-      // skipping them inside an even split of all items would leave the launch as long as before);
-      // the shell launch deals its few items round-robin over all waves.
-      if (h->region_nitems[region] < 0) {
-        const int64_t gw = h->md.gw, ngroups = h->md.ncube_pad / gw;
-        std::vector<char> hit((size_t)ngroups, 0);
-        std::vector<int32_t> cnt((size_t)ngroups, 0);
-        for (int bx = 0; bx < a.nbox; ++bx)
-          for (int ck = a.boxes_o[bx][2]; ck < a.boxes_o[bx][2] + a.boxes_n[bx][2]; ++ck)
-            for (int cj = a.boxes_o[bx][1]; cj < a.boxes_o[bx][1] + a.boxes_n[bx][1]; ++cj)
-              for (int ci = a.boxes_o[bx][0]; ci < a.boxes_o[bx][0] + a.boxes_n[bx][0]; ++ci) {
-                int64_t cube = ci + (int64_t)h->cfg.n[0] * (cj + (int64_t)h->cfg.n[1] * ck);
-                hit[(size_t)(cube / gw)] = 1;
-                cnt[(size_t)(cube / gw)] += 1;
-              }
-        // Whole groups only (always, on meshes whose rows are a multiple of the group width: a shell in x is one
-        // group thick): the kernels then skip the cube coordinates and the box tests, as in a whole-block launch.
-        // (The boxes of a region are disjoint, so the count of a group tells.)
-        bool whole = true;
-        for (int64_t g = 0; g < ngroups; ++g)
-          if (hit[(size_t)g] && cnt[(size_t)g] != std::min<int64_t>(gw, h->md.ncube - g * gw)) whole = false;
-        std::vector<int32_t> items;
-        for (int64_t g = 0; g < ngroups; ++g)
-          if (hit[(size_t)g])
-            for (int k = 0; k < h->ncls; ++k) items.push_back((int32_t)(g * h->ncls + k));
-        DevBuf<int32_t> list;
-        if (!items.empty()) HIPCHECK(h, list.upload(items.data(), items.size()));
-        h->region_items[region] = std::move(list);
-        h->region_nitems[region] = (int32_t)items.size();
-        h->region_whole[region] = whole;
-      }
-      a.item_list = h->region_items[region].get();
-      a.nlist = h->region_nitems[region];
-      if ((h->use_mfma || h->use_hexm) && h->region_whole[region] && !h->no_whole) a.all_active = 1;
-    }
-    a.nitems = a.item_list ? a.nlist : (int32_t)std::min<int64_t>((h->md.ncube_pad / h->md.gw) * h->ncls, INT32_MAX);
-    int rc = h->use_mfma   ? launch_stage_mfma(kind, h->cfg.degree, a, h->stream)
-             : h->use_hexm ? launch_stage_hexm(kind, h->cfg.degree, a, (long)(h->md.ncube_pad / 16), h->stream)
-             : h->use_tile ? launch_stage_tile2d(kind, h->cfg.degree, a, h->t2c, (long)(h->md.ncube_pad / 16) * h->ncls, h->stream)
-                           : launch_stage_lane(kind, h->cfg.dim, h->cfg.degree, a, (long)(h->md.ncube_pad / 64) * h->ncls, h->stream);
-    if (rc != 0) return fail(h, SG_ERR_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString((hipError_t)rc));
     return SG_OK;
   }
+  a.nbox = 0;
   for (const Box& b : boxes) {
-    bool empty = false;
+    if (b.n[0] <= 0 || b.n[1] <= 0 || b.n[2] <= 0) continue;
+    if (a.nbox >= SG_MAX_BOXES) return fail(h, SG_ERR_STATE, "region has more boxes than a launch can carry");
     for (int k = 0; k < 3; ++k) {
-      a.box_o[k] = b.o[k];
-      a.box_n[k] = b.n[k];
-      empty = empty || (b.n[k] <= 0);
+      a.boxes_o[a.nbox][k] = b.o[k];
+      a.boxes_n[a.nbox][k] = b.n[k];
     }
-    if (empty) continue;
-    int rc = launch_stage(kind, h->cfg.dim, h->cfg.degree, a, h->stream);
-    if (rc != 0) return fail(h, SG_ERR_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString((hipError_t)rc));
+    a.nbox += 1;
   }
-  return SG_OK;
+  if (a.nbox == 0) return SG_OK;
+  a.spread = (region == SG_REGION_BOUNDARY) ? 1 : 0;
+  // only launches that run while an exchange is in flight leave block slots to RCCL
+  a.grid_blocks = (region == SG_REGION_INTERIOR || region == SG_REGION_SECOND) ? h->grid_blocks : h->grid_full;
+  // (the sponge is part of F only, and only cells with a matrix of their own make items differ in cost: then one item per
+  // wave on the prime-strided grid)
+  if (h->family == Family::Tile2d) a.grid_blocks = (h->sponge.nslots > 0 && kind == 0) ? h->tile_grid_sponge : h->tile_grid;
+  a.item_list = nullptr;
+  a.nlist = 0;
+  a.order_chunk = (h->family == Family::Mfma && !a.spread && kind == 0) ? h->order_chunk : 0;
+  if (region != SG_REGION_ALL) {
+    if (int rc = region_items(h, region, a)) return rc;
+    a.item_list = h->region_items[region].get();
+    a.nlist = h->region_nitems[region];
+    if (family_whole_groups(h->family) && h->region_whole[region] && !h->no_whole) a.all_active = 1;
+  }
+  a.nitems = a.item_list ? a.nlist : (int32_t)std::min<int64_t>((h->md.ncube_pad / h->md.gw) * h->ncls, INT32_MAX);
+  return launch_family(h, kind, a);
+}
+
+static int run_op(sg_handle* h, int kind, int in_f, int out_f, int aux_f, int mode, double c_self, double c_aux,
+                  double c_new, int region, int uabs_f = SG_FIELD_U, bool with_source = false, bool density = false,
+                  double src_coef = 1.0) {
+  StageArgs a;
+  if (int rc = stage_args(h, a, kind, in_f, out_f, aux_f, mode, c_self, c_aux, c_new, region, uabs_f, with_source, density, src_coef))
+    return rc;
+  if (int rc = sponge_pre_pass(h, kind, out_f, mode, region, uabs_f)) return rc;
+  if (!h->name_out) mark_field_written(h, out_f);     // (after the pre-pass decision: an in-place stage absorbs the state it overwrites)
+  return launch_region(h, kind, region, a);
 }
 
 // the source lives on single nodes: added to each part of a split stage right after the launch
@@ -295,6 +320,31 @@ int resolve_timing(sg_handle* h) {
   return SG_OK;
 }
 
+// Per-launch timing (sg_enable_timing): an event pair around a stage launch or a halo pack on stream s, resolved lazily by
+// resolve_timing (8192 pending pairs at once, on the main stream); id as in sg_handle::ev_stage_ids.
+static int timing_begin(sg_handle* h, hipStream_t s, size_t& k) {
+  k = h->ev_stage_ids.size();
+  if (!h->timing) return SG_OK;
+  if (k >= 8192) {
+    if (int rc = resolve_timing(h)) return rc;
+    k = 0;
+  }
+  while (h->ev_pool.size() < 2 * k + 2) {
+    hipEvent_t e;
+    HIPCHECK(h, hipEventCreate(&e));
+    h->ev_pool.push_back(e);
+  }
+  HIPCHECK(h, hipEventRecord(h->ev_pool[2 * k], s));
+  return SG_OK;
+}
+
+static int timing_end(sg_handle* h, hipStream_t s, size_t k, int id) {
+  if (!h->timing) return SG_OK;
+  HIPCHECK(h, hipEventRecord(h->ev_pool[2 * k + 1], s));
+  h->ev_stage_ids.push_back(id);
+  return SG_OK;
+}
+
 extern "C" {
 
 int sg_run_stage(sg_handle* h, int stage, int region) {
@@ -304,7 +354,6 @@ int sg_run_stage(sg_handle* h, int stage, int region) {
   if (stage < 0 || stage > 5) return fail(h, SG_ERR_ARG, "unknown stage");
   HIPCHECK(h, hipSetDevice(h->cfg.device));
   const bool second = h->overlap && region == SG_REGION_SECOND;
-  hipStream_t const main_stream = h->stream;
   if (second) {
     // depends on everything before this stage's FIRST (ev_stage), not on FIRST itself - so FIRST of the SAME stage
     // must have been issued (it records ev_stage); anything else would wait on a stale event and race
@@ -312,7 +361,6 @@ int sg_run_stage(sg_handle* h, int stage, int region) {
       return fail(h, SG_ERR_STATE, "sg_run_stage(stage, SG_REGION_SECOND) must follow sg_run_stage(stage, SG_REGION_FIRST) of the same stage");
     h->first_recorded_stage = -1;
     HIPCHECK(h, hipStreamWaitEvent(h->stream2, h->ev_stage, 0));
-    h->stream = h->stream2;
   } else {
     if (int rc = join_second(h)) return rc;
     if (h->overlap && region == SG_REGION_FIRST) {
@@ -320,33 +368,18 @@ int sg_run_stage(sg_handle* h, int stage, int region) {
       h->first_recorded_stage = stage;
     }
   }
-  size_t k = h->ev_stage_ids.size();
-  int rc = SG_OK;
-  if (h->timing) {
-    if (k >= 8192) {
-      h->stream = main_stream;
-      rc = resolve_timing(h);
-      if (rc != SG_OK) return rc;
-      if (second) h->stream = h->stream2;
-      k = 0;
-    }
-    while (rc == SG_OK && h->ev_pool.size() < 2 * k + 2) {
-      hipEvent_t e;
-      if (hipEventCreate(&e) != hipSuccess) rc = fail(h, SG_ERR_DEVICE, "hipEventCreate failed");
-      else h->ev_pool.push_back(e);
-    }
-    if (rc == SG_OK && hipEventRecord(h->ev_pool[2 * k], h->stream) != hipSuccess) rc = fail(h, SG_ERR_DEVICE, "hipEventRecord failed");
-  }
-  if (rc == SG_OK) rc = run_stage_impl(h, stage, region);
-  if (rc == SG_OK && h->timing) {
-    if (hipEventRecord(h->ev_pool[2 * k + 1], h->stream) != hipSuccess) rc = fail(h, SG_ERR_DEVICE, "hipEventRecord failed");
-    else h->ev_stage_ids.push_back(stage + ((h->overlap && region == SG_REGION_FIRST) ? 16 : (second ? 32 : 0)));
-  }
+  hipStream_t const main_stream = h->stream, s = second ? h->stream2 : h->stream;
+  size_t k = 0;
+  int rc = timing_begin(h, s, k);     // (a flush of the pending pairs resolves them on the main stream: h->stream is still that)
+  if (rc != SG_OK) return rc;
+  h->stream = s;
+  rc = run_stage_impl(h, stage, region);
+  if (rc == SG_OK) rc = timing_end(h, s, k, stage + ((h->overlap && region == SG_REGION_FIRST) ? 16 : (second ? 32 : 0)));
   if (second) {
     if (rc == SG_OK && hipEventRecord(h->ev_second, h->stream2) != hipSuccess) rc = fail(h, SG_ERR_DEVICE, "hipEventRecord failed");
     h->second_pending = rc == SG_OK;
-    h->stream = main_stream;
   }
+  h->stream = main_stream;
   if (rc != SG_OK) return rc;
   h->counters.launches[stage] += 1;
   return SG_OK;
@@ -502,49 +535,11 @@ int sg_halo_bytes(const sg_handle* h, int field, int side, size_t* nbytes) {
   return SG_OK;
 }
 
-// pack launches are timed like stage launches (event pairs resolved lazily; stage id 6 = halo pack)
-static int pack_begin(sg_handle* h, size_t& k) {
-  if (int rc = join_second(h)) return rc;
-  k = h->ev_stage_ids.size();
-  if (!h->timing) return SG_OK;
-  if (k >= 8192) {
-    int rc = resolve_timing(h);
-    if (rc != SG_OK) return rc;
-    k = 0;
-  }
-  while (h->ev_pool.size() < 2 * k + 2) {
-    hipEvent_t e;
-    HIPCHECK(h, hipEventCreate(&e));
-    h->ev_pool.push_back(e);
-  }
-  HIPCHECK(h, hipEventRecord(h->ev_pool[2 * k], h->stream));
-  return SG_OK;
-}
-
-static int pack_end(sg_handle* h, size_t k, size_t nbytes) {
-  if (h->timing) {
-    HIPCHECK(h, hipEventRecord(h->ev_pool[2 * k + 1], h->stream));
-    h->ev_stage_ids.push_back(6);
-  }
-  h->counters.halo_pack_launches += 1;
-  h->counters.halo_bytes_packed += (int64_t)nbytes;
-  return SG_OK;
-}
-
 int sg_halo_pack(sg_handle* h, int field, int side, void* dev_out) {
   if (!h || !dev_out || field < 0 || field > 3 || side < 0 || side >= 2 * h->cfg.dim) return SG_ERR_ARG;
-  HIPCHECK(h, hipSetDevice(h->cfg.device));
-  const int d = h->cfg.dim;
-  int comps = field_is_stress(field) ? d * d : d;
-  void* out = dev_out;
-  size_t k = 0, nb = 0;
-  int rc = pack_begin(h, k);
-  if (rc != SG_OK) return rc;
-  rc = launch_pack(h->md_dev.get(), h->md, h->field[field].get(), comps, 1, &side, &out,
-                   (h->sym && field_is_stress(field)) ? 1 : 0, h->f32, h->stream);
-  if (rc != 0) return fail(h, SG_ERR_DEVICE, "pack kernel launch failed");
-  (void)sg_halo_bytes(h, field, side, &nb);
-  return pack_end(h, k, nb);
+  void* outs[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  outs[side] = dev_out;
+  return sg_halo_pack_sides(h, field, outs);
 }
 
 int sg_halo_pack_sides(sg_handle* h, int field, void* const* dev_out) {
@@ -560,8 +555,9 @@ int sg_halo_pack_sides(sg_handle* h, int field, void* const* dev_out) {
       outs[n] = dev_out[s];
       n += 1;
     }
+  if (int rc = join_second(h)) return rc;
   size_t k = 0, total = 0;
-  int rc = pack_begin(h, k);
+  int rc = timing_begin(h, h->stream, k);     // pack launches are timed like stage launches (stage id 6)
   if (rc != SG_OK) return rc;
   rc = launch_pack(h->md_dev.get(), h->md, h->field[field].get(), comps, n, sides, outs,
                    (h->sym && field_is_stress(field)) ? 1 : 0, h->f32, h->stream);
@@ -571,7 +567,10 @@ int sg_halo_pack_sides(sg_handle* h, int field, void* const* dev_out) {
     (void)sg_halo_bytes(h, field, sides[i], &nb);
     total += nb;
   }
-  return pack_end(h, k, total);
+  if (int rc = timing_end(h, h->stream, k, 6)) return rc;
+  h->counters.halo_pack_launches += 1;
+  h->counters.halo_bytes_packed += (int64_t)total;
+  return SG_OK;
 }
 
 // ---- instrumentation ----------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 """Generic (thread-per-node, table-driven) against lane (sum-factorised, lane-per-cell) kernels on small hexahedral blocks:
-where SG_HEX_LANE_MIN_CELLS (csrc/kernels.hpp) should sit."""
+where SG_HEX_LANE_MIN_CELLS (csrc/hostlogic.hpp) should sit."""
 import os
 import sys
 import time

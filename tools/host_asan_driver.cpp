@@ -136,7 +136,6 @@ static void regions_and_coords() {
           cfg.diagonal = diagonal;
           cfg.nbr_mask = mask;
           cfg.cube0[0] = 3;
-          (void)choose_kernel_path(cfg);
           for (int region = 0; region <= 4; ++region) {
             int32_t boxes[SG_MAX_REGION_BOXES * 6];
             const int nb = sg_region_boxes(&cfg, region, boxes, SG_MAX_REGION_BOXES);
@@ -158,6 +157,121 @@ static void regions_and_coords() {
         }
     }
   EXPECT(sg_region_boxes(nullptr, 0, nullptr, 0) == SG_ERR_ARG);
+}
+
+// Which kernel family runs a block (hostapi.cpp choose_kernel_path), pinned row by row: one row on each side of every size
+// threshold, and every SEIGEN_HIP_PATH value - unset, the four names, an unknown string - for each dimension and cell type.
+// (The lane thresholds only decide in 1-D: 2-D simplices take the tile kernels and 3-D ones the MFMA kernels first.)
+static void kernel_family_table() {
+  using F = Family;
+  const int64_t hx = SG_HEX_LANE_MIN_CELLS(1), hx2 = SG_HEX_LANE_MIN_CELLS(2);
+  struct Row {
+    const char* path;   // SEIGEN_HIP_PATH, nullptr = unset
+    int dim, diagonal, degree;
+    int64_t n0, n1, n2;
+    Family family;
+    int gw;
+  };
+  const int Q = SG_DIAGONAL_QUAD;
+  const Row rows[] = {
+      // unset: the measured thresholds
+      {nullptr, 1, 0, 1, 196607, 1, 1, F::Generic, 1},
+      {nullptr, 1, 0, 1, 196608, 1, 1, F::Lane, 64},
+      {nullptr, 1, 0, 2, 119999, 1, 1, F::Generic, 1},
+      {nullptr, 1, 0, 2, 120000, 1, 1, F::Lane, 64},
+      {nullptr, 1, 0, 4, 119999, 1, 1, F::Generic, 1},
+      {nullptr, 1, 0, 4, 120000, 1, 1, F::Lane, 64},
+      {nullptr, 2, 0, 1, 2, 2, 1, F::Tile2d, 16},
+      {nullptr, 2, 1, 4, 512, 512, 1, F::Tile2d, 16},
+      {nullptr, 3, 0, 1, 1, 1, 10922, F::Generic, 1},      // 65532 cells
+      {nullptr, 3, 1, 1, 1, 1, 10923, F::Mfma, 16},        // 65538 cells
+      {nullptr, 3, 0, 2, 2, 2, 2, F::Mfma, 16},
+      {nullptr, 3, 0, 4, 2, 2, 2, F::Mfma, 16},
+      {nullptr, 2, Q, 1, 2, 2, 1, F::Tile2d, 16},
+      {nullptr, 2, Q, 4, 512, 512, 1, F::Tile2d, 16},
+      {nullptr, 3, Q, 1, hx - 1, 1, 1, F::Generic, 1},
+      {nullptr, 3, Q, 1, hx, 1, 1, F::Lane, 64},
+      {nullptr, 3, Q, 2, hx2 - 1, 1, 1, F::Generic, 1},
+      {nullptr, 3, Q, 2, hx2, 1, 1, F::Lane, 64},
+      {nullptr, 3, Q, 3, 2, 2, 2, F::Hexm, 16},
+      {nullptr, 3, Q, 4, 2, 2, 2, F::Hexm, 16},
+      // generic: everywhere
+      {"generic", 1, 0, 1, 196608, 1, 1, F::Generic, 1},
+      {"generic", 2, 0, 2, 512, 512, 1, F::Generic, 1},
+      {"generic", 3, 0, 1, 1, 1, 10923, F::Generic, 1},
+      {"generic", 3, 0, 4, 2, 2, 2, F::Generic, 1},
+      {"generic", 2, Q, 2, 512, 512, 1, F::Generic, 1},
+      {"generic", 3, Q, 1, hx, 1, 1, F::Generic, 1},
+      {"generic", 3, Q, 4, 2, 2, 2, F::Generic, 1},
+      // lane: wherever lane kernels exist; not 3-D simplices P3 / P4 (generic), not 2-D quadrilaterals (tile), not DQ_3 / DQ_4
+      {"lane", 1, 0, 1, 8, 1, 1, F::Lane, 64},
+      {"lane", 1, 0, 4, 8, 1, 1, F::Lane, 64},
+      {"lane", 2, 0, 1, 2, 2, 1, F::Lane, 64},
+      {"lane", 2, 0, 4, 512, 512, 1, F::Lane, 64},
+      {"lane", 3, 0, 1, 1, 1, 10923, F::Lane, 64},
+      {"lane", 3, 0, 2, 2, 2, 2, F::Lane, 64},
+      {"lane", 3, 0, 3, 2, 2, 2, F::Generic, 1},
+      {"lane", 3, 0, 4, 2, 2, 2, F::Generic, 1},
+      {"lane", 2, Q, 2, 2, 2, 1, F::Tile2d, 16},
+      {"lane", 3, Q, 1, 2, 2, 2, F::Lane, 64},
+      {"lane", 3, Q, 2, 2, 2, 2, F::Lane, 64},
+      {"lane", 3, Q, 3, 2, 2, 2, F::Hexm, 16},
+      // mfma: 3-D P1 simplices below the threshold; elsewhere as unset
+      {"mfma", 1, 0, 1, 8, 1, 1, F::Generic, 1},
+      {"mfma", 1, 0, 1, 196608, 1, 1, F::Lane, 64},
+      {"mfma", 2, 0, 3, 2, 2, 1, F::Tile2d, 16},
+      {"mfma", 3, 0, 1, 2, 2, 2, F::Mfma, 16},
+      {"mfma", 3, 0, 1, 1, 1, 10923, F::Mfma, 16},
+      {"mfma", 2, Q, 3, 2, 2, 1, F::Tile2d, 16},
+      {"mfma", 3, Q, 1, hx - 1, 1, 1, F::Generic, 1},
+      {"mfma", 3, Q, 1, hx, 1, 1, F::Lane, 64},
+      {"mfma", 3, Q, 3, 2, 2, 2, F::Hexm, 16},
+      // tile: as unset (the tile kernels are the default wherever they exist; ignored in 1-D and 3-D)
+      {"tile", 1, 0, 1, 8, 1, 1, F::Generic, 1},
+      {"tile", 1, 0, 1, 196608, 1, 1, F::Lane, 64},
+      {"tile", 2, 0, 1, 2, 2, 1, F::Tile2d, 16},
+      {"tile", 3, 0, 1, 2, 2, 2, F::Generic, 1},
+      {"tile", 3, 0, 1, 1, 1, 10923, F::Mfma, 16},
+      {"tile", 2, Q, 1, 2, 2, 1, F::Tile2d, 16},
+      {"tile", 3, Q, 1, 2, 2, 2, F::Generic, 1},
+      {"tile", 3, Q, 1, hx, 1, 1, F::Lane, 64},
+      {"tile", 3, Q, 4, 2, 2, 2, F::Hexm, 16},
+      // an unknown string (or an empty one): as unset
+      {"bogus", 1, 0, 1, 196607, 1, 1, F::Generic, 1},
+      {"bogus", 1, 0, 1, 196608, 1, 1, F::Lane, 64},
+      {"bogus", 2, 0, 2, 2, 2, 1, F::Tile2d, 16},
+      {"bogus", 3, 0, 1, 2, 2, 2, F::Generic, 1},
+      {"bogus", 3, 0, 1, 1, 1, 10923, F::Mfma, 16},
+      {"bogus", 3, 0, 3, 2, 2, 2, F::Mfma, 16},
+      {"bogus", 2, Q, 2, 2, 2, 1, F::Tile2d, 16},
+      {"bogus", 3, Q, 1, hx - 1, 1, 1, F::Generic, 1},
+      {"bogus", 3, Q, 2, hx2, 1, 1, F::Lane, 64},
+      {"bogus", 3, Q, 3, 2, 2, 2, F::Hexm, 16},
+      {"", 3, 0, 1, 2, 2, 2, F::Generic, 1},
+      {"", 2, 0, 1, 2, 2, 1, F::Tile2d, 16},
+  };
+  for (const Row& r : rows) {
+    sg_config cfg;
+    std::memset(&cfg, 0, sizeof(cfg));
+    cfg.dim = r.dim;
+    cfg.diagonal = r.diagonal;
+    cfg.degree = r.degree;
+    cfg.n[0] = (int32_t)r.n0;
+    cfg.n[1] = (int32_t)r.n1;
+    cfg.n[2] = (int32_t)r.n2;
+    for (int a = 0; a < 3; ++a) cfg.h[a] = 1.0;
+    if (r.path) setenv("SEIGEN_HIP_PATH", r.path, 1);
+    else unsetenv("SEIGEN_HIP_PATH");
+    const Family f = choose_kernel_path(cfg);
+    const int gw = family_gw(f);
+    if (f != r.family || gw != r.gw) {
+      std::fprintf(stderr, "FAIL kernel family: SEIGEN_HIP_PATH=%s dim %d diagonal %d degree %d n %lld x %lld x %lld: family %d gw %d, want %d gw %d\n",
+                   r.path ? r.path : "(unset)", r.dim, r.diagonal, r.degree, (long long)r.n0, (long long)r.n1, (long long)r.n2, (int)f, gw,
+                   (int)r.family, r.gw);
+      nfail += 1;
+    }
+  }
+  unsetenv("SEIGEN_HIP_PATH");
 }
 
 // sg_set_absorption's host half (csrc/sponge_tables.cpp): every kind of cell - none, constant, affine, general - side by side on
@@ -273,6 +387,7 @@ int main() {
     tile_tables_2d(degree, KIND_TENSOR);
   }
   regions_and_coords();
+  kernel_family_table();
   for (int dim = 1; dim <= 3; ++dim)
     for (int degree : {1, 2, 4})
       for (int kind : {KIND_SIMPLEX, KIND_TENSOR}) {

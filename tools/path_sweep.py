@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Lane-per-cell vs generic stage kernels over block sizes (2-D and 3-D low order): ms per LF4 step.
-Chooses the size threshold in api.cpp (use_lane)."""
+Chooses the lane kernels' size thresholds (csrc/hostapi.cpp choose_kernel_path)."""
 import os
 import sys
 import time

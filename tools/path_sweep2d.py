@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """2-D kernel families over block sizes: ms per LF4 step (device time, best of 3 x `steps`) for the generic,
-lane-per-cell and MFMA tile kernels.  Chooses SG_TILE2D_MIN_CELLS in api.cpp.
+lane-per-cell and MFMA tile kernels: the measurements behind the 2-D family choice (csrc/hostapi.cpp choose_kernel_path).
 usage: path_sweep2d.py [--paths generic,lane,tile] [--degrees 1,2,3,4] [--sizes 40x40,128x128,...]"""
 import argparse
 import os
