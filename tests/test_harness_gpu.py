@@ -213,7 +213,11 @@ class _LocalExchange(object):
                 b.end_step()
 
 
-def _multiblock_case(dim, degree, n, grid, pipelined, extras=False, dtype="f64", separable=False, diagonal="left"):
+def _multiblock_case(dim, degree, n, grid, pipelined, extras=False, dtype="f64", separable=False, diagonal="left",
+                     sym=False):
+    """Steps the mesh as one block and as the blocks of `grid` and asserts the two agree bitwise.  sym: a symmetric
+    initial stress (the blocks stay in symmetric-stress mode).  Returns the single block's inputs and results (u0, s0,
+    dt, sigma, src_nodes, src_steps - the source values of each step -, u, s) and the stage kernels the split blocks name."""
     torch = pytest.importorskip("torch")
     if not torch.cuda.is_available():
         pytest.skip("torch sees no GPU")
@@ -225,11 +229,14 @@ def _multiblock_case(dim, degree, n, grid, pipelined, extras=False, dtype="f64",
     single = HipBlock(dim, degree, n, h, [0.0] * dim, diagonal, dtype=dtype)
     u0 = seeded(single.field_shape(_lib.FIELD_U), 11)
     s0 = seeded(single.field_shape(_lib.FIELD_S), 12)
+    if sym:
+        s0 = 0.5 * (s0 + np.swapaxes(s0, -1, -2))
     dt = 0.02 * min(h) / degree ** 2
     single.set_params(1.0, dt, 0.5, 0.25)
     single.set_field(_lib.FIELD_U, u0)
     single.set_field(_lib.FIELD_S, s0)
     nd = single.nd
+    sigma = src_nodes = src_steps = None
     if extras:      # a sponge and a time-dependent source scattered over the mesh (shell cells included)
         r3 = np.random.default_rng(77)
         nq = 5 ** dim if diagonal == "quadrilateral" else {1: 5, 2: 15, 3: 35}[dim]
@@ -242,8 +249,10 @@ def _multiblock_case(dim, degree, n, grid, pipelined, extras=False, dtype="f64",
         single.set_absorption(sigma, 4)
         if separable:       # one slice and a weight per step (sg_set_source_separable)
             single.set_source_separable(src_nodes, src_vals[0], src_w)
+            src_steps = src_w[:, None, None, None] * src_vals[0]
         else:
             single.set_source(src_nodes, src_vals)
+            src_steps = src_vals
     single.step(3)
     uref, sref = single.get_field(_lib.FIELD_U), single.get_field(_lib.FIELD_S)
 
@@ -281,11 +290,13 @@ def _multiblock_case(dim, degree, n, grid, pipelined, extras=False, dtype="f64",
                 b.set_source(mynodes, src_vals[:, mine] if mine else None)
         blocks.append(b)
     ex = _LocalExchange(blocks, parts)
+    names = sorted({b.stage_kernel_name(st) for b in blocks for st in range(6)})     # halo buffers attached: as they run
     ex.step(3, pipelined)
     for b, p in zip(blocks, parts):
         sel = cells_of(p)
         assert np.array_equal(b.get_field(_lib.FIELD_U), uref[sel]), "velocity differs from the single-block run"
         assert np.array_equal(b.get_field(_lib.FIELD_S), sref[sel]), "stress differs from the single-block run"
+    return dict(u0=u0, s0=s0, dt=dt, sigma=sigma, src_nodes=src_nodes, src_steps=src_steps, u=uref, s=sref, names=names)
 
 
 @pytest.mark.parametrize("dim,degree,n,grid", [

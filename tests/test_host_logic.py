@@ -35,6 +35,21 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(L, name), "libseigen_hip.so does not export %s" % name
 
 
+def test_mfma_family_instantiations_are_the_listed_ones():
+    """The kernel objects of the 3-D matrix-pipe family in the built library are exactly MFMA_KERNELS, the list
+    tests/test_mfma_family_gpu.py checks row by row against the oracle: no instantiation joins or leaves unseen."""
+    import subprocess
+    from tests.test_mfma_family_gpu import MFMA_KERNELS
+    readelf = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin", "llvm-readelf")
+    assert os.path.exists(readelf), "llvm-readelf (shipped with ROCm) not found at %s: set ROCM_PATH" % readelf
+    out = subprocess.run([readelf, "--dyn-syms", "--demangle", _lib.lib_path()], capture_output=True, text=True, check=True).stdout
+    pat = re.compile(r"\bOBJECT\b.*?\b(sg::(?:mfma_stage_[FG]|sponge_affine_mfma)<[^>]*>)\(")
+    found = {m.group(1) for m in map(pat.search, out.splitlines()) if m}
+    assert not MFMA_KERNELS - found, "listed but not in the library: %s" % sorted(MFMA_KERNELS - found)
+    assert not found - MFMA_KERNELS, "in the library but not listed in MFMA_KERNELS: %s" % sorted(found - MFMA_KERNELS)
+    assert len(found) == 140
+
+
 def test_create_fails_loudly_without_device_or_bad_args():
     L = lib()
     cfg = _lib.SgConfig()

@@ -378,6 +378,7 @@ def test_3d_sponge_constant_and_matrix_cells(gpu, monkeypatch, degree, n, diagon
 @pytest.mark.parametrize("degree,n,diagonal,path", [
     (4, (17, 3, 2), "left", ""), (3, (6, 3, 4), "left", ""), (2, (5, 3, 4), "left", "lane"), (1, (9, 2, 3), "left", "lane"),
     (3, (5, 3, 2), "quadrilateral", ""), (4, (3, 2, 2), "quadrilateral", ""), (2, (5, 3, 2), "quadrilateral", "lane"),
+    (1, (17, 3, 2), "left", "mfma"), (2, (18, 3, 2), "left", "mfma"),          # the matrix-pipe form, sponge_affine_mfma<1>, <2>
 ])
 @pytest.mark.parametrize("sigma_degree", [4, 1])
 def test_3d_affine_sigma_ramp(gpu, monkeypatch, degree, n, diagonal, path, sigma_degree):
@@ -400,6 +401,8 @@ def test_3d_affine_sigma_ramp(gpu, monkeypatch, degree, n, diagonal, path, sigma
     for affine in ("1", "0"):
         monkeypatch.setenv("SEIGEN_HIP_SPONGE_AFFINE", affine)
         blk = HipBlock(3, degree, n, h, [0.0] * 3, diagonal)
+        if path == "mfma":
+            assert blk.stage_kernel_name(_lib.STAGE_UH1).startswith("sg::mfma_stage_F<double,")
         u0 = seeded(blk.field_shape(_lib.FIELD_U), 71)
         s0 = seeded(blk.field_shape(_lib.FIELD_S), 72)
         s0 = 0.5 * (s0 + np.swapaxes(s0, -1, -2))
