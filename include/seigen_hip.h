@@ -230,6 +230,30 @@ int sg_run_stage(sg_handle* h, int stage, int region);
 /* advance the source-amplitude index after a manually staged step */
 int sg_end_step(sg_handle* h);
 
+/* ---- receivers (tests/explosive_source/uy.py:31-43: VelocityNew written to a VTU file at every step, three points
+ * probed in every 5th file with vtktools.vtu.ProbeData) ------------------------------------------------------------
+ * A receiver is a physical point; its samples are taken on the device inside the time loop.  A step is a completed LF4
+ * step counted from the arming call - through sg_step (graph replay or eager, with or without a communicator) or through
+ * sg_end_step after host-driven stages.  Sample j (0-based) is taken after step (j+1)*every.  Per receiver a sample holds
+ * the velocity u1 (what bit 0: dim values) and then the stress s1 (bit 1: dim x dim, row-major; in symmetric-stress
+ * storage the i > j entries are their mirrors), each value sum_a phi_a(xi) field[cell][a][c] over the nodes a in
+ * ascending order, in double with fma (FP32 blocks convert every nodal value first): bitwise the same under graph replay
+ * and eager launches, for one sg_step(n) and n calls of sg_step(1), for host-driven stages, and on a split block.
+ * The cell and xi of a point: sg_locate_points.  A block owns a receiver when the chosen cube (in the mesh's indices)
+ * lies in it: under any partition every point inside the mesh has exactly one owner, a point outside none.
+ * Arm: nrec points [nrec][dim] (all of the mesh's receivers: each block keeps the ones it owns), owned[nrec] out (0/1,
+ * may be NULL), what = bit 0 velocity | bit 1 stress, every >= 1, capacity = samples the device buffer holds.  nrec = 0
+ * disarms; re-arming discards the old samples; a failed call leaves the previous receivers recording, samples intact.
+ * sg_step(n) whose samples would exceed the capacity returns SG_ERR_STATE before it queues anything (fields, counters
+ * and trace untouched); sg_end_step of a step due a sample the trace has no room for returns SG_ERR_STATE and does not
+ * count the step.  No receivers armed: no extra launch, the same captured graphs. */
+int sg_set_receivers(sg_handle* h, int64_t nrec, const double* pts, int what, int64_t every, int64_t capacity,
+                     int32_t* owned);
+/* samples taken so far -> out[nsamples][nrec][ncomp] (ncomp = dim * bit0 + dim^2 * bit1), rows of receivers this block
+ * does not own are 0.0; nbytes must be that of `capacity` samples; *nsamples = samples taken.  Replaces the host-side
+ * probe of every 5th VTU file (uy.py:36-43, vtktools.vtu.ProbeData). */
+int sg_get_receivers(sg_handle* h, double* out, size_t nbytes, int64_t* nsamples);
+
 /* un-fused operators for stage-level parity tests:
  *   out = Minv f(w; s_in, u_abs)   (elastic.py:204-209 + :358-367)
  *   out = Minv g(v; u_in)          (elastic.py:211-219 + :358-367)
@@ -328,6 +352,15 @@ int sg_tabulate(int dim, int degree, int64_t npts, const double* xi, double* phi
  * the element of sg_config::diagonal = 2. */
 int64_t sg_reference_operator_cell(int cell_type, int dim, int degree, int which, int q, double* out, size_t nbytes);
 int sg_tabulate_cell(int cell_type, int dim, int degree, int64_t npts, const double* xi, double* phi);
+/* Point location (device-free; cfg->device / stream ignored, like sg_block_node_coords): cell[k] = the block-local cell
+ * owning pts[k][dim], or -1 (another block's, or outside the mesh); xi[k][dim] its reference coordinates (0 where -1).
+ * The rule (seigen_amd/functionspace.py locate, the stand-in for the point location behind vtktools.vtu.ProbeData that
+ * tests/explosive_source/uy.py:36-43 relies on): per axis t = (p - origin) / h; the cube floor(t) and, on a grid line
+ * (|t - round t| < 1e-9), also the one below it if its index in the MESH (cube0 + local) is >= 0; candidates in ascending
+ * order (z slowest), classes in ascending order; the first cell whose reference coordinates pass xi >= -1e-12 and
+ * sum xi <= 1 + 1e-12 (tensor-product cells: max xi) wins - on a grid line the lower cube, the lower side of a
+ * discontinuous field. */
+int sg_locate_points(const sg_config* cfg, int64_t npts, const double* pts, int64_t* cell, double* xi);
 /* The disjoint boxes of cubes {origin[3], extent[3]} a region of a split stage covers in the block
  * `cfg` describes (n, dim, nbr_mask); returns their number (at most SG_MAX_REGION_BOXES; a stage
  * launch carries that many), writes the first `max_boxes` of them to boxes[][6]. */

@@ -27,6 +27,16 @@ def comm_library():
     return buf.value.decode(), int(v.value)
 
 
+def locate_points(cfg, points):
+    """(cell [npts], xi [npts, dim]) of the points [npts, dim] in the block `cfg` (an SgConfig) describes: the block-local
+    cell that owns each point, -1 where another block or no block of the mesh does (sg_locate_points; device-free)."""
+    pts = _f64(points).reshape(-1, cfg.dim)
+    cell = np.empty(len(pts), dtype=np.int64)
+    xi = np.empty((len(pts), cfg.dim))
+    check(_lib.load().sg_locate_points(C.byref(cfg), len(pts), pts.ctypes.data, cell.ctypes.data, xi.ctypes.data))
+    return cell, xi
+
+
 class HipBlock(object):
     def __init__(self, dim, degree, n, h, origin, diagonal="left", nbr_mask=0, device=0, stream=None, dtype="f64",
                  cube0=None):
@@ -202,6 +212,27 @@ class HipBlock(object):
 
     def end_step(self):
         check(self.lib.sg_end_step(self.h), self.h)
+
+    # ---- receivers (sg_set_receivers / sg_get_receivers) ----------------------------------------
+    def set_receivers(self, points, what=1, every=1, capacity=0):
+        """Arm receivers at `points` [nrec, dim] - all of the mesh's: the block records the ones it owns - sampling the
+        velocity (what bit 0) and / or the stress (bit 1) after every `every`-th step, room for `capacity` samples.
+        No points: disarm.  Returns owned [nrec] (bool)."""
+        pts = _f64(points).reshape(-1, self.dim)
+        owned = np.zeros(len(pts), dtype=np.int32)
+        check(self.lib.sg_set_receivers(self.h, len(pts), pts.ctypes.data, int(what), int(every), int(capacity),
+                                        owned.ctypes.data), self.h)
+        ncomp = (self.dim if what & 1 else 0) + (self.dim * self.dim if what & 2 else 0)
+        self._rec_shape = (int(capacity), len(pts), ncomp) if len(pts) else (0, 0, 0)
+        return owned.astype(bool)
+
+    def get_receivers(self):
+        """The samples taken so far, [n, nrec, ncomp]: per receiver the velocity's dim values, then the stress's dim * dim
+        (row-major); rows of receivers the block does not own are 0."""
+        out = np.zeros(getattr(self, "_rec_shape", (0, 0, 0)))
+        n = C.c_int64()
+        check(self.lib.sg_get_receivers(self.h, out.ctypes.data, out.nbytes, C.byref(n)), self.h)
+        return out[:n.value]
 
     def apply_F(self, s_in, u_abs, u_out):
         check(self.lib.sg_apply_F(self.h, s_in, u_abs, u_out), self.h)

@@ -724,6 +724,83 @@ int sg_set_source_box_ricker(sg_handle* h, const double* lo, const double* hi, d
   return sg_set_source_separable(h, (int64_t)nodes.size(), nodes.data(), pattern.data(), nsteps, w.data());
 }
 
+// The receivers: located on the host (hostlogic.hpp locate_point, the rule of sg_locate_points), tabulated with the
+// element's basis, uploaded into locals, and moved into the handle once nothing can fail any more.
+int sg_set_receivers(sg_handle* h, int64_t nrec, const double* pts, int what, int64_t every, int64_t capacity,
+                     int32_t* owned) {
+  if (!h) return SG_ERR_ARG;
+  if (nrec < 0) return fail(h, SG_ERR_ARG, "sg_set_receivers: nrec must be >= 0");
+  if (nrec > 0 && !pts) return fail(h, SG_ERR_ARG, "sg_set_receivers: no points");
+  if (nrec > 0 && (what < 1 || what > 3)) return fail(h, SG_ERR_ARG, "sg_set_receivers: what must be 1 (velocity), 2 (stress) or 3");
+  if (nrec > 0 && every < 1) return fail(h, SG_ERR_ARG, "sg_set_receivers: every must be >= 1");
+  if (nrec > 0 && capacity < 0) return fail(h, SG_ERR_ARG, "sg_set_receivers: capacity must be >= 0");
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  const int d = h->cfg.dim, nd = h->re.nd;
+  ReceiverTables rt;
+  std::vector<int32_t> own((size_t)nrec, 0);
+  if (nrec > 0) {
+    NodeGeom G;
+    if (!G.init(&h->cfg, h->cfg.degree)) return fail(h, SG_ERR_ARG, "sg_set_receivers: cell type");
+    const int64_t gw = h->md.gw;
+    std::vector<int64_t> item;
+    std::vector<int32_t> lane;
+    std::vector<double> phi;
+    for (int64_t k = 0; k < nrec; ++k) {
+      double xi[3] = {0, 0, 0};
+      const int64_t cell = locate_point(G, pts + k * d, xi);
+      if (cell < 0) continue;
+      const int64_t cube = cell / h->ncls, cls = cell % h->ncls;
+      own[(size_t)k] = 1;
+      rt.row.push_back(k);
+      item.push_back((cube / gw) * h->ncls + cls);
+      lane.push_back((int32_t)(cube % gw));
+      phi.resize(phi.size() + (size_t)nd);
+      tabulate(d, h->cfg.degree, 1, xi, phi.data() + phi.size() - nd, h->re.kind);
+    }
+    rt.nrec = nrec;
+    rt.nown = (int64_t)rt.row.size();
+    rt.what = what;
+    rt.ncomp = ((what & 1) ? d : 0) + ((what & 2) ? d * d : 0);
+    rt.every = every;
+    rt.capacity = capacity;
+    if (rt.nown > 0 && capacity > ((int64_t)1 << 40) / (rt.nown * rt.ncomp))
+      return fail(h, SG_ERR_ARG, "sg_set_receivers: capacity too large");
+    const size_t tlen = (size_t)(capacity * rt.nown * rt.ncomp);
+    const int64_t zero = 0;
+    HIPCHECK(h, rt.item.upload(item.data(), item.size()));
+    HIPCHECK(h, rt.lane.upload(lane.data(), lane.size()));
+    HIPCHECK(h, rt.phi.upload(phi.data(), phi.size()));
+    if (rt.trace.alloc(tlen) != hipSuccess) return fail(h, SG_ERR_NOMEM, "sg_set_receivers: hipMalloc of the trace failed");
+    HIPCHECK(h, hipMemset(rt.trace.get(), 0, std::max<size_t>(tlen, 1) * sizeof(double)));
+    HIPCHECK(h, rt.ctr.upload(&zero, 1));
+  }
+  HIPCHECK(h, sync_all(h));
+  h->rec = std::move(rt);
+  h->epoch += 1;
+  if (owned) std::memcpy(owned, own.data(), own.size() * sizeof(int32_t));
+  return SG_OK;
+}
+
+int sg_get_receivers(sg_handle* h, double* out, size_t nbytes, int64_t* nsamples) {
+  if (!h || !nsamples) return SG_ERR_ARG;
+  const ReceiverTables& rt = h->rec;
+  const size_t want = (size_t)(rt.capacity * rt.nrec * rt.ncomp) * sizeof(double);
+  if (nbytes != want || (want > 0 && !out))
+    return fail(h, SG_ERR_ARG, "sg_get_receivers: the buffer must hold capacity x nrec x ncomp doubles (" + std::to_string(want) + " bytes)");
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  HIPCHECK(h, sync_all(h));
+  const int64_t n = rt.samples();
+  std::vector<double> t((size_t)(n * rt.nown * rt.ncomp));
+  if (!t.empty()) HIPCHECK(h, hipMemcpy(t.data(), rt.trace.get(), t.size() * sizeof(double), hipMemcpyDeviceToHost));
+  if (want > 0) std::memset(out, 0, want);
+  for (int64_t j = 0; j < n; ++j)
+    for (int64_t r = 0; r < rt.nown; ++r)
+      std::memcpy(out + (j * rt.nrec + rt.row[(size_t)r]) * rt.ncomp, t.data() + (j * rt.nown + r) * rt.ncomp,
+                  (size_t)rt.ncomp * sizeof(double));
+  *nsamples = n;
+  return SG_OK;
+}
+
 int sg_get_sym(const sg_handle* h, int* sym) {
   if (!h || !sym) return SG_ERR_ARG;
   *sym = h->sym ? 1 : 0;

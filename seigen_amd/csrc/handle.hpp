@@ -105,6 +105,26 @@ struct SourceTables {
   DevBuf<int32_t> slot, idx;
 };
 
+// The receivers of sg_set_receivers (the points of tests/explosive_source/uy.py:31-43), on the device: the owned ones'
+// cells and basis values, and the trace the recorder (kernels_recv.hip) fills at the end of every `every`-th step
+struct ReceiverTables {
+  int64_t nrec = 0;           // receivers armed (0: none; every block of a mesh is handed all of them)
+  int64_t nown = 0;           // ... of which this block owns these, in the order given
+  std::vector<int64_t> row;   // [nown] -> receiver index (the row of sg_get_receivers' output)
+  DevBuf<int64_t> item;       // [nown] (cube / gw) * ncls + class of the owning cell: node a, component c of a field with
+  DevBuf<int32_t> lane;       // [nown] cube % gw                  ncomp components at ((item * nd + a) * ncomp + c) * gw + lane
+  DevBuf<double> phi;         // [nown][nd] basis of the cell at the point
+  int what = 0;               // bit 0: velocity (dim values), bit 1: stress (dim x dim, row-major)
+  int ncomp = 0;
+  int64_t every = 1, capacity = 0;
+  DevBuf<double> trace;       // [capacity][nown][ncomp]
+  int64_t steps = 0;          // steps completed since arming; sample j is taken after step (j + 1) * every
+  // graph replay: the step index of the launches of a capture (RecvArgs::ctr), set by sg_step before it replays and
+  // bumped by a one-thread launch after the recorder (the role of sg_handle::src_ctr_d for the receivers)
+  DevBuf<int64_t> ctr;
+  int64_t samples() const { return nrec > 0 ? steps / every : 0; }
+};
+
 struct sg_handle {
   sg_config cfg;
   sg_comm_state* comm = nullptr;
@@ -154,6 +174,9 @@ struct sg_handle {
   DevBuf<int64_t> src_ctr_d;
   bool capture_src = false;   // stage launches issued now (a capture) take slice and weight from src_ctr_d
   bool graph_src = false;     // the captured graphs contain the source launches
+  ReceiverTables rec;
+  bool capture_rec = false;   // a capture: the recorder takes the step from rec.ctr
+  bool graph_rec = false;     // the captured graphs contain the recorder launches
   // halo
   const double* ghost[4][6] = {};
   // execution

@@ -3,6 +3,7 @@
 // reference-element operators and mesh tables.  No HIP header, no HIP call: this file, refelem.cpp, mesh_tables.cpp and
 // mfma_tables.cpp are what `make host-asan` builds with -fsanitize=address,undefined and runs on the CPU.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 
 #include "hostlogic.hpp"
@@ -115,9 +116,115 @@ void region_boxes(int d, const int32_t n[3], const int32_t has_nbr[6], int regio
   }
 }
 
+// J xi = r for a dim x dim system, Gaussian elimination with partial pivoting (what np.linalg.solve does in
+// functionspace.py locate); false if J is singular
+static bool solve_small(int d, double J[3][3], double r[3], double xi[3]) {
+  for (int j = 0; j < d; ++j) {
+    int pv = j;
+    for (int i = j + 1; i < d; ++i)
+      if (std::fabs(J[i][j]) > std::fabs(J[pv][j])) pv = i;
+    if (J[pv][j] == 0.0) return false;
+    if (pv != j) {
+      for (int k = 0; k < d; ++k) std::swap(J[j][k], J[pv][k]);
+      std::swap(r[j], r[pv]);
+    }
+    for (int i = j + 1; i < d; ++i) {
+      const double l = J[i][j] / J[j][j];
+      for (int k = j; k < d; ++k) J[i][k] -= l * J[j][k];
+      r[i] -= l * r[j];
+    }
+  }
+  for (int i = d - 1; i >= 0; --i) {
+    double v = r[i];
+    for (int k = i + 1; k < d; ++k) v -= J[i][k] * xi[k];
+    xi[i] = v / J[i][i];
+  }
+  return true;
+}
+
+int64_t locate_point(const NodeGeom& G, const double* p, double* xi) {
+  const sg_config& cfg = *G.cfg;
+  const int d = G.d;
+  // the cell's vertices are lattice corners: node 0 and the nodes P steps along each reference axis
+  int corner[4] = {0, 0, 0, 0};
+  for (int v = 0; v <= d; ++v)
+    for (int a = 0; a < G.nq; ++a) {
+      bool hit = true;
+      for (int m = 0; m < d; ++m) hit = hit && G.lat[(size_t)a * d + m] == (m == v - 1 ? G.degree : 0);
+      if (hit) {
+        corner[v] = a;
+        break;
+      }
+    }
+  int64_t opt[3][2] = {{0, 0}, {0, 0}, {0, 0}};
+  int nopt[3] = {1, 1, 1};
+  for (int a = 0; a < d; ++a) {
+    const double t = (p[a] - cfg.origin[a]) / cfg.h[a];
+    if (!(std::fabs(t) < 1e15)) return -1;     // NaN, or far outside any mesh
+    const int64_t i = (int64_t)std::floor(t);
+    nopt[a] = 0;
+    if (std::fabs(t - std::nearbyint(t)) < 1e-9 && i - 1 >= 0) opt[a][nopt[a]++] = i - 1;
+    if (i >= 0) opt[a][nopt[a]++] = i;
+    if (nopt[a] == 0) return -1;
+  }
+  for (int oz = 0; oz < nopt[2]; ++oz)
+    for (int oy = 0; oy < nopt[1]; ++oy)
+      for (int ox = 0; ox < nopt[0]; ++ox) {
+        const int64_t g[3] = {opt[0][ox], opt[1][oy], opt[2][oz]};
+        // block-local cube (NodeGeom adds cube0 back first: the same coordinates on every block)
+        int c[3] = {0, 0, 0};
+        bool mine = true;
+        for (int a = 0; a < d; ++a) {
+          const int64_t l = g[a] - cfg.cube0[a];
+          // the candidates of an axis are at most one apart: none of them lies in this block
+          if (l < -1 || l > cfg.n[a]) return -1;
+          c[a] = (int)l;
+          mine = mine && l >= 0 && l < cfg.n[a];
+        }
+        for (int k = 0; k < G.ncls; ++k) {
+          double V[4][3];
+          for (int v = 0; v <= d; ++v) G.node(c, k, corner[v], V[v]);
+          double J[3][3], r[3], x[3] = {0, 0, 0};
+          for (int i = 0; i < d; ++i) {
+            for (int m = 0; m < d; ++m) J[i][m] = V[m + 1][i] - V[0][i];
+            r[i] = p[i] - V[0][i];
+          }
+          if (!solve_small(d, J, r, x)) continue;
+          double lo = x[0], hi = x[0], sum = x[0];
+          for (int m = 1; m < d; ++m) {
+            lo = std::min(lo, x[m]);
+            hi = std::max(hi, x[m]);
+            sum += x[m];
+          }
+          const double top = cfg.diagonal == SG_DIAGONAL_QUAD ? hi : sum;
+          if (!(lo >= -1e-12 && top <= 1.0 + 1e-12)) continue;
+          if (!mine) return -1;     // the winner lies in a neighbouring block
+          for (int m = 0; m < d; ++m) xi[m] = x[m];
+          const int64_t cube = c[0] + (int64_t)cfg.n[0] * ((d > 1 ? c[1] : 0) + (int64_t)(d > 1 ? cfg.n[1] : 1) * (d > 2 ? c[2] : 0));
+          return cube * G.ncls + k;
+        }
+      }
+  return -1;
+}
+
 extern "C" {
 
 int sg_abi_version(void) { return SG_ABI_VERSION; }
+
+int sg_locate_points(const sg_config* cfg, int64_t npts, const double* pts, int64_t* cell, double* xi) {
+  if (!cfg || npts < 0 || (npts > 0 && (!pts || !cell || !xi))) return SG_ERR_ARG;
+  if (cfg->dim < 1 || cfg->dim > 3 || cfg->degree < 1 || cfg->degree > 8) return SG_ERR_ARG;
+  for (int a = 0; a < cfg->dim; ++a)
+    if (cfg->n[a] < 1 || !(cfg->h[a] > 0.0)) return SG_ERR_ARG;
+  NodeGeom G;
+  if (!G.init(cfg, cfg->degree)) return SG_ERR_ARG;
+  const int d = cfg->dim;
+  for (int64_t k = 0; k < npts; ++k) {
+    for (int m = 0; m < d; ++m) xi[k * d + m] = 0.0;
+    cell[k] = locate_point(G, pts + k * d, xi + k * d);
+  }
+  return SG_OK;
+}
 
 int sg_block_node_coords(const sg_config* cfg, int degree, double* out, size_t nbytes) {
   if (!cfg || !out || degree < 1 || degree > 8 || cfg->dim < 1 || cfg->dim > 3) return SG_ERR_ARG;

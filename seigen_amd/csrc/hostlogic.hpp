@@ -101,3 +101,10 @@ struct NodeGeom {
   }
 };
 
+// Point location of sg_locate_points and sg_set_receivers: the rule of seigen_amd/functionspace.py locate, with the
+// candidate cubes counted in the MESH's indices.  Per axis the cube holding the point; on a grid line (|t - round t| <
+// 1e-9) also the one below it, provided that exists (global index >= 0).  The candidates are tried in ascending order
+// (z slowest), in each the classes in ascending order; the first whose reference coordinates pass -1e-12 / 1 + 1e-12
+// wins.  Every block of a partition finds the same winner; the block that holds it owns the point.
+// Returns the block-local cell (xi[dim] its reference coordinates) or -1: another block's, or outside the mesh.
+int64_t locate_point(const NodeGeom& G, const double* p, double* xi);

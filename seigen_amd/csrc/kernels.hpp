@@ -254,4 +254,22 @@ int launch_sponge_affine_mfma(int P, const void* uabs, const double* fragX, cons
 // the device-side step counter of SrcStep: *ctr = value (add = 0) or *ctr += value (add = 1), one thread
 int launch_step_counter(int64_t* ctr, int64_t value, int add, void* stream);
 
+// Receiver samples (kernels_recv.hip): after step s (counted from the arming call) with s % every == 0, sample
+// j = s / every - 1 of receiver r, component q: trace[j][r][q] = sum_a phi[r][a] field[node a][c] over a ascending, in
+// double with fma (q < nu: the velocity, c = q; else the stress, c = q - nu, the (i > j) entries from their mirrors in
+// symmetric mode).  Field offsets as in every layout: ((item * nd + a) * ncomp_field + c) * gw + lane.
+struct RecvArgs {
+  const int64_t* ctr;      // graph replay: *ctr + 1 is the step that just ended; null: `step`
+  int64_t step;
+  int64_t every, capacity; // (a sample index beyond the capacity is not written)
+  const int64_t* item;     // [nown]
+  const int32_t* lane;     // [nown]
+  const double* phi;       // [nown][nd]
+  double* trace;           // [capacity][nown][ncomp]
+  int64_t nown;
+  int32_t ncomp, nu;       // components per receiver, of which the first nu are the velocity's
+  int32_t dim, nd, gw, sym;
+};
+int launch_receivers(const void* u, const void* s, const RecvArgs& a, int f32, void* stream);
+
 }  // namespace sg

@@ -385,8 +385,48 @@ int sg_run_stage(sg_handle* h, int stage, int region) {
   return SG_OK;
 }
 
+// The end of a step for the receivers (sg_set_receivers): the recorder samples u1 and s1 of the step that just ended, on
+// the main stream behind stage S1's SECOND launch.  Eager launches name the step by value and count it here; the launches
+// of a capture read it from rec.ctr and bump that (sg_step sets it before it replays and counts the replayed steps).
+// SG_ERR_STATE, nothing queued and nothing counted: the step is due a sample the trace has no room for.
+static int record_step(sg_handle* h) {
+  ReceiverTables& rt = h->rec;
+  if (rt.nrec == 0 || h->name_out) return SG_OK;
+  const int64_t step = rt.steps + 1;
+  if (!h->capture_rec && step % rt.every == 0 && step / rt.every > rt.capacity)
+    return fail(h, SG_ERR_STATE, "receiver trace full: read it out (sg_get_receivers) and re-arm before stepping on");
+  if (rt.nown > 0) {
+    if (int rc = join_second(h)) return rc;
+    RecvArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.ctr = h->capture_rec ? rt.ctr.get() : nullptr;
+    a.step = step;
+    a.every = rt.every;
+    a.capacity = rt.capacity;
+    a.item = rt.item.get();
+    a.lane = rt.lane.get();
+    a.phi = rt.phi.get();
+    a.trace = rt.trace.get();
+    a.nown = rt.nown;
+    a.ncomp = rt.ncomp;
+    a.nu = (rt.what & 1) ? h->cfg.dim : 0;
+    a.dim = h->cfg.dim;
+    a.nd = h->re.nd;
+    a.gw = (int32_t)h->md.gw;
+    a.sym = h->sym ? 1 : 0;
+    if (launch_receivers(h->field[SG_FIELD_U].get(), h->field[SG_FIELD_S].get(), a, h->f32, h->stream) != 0)
+      return fail(h, SG_ERR_DEVICE, "receiver launch failed");
+    if (h->capture_rec && launch_step_counter(rt.ctr.get(), 1, 1, h->stream) != 0)
+      return fail(h, SG_ERR_DEVICE, "step counter launch failed");
+  }
+  if (!h->capture_rec) rt.steps = step;
+  return SG_OK;
+}
+
 int sg_end_step(sg_handle* h) {
   if (!h) return SG_ERR_ARG;
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  if (int rc = record_step(h)) return rc;
   h->src_step += 1;
   h->counters.steps += 1;
   return SG_OK;
@@ -401,7 +441,7 @@ static int enqueue_step(sg_handle* h) {
   // the next step's slice (tile path: stage UH1 bumps the counter itself, run_op)
   if (h->capture_src && !h->src.fused && launch_step_counter(h->src_ctr_d.get(), 1, 1, h->stream) != 0)
     return fail(h, SG_ERR_DEVICE, "step counter launch failed");
-  return SG_OK;
+  return record_step(h);
 }
 
 // capture `steps` steps into an executable graph; on any failure graphs are switched off for the handle
@@ -419,10 +459,12 @@ static hipGraphExec_t capture_steps(sg_handle* h, int steps, bool with_src) {
   if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return nullptr;
   int rc = SG_OK;
   h->capture_src = with_src;
+  h->capture_rec = h->rec.nrec > 0;
   h->sponge.pre_ver = ~0ull;      // a replay starts from whatever the buffer holds: the captured step computes its own
   for (int k = 0; k < steps && rc == SG_OK; ++k) rc = enqueue_step(h);
   h->sponge.pre_ver = ~0ull;      // nothing was launched: the buffer holds what it held
   h->capture_src = false;
+  h->capture_rec = false;
   hipError_t e = hipStreamEndCapture(h->stream, &g);
   if (rc == SG_OK && e == hipSuccess && g) {
     if (hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) != hipSuccess) ge = nullptr;
@@ -435,6 +477,11 @@ static hipGraphExec_t capture_steps(sg_handle* h, int steps, bool with_src) {
 int sg_step(sg_handle* h, int64_t nsteps) {
   if (!h || nsteps < 0) return SG_ERR_ARG;
   if (!h->params_set) return fail(h, SG_ERR_STATE, "sg_set_params must be called before stepping");
+  // the receivers' samples of all nsteps steps must fit the trace: checked before anything is queued (native exchange too)
+  if (h->rec.nrec > 0 && (h->rec.steps + nsteps) / h->rec.every > h->rec.capacity)
+    return fail(h, SG_ERR_STATE, "sg_step: the receiver trace has room for " + std::to_string(h->rec.capacity - h->rec.samples()) +
+                                     " more samples, these steps take " +
+                                     std::to_string((h->rec.steps + nsteps) / h->rec.every - h->rec.samples()));
   HIPCHECK(h, hipSetDevice(h->cfg.device));
   for (int s = 0; s < 6; ++s)
     if (h->md.has_nbr[s]) {
@@ -449,13 +496,16 @@ int sg_step(sg_handle* h, int64_t nsteps) {
   const bool graphs = h->graph_ok && !h->timing && nsteps >= 2;
   const bool with_src = source_active(h) && h->src_ctr_d.get() != nullptr;
   if (graphs && source_active(h) && !with_src) return fail(h, SG_ERR_STATE, "source without a device-side step counter");
-  if (graphs && (h->graph_epoch != h->epoch || h->graph_src != with_src)) {
+  // armed receivers are part of the graphs too: the recorder takes its step from rec.ctr, set here like the source's
+  const bool with_rec = h->rec.nrec > 0;
+  if (graphs && (h->graph_epoch != h->epoch || h->graph_src != with_src || h->graph_rec != with_rec)) {
     if (h->graph1) (void)hipGraphExecDestroy(h->graph1);
     if (h->graph8) (void)hipGraphExecDestroy(h->graph8);
     h->graph1 = capture_steps(h, 1, with_src);
     h->graph8 = h->graph1 ? capture_steps(h, 8, with_src) : nullptr;
     h->graph_epoch = h->epoch;
     h->graph_src = with_src;
+    h->graph_rec = with_rec;
     if (!h->graph1 || !h->graph8) h->graph_ok = false;  // same kernels, launched one by one below
   }
   HIPCHECK(h, hipEventRecord(h->ev0, h->stream));
@@ -463,11 +513,14 @@ int sg_step(sg_handle* h, int64_t nsteps) {
     // (tile path: the counter is bumped by the launch that OPENS a step, so it starts one short)
     if (with_src && launch_step_counter(h->src_ctr_d.get(), h->src_step - (h->src.fused ? 1 : 0), 0, h->stream) != 0)
       return fail(h, SG_ERR_DEVICE, "step counter launch failed");
+    if (h->rec.nown > 0 && launch_step_counter(h->rec.ctr.get(), h->rec.steps, 0, h->stream) != 0)
+      return fail(h, SG_ERR_DEVICE, "step counter launch failed");
     for (; k + 8 <= nsteps; k += 8) HIPCHECK(h, hipGraphLaunch(h->graph8, h->stream));
     for (; k < nsteps; ++k) HIPCHECK(h, hipGraphLaunch(h->graph1, h->stream));
     for (int st = 0; st < 6; ++st) h->counters.launches[st] += nsteps;
     h->counters.steps += nsteps;
     h->src_step += nsteps;
+    if (with_rec) h->rec.steps += nsteps;
     if (nsteps > 0) {
       for (int f = 0; f < 4; ++f) mark_field_written(h, f);
       h->sponge.pre_ver = ~0ull;
@@ -484,6 +537,7 @@ int sg_step(sg_handle* h, int64_t nsteps) {
         h->counters.launches[st] += 1;
       }
     }
+    if (int rc = record_step(h)) return rc;
     h->src_step += 1;
     h->counters.steps += 1;
   }

@@ -36,7 +36,7 @@ import numpy as np
 from . import _lib
 from .backend import HipBlock
 from .functionspace import Function, FunctionSpace, TensorFunctionSpace, VectorFunctionSpace
-from .helpers import log, allreduce_sum
+from .helpers import log, allreduce_sum, allreduce_sum_array
 from .parallel import world, HaloExchanger, NativeExchanger
 from .profiling import timed_region
 
@@ -135,6 +135,8 @@ class ElasticLF4(object):
             self.invmass_stress = None
             self._exchanger = None
             self._step_index = 0
+            self._receivers = None          # (points, every, what) of set_receivers
+            self._receiver_times = []
 
         if self.output:
             with timed_region('i/o'):
@@ -437,6 +439,54 @@ class ElasticLF4(object):
             return
         self._block.set_source(nodes, values, static=static)
 
+    # ---- receivers (tests/explosive_source/uy.py:31-43) -------------------------------------------
+    def set_receivers(self, points, every=1, fields=("velocity",)):
+        """Record `fields` ("velocity" = VelocityNew, "stress" = StressNew) at the physical `points` [R, dim] after every
+        `every`-th step of the next runs, on the device inside the time loop (sg_set_receivers) - what the reference's
+        receiver script gets by writing a VTU file per step and probing every 5th.  Collective with more than one rank:
+        every point must have exactly one owning block (ValueError naming the first that has not)."""
+        what = 0
+        for f in fields:
+            if f not in ("velocity", "stress"):
+                raise ValueError("receiver fields are 'velocity' and 'stress', not %r" % (f,))
+            what |= 1 if f == "velocity" else 2
+        if what == 0 or int(every) < 1:
+            raise ValueError("set_receivers needs at least one field and every >= 1")
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, self.dimension)
+        from .backend import locate_points
+        from .functionspace import block_config
+        cell, _ = locate_points(block_config(self.mesh, self.degree), pts)
+        owners = allreduce_sum_array((cell >= 0).astype(np.float64))
+        for k in range(len(pts)):
+            if owners[k] != 1:
+                raise ValueError("receiver %d at %r has %d owning blocks, not one (outside the mesh?)"
+                                 % (k, tuple(pts[k]), int(owners[k])))
+        self._receivers = (pts, int(every), what)
+
+    def receiver_traces(self):
+        """(times [n], {"velocity": [n, R, dim], "stress": [n, R, dim, dim]}) of the receivers of the last run: sample j
+        after step (j + 1) * every, at t = times[j]."""
+        if self._receivers is None:
+            raise RuntimeError("no receivers: call set_receivers before run")
+        pts, every, what = self._receivers
+        d = self.dimension
+        tr = allreduce_sum_array(self._block.get_receivers())     # rows of the other blocks' receivers are 0 here
+        n = tr.shape[0]
+        out = {}
+        if what & 1:
+            out["velocity"] = tr[..., :d].copy()
+        if what & 2:
+            off = d if what & 1 else 0
+            out["stress"] = tr[..., off:off + d * d].reshape(n, len(pts), d, d)
+        return np.array(self._receiver_times[:n]), out
+
+    def _arm_receivers(self, times):
+        if self._receivers is None:
+            return
+        pts, every, what = self._receivers
+        self._block.set_receivers(pts, what, every, len(times) // every)
+        self._receiver_times = list(times[every - 1::every])
+
     # ---- time loop (elastic.py:267-315) ----------------------------------------------------------
     def step_times(self, T):
         """The values of `t` visited by the reference loop ``t = dt; while t <= T + 1e-12``."""
@@ -478,6 +528,7 @@ class ElasticLF4(object):
             with timed_region('source term update'):
                 self.upload_source(times)
             self._agree_on_stress_storage()
+            self._arm_receivers(times)
             with self.loop_context():
                 if self.output:
                     for t in times:

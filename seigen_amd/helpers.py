@@ -36,6 +36,20 @@ def allreduce_sum(value):
     return type(value)(t.item())
 
 
+def allreduce_sum_array(a):
+    """Element-wise sum of a float64 array over the ranks (the array itself with one rank)."""
+    import numpy as np
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    dist = _dist()
+    if dist is None or dist.get_world_size() == 1:
+        return a
+    import torch
+    dev = "cuda" if dist.get_backend() == "nccl" else "cpu"
+    t = torch.from_numpy(a.copy()).to(dev)
+    dist.all_reduce(t)
+    return t.cpu().numpy()
+
+
 def get_dofs(mesh, p):
     """Global (stress, velocity) degree-of-freedom counts (``seigen/helpers.py:57-67``;
     the reference body uses undefined names - this is what it is meant to return)."""

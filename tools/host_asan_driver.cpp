@@ -159,6 +159,87 @@ static void regions_and_coords() {
   EXPECT(sg_region_boxes(nullptr, 0, nullptr, 0) == SG_ERR_ARG);
 }
 
+// sg_locate_points (the receivers' point location) on every dim, cell kind and degree: points inside cells, on cube faces,
+// edges and vertices (grid lines), on the faces between the simplices of a cube, on the mesh boundary and outside; the
+// blocks of a 2 x 2 x 2 (2-D: 2 x 2, 1-D: 2) split must own every point inside exactly once, in the cell the whole mesh finds
+static void point_location() {
+  for (int dim = 1; dim <= 3; ++dim)
+    for (int diagonal : {0, 1, 2}) {
+      if (diagonal == 2 && dim == 1) continue;
+      for (int degree = 1; degree <= 4; ++degree) {
+        sg_config whole;
+        std::memset(&whole, 0, sizeof(whole));
+        whole.dim = dim;
+        whole.degree = degree;
+        for (int a = 0; a < 3; ++a) {
+          whole.n[a] = a < dim ? 4 : 1;
+          whole.h[a] = a < dim ? 0.25 * (a + 1) : 1.0;
+        }
+        whole.diagonal = diagonal;
+        std::vector<double> pts;
+        // fractions of a cube: on lines (0), on the inner faces (equal / complementary), inside; cubes -1 .. 4
+        const double fr[] = {0.0, 0.25, 0.5, 0.75, 0.3, 0.7};
+        for (int cz = (dim > 2 ? -1 : 0); cz <= (dim > 2 ? 4 : 0); ++cz)
+          for (int cy = (dim > 1 ? -1 : 0); cy <= (dim > 1 ? 4 : 0); ++cy)
+            for (int cx = -1; cx <= 4; ++cx)
+              for (int f = 0; f < 6; ++f) {
+                const int c[3] = {cx, cy, cz};
+                for (int a = 0; a < dim; ++a) pts.push_back((c[a] + (a == 1 ? 1.0 - fr[f] : fr[f])) * whole.h[a]);
+              }
+        const int64_t np = (int64_t)pts.size() / dim;
+        std::vector<int64_t> cell1(np), cell(np);
+        std::vector<double> xi1(pts.size()), xi(pts.size());
+        EXPECT(sg_locate_points(&whole, np, pts.data(), cell1.data(), xi1.data()) == SG_OK);
+        std::vector<int> owners(np, 0);
+        for (int b = 0; b < (1 << dim); ++b) {
+          sg_config blk = whole;
+          for (int a = 0; a < dim; ++a) {
+            const int hi = (b >> a) & 1;
+            blk.n[a] = 2;
+            blk.cube0[a] = 2 * hi;
+            blk.nbr_mask |= 1 << (2 * a + (1 - hi));
+          }
+          EXPECT(sg_locate_points(&blk, np, pts.data(), cell.data(), xi.data()) == SG_OK);
+          for (int64_t k = 0; k < np; ++k) {
+            if (cell[k] < 0) continue;
+            owners[k] += 1;
+            const int ncls = dim == 1 || diagonal == 2 ? 1 : (dim == 2 ? 2 : 6);
+            const int64_t cube = cell[k] / ncls;
+            const int64_t lc[3] = {cube % 2, (cube / 2) % 2, cube / 4};
+            int64_t g = 0, mul = 1;
+            for (int a = 0; a < dim; ++a) {
+              g += (lc[a] + blk.cube0[a]) * mul;
+              mul *= 4;
+            }
+            EXPECT(g * ncls + cell[k] % ncls == cell1[k]);
+            for (int a = 0; a < dim; ++a) EXPECT(xi[k * dim + a] == xi1[k * dim + a]);
+          }
+        }
+        for (int64_t k = 0; k < np; ++k) {
+          EXPECT(owners[k] == (cell1[k] >= 0 ? 1 : 0));
+          bool inside = true;
+          for (int a = 0; a < dim; ++a) inside = inside && pts[k * dim + a] >= 0.0 && pts[k * dim + a] <= 4 * whole.h[a];
+          EXPECT(inside == (cell1[k] >= 0));
+          for (int a = 0; a < dim && cell1[k] >= 0; ++a) EXPECT(xi1[k * dim + a] >= -1e-12 && xi1[k * dim + a] <= 1.0 + 1e-12);
+        }
+      }
+    }
+  sg_config cfg;
+  std::memset(&cfg, 0, sizeof(cfg));
+  cfg.dim = 2;
+  cfg.degree = 2;
+  cfg.n[0] = cfg.n[1] = 2;
+  cfg.h[0] = cfg.h[1] = 1.0;
+  double p[2] = {0.5, 0.5}, x[2];
+  int64_t c = 0;
+  EXPECT(sg_locate_points(&cfg, -1, p, &c, x) == SG_ERR_ARG);
+  EXPECT(sg_locate_points(&cfg, 1, nullptr, &c, x) == SG_ERR_ARG);
+  EXPECT(sg_locate_points(nullptr, 1, p, &c, x) == SG_ERR_ARG);
+  EXPECT(sg_locate_points(&cfg, 1, p, &c, x) == SG_OK && c >= 0);
+  cfg.h[1] = 0.0;
+  EXPECT(sg_locate_points(&cfg, 1, p, &c, x) == SG_ERR_ARG);
+}
+
 // Which kernel family runs a block (hostapi.cpp choose_kernel_path), pinned row by row: one row on each side of every size
 // threshold, and every SEIGEN_HIP_PATH value - unset, the four names, an unknown string - for each dimension and cell type.
 // (The lane thresholds only decide in 1-D: 2-D simplices take the tile kernels and 3-D ones the MFMA kernels first.)
@@ -387,6 +468,7 @@ int main() {
     tile_tables_2d(degree, KIND_TENSOR);
   }
   regions_and_coords();
+  point_location();
   kernel_family_table();
   for (int dim = 1; dim <= 3; ++dim)
     for (int degree : {1, 2, 4})
