@@ -123,9 +123,6 @@ struct sg_comm_state {
     }                                                                                            \
   } while (0)
 
-static const int kStageOutput[6] = {SG_FIELD_UH, SG_FIELD_SH, SG_FIELD_U, SG_FIELD_SH, SG_FIELD_UH, SG_FIELD_S};
-static const int kStageInput[6] = {SG_FIELD_S, SG_FIELD_UH, SG_FIELD_SH, SG_FIELD_U, SG_FIELD_SH, SG_FIELD_UH};
-
 static int resolve_waits(sg_handle* h) {
   sg_comm_state* c = h->comm;
   for (size_t k = 0; k + 1 < c->wait_events.size(); k += 2) {
@@ -210,40 +207,27 @@ int comm_step(sg_handle* h, int64_t nsteps) {
   if (nsteps <= 0) return SG_OK;
   HIPCHECK(h, hipEventRecord(h->ev0, h->stream));
   // the halo of the first stage's input: the caller may have changed the fields since the last call
-  int rc = exchange(h, kStageInput[0], nullptr);
-  if (rc != SG_OK) return rc;
+  if (int rc = exchange(h, lf4_stage_input(0), nullptr)) return rc;
   for (int64_t k = 0; k < nsteps; ++k) {
     for (int st = 0; st < 6; ++st) {
-      rc = sg_run_stage(h, st, SG_REGION_FIRST);
-      if (rc != SG_OK) return rc;
+      if (int rc = sg_run_stage(h, st, SG_REGION_FIRST)) return rc;
       hipEvent_t recv_done = nullptr, second_done = nullptr;
-      rc = exchange(h, kStageOutput[st], h->timing ? &recv_done : nullptr);
-      if (rc != SG_OK) return rc;
-      rc = sg_run_stage(h, st, SG_REGION_SECOND);
-      if (rc != SG_OK) return rc;
+      if (int rc = exchange(h, lf4_stage_output(st), h->timing ? &recv_done : nullptr)) return rc;
+      if (int rc = sg_run_stage(h, st, SG_REGION_SECOND)) return rc;
       if (h->timing) {
         // what the next stage waits for the traces BEYOND the end of the SECOND launch that ran beside them
-        rc = take_event(h, &second_done);
-        if (rc != SG_OK) return rc;
+        if (int rc = take_event(h, &second_done)) return rc;
         HIPCHECK(h, hipEventRecord(second_done, h->overlap ? h->stream2 : h->stream));
         c->wait_events.push_back(second_done);
         c->wait_events.push_back(recv_done);
-        if (c->wait_events.size() >= 8192) {
-          rc = resolve_waits(h);
-          if (rc != SG_OK) return rc;
-        }
+        if (c->wait_events.size() >= 8192)
+          if (int rc = resolve_waits(h)) return rc;
       }
     }
-    rc = sg_end_step(h);
-    if (rc != SG_OK) return rc;
+    if (int rc = sg_end_step(h)) return rc;
   }
-  if (int rc2 = join_second(h)) return rc2;
-  HIPCHECK(h, hipEventRecord(h->ev1, h->stream));
-  HIPCHECK(h, hipEventSynchronize(h->ev1));
-  float ms = 0;
-  HIPCHECK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  h->last_ms = ms;
-  return SG_OK;
+  if (int rc = join_second(h)) return rc;
+  return finish_step_call(h);
 }
 
 void comm_release(sg_handle* h) {

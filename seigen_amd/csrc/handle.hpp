@@ -268,6 +268,7 @@ inline void region_boxes(const sg_handle* h, int region, std::vector<Box>& out) 
                shell_width_x(h->md.gw, h->cfg.n[0], h->md.has_nbr[0] != 0, h->md.has_nbr[1] != 0));
 }
 int resolve_timing(sg_handle* h);
+int finish_step_call(sg_handle* h);   // stages.cpp: the end of sg_step and comm_step (ev1, synchronise, last_ms)
 // comm.cpp
 int comm_step(sg_handle* h, int64_t nsteps);
 void comm_release(sg_handle* h);

@@ -54,6 +54,35 @@ Family choose_kernel_path(const sg_config& cfg) {
   return Family::Generic;
 }
 
+StageOp lf4_stage(int stage, double dt, double rho, bool rho_physical, bool per_cell_density) {
+  const double c3 = dt * dt * dt / 24.0;
+  const int U = SG_FIELD_U, UH = SG_FIELD_UH, S = SG_FIELD_S, SH = SG_FIELD_SH;
+  switch (stage) {   // {kind, in, out, aux, uabs, mode, c_self, c_aux, c_new, with_source, src_coef, density}
+    case SG_STAGE_UH1: return {0, S, UH};
+    case SG_STAGE_STEMP: return {1, UH, SH, -1, U, 0, 0.0, 0.0, 0.0, true, 1.0, false};
+    case SG_STAGE_U1:
+      // explicit mode keeps only rhs(form_u1): u1 = rho*u0 + dt*uh1 + dt^3/24*uh2 (elastic.py:341-345, :354-356);
+      // sg_set_density(physical = 1): u1 = u0 + (dt*uh1 + dt^3/24*uh2)/rho; per-cell density: factors in rho2
+      if (per_cell_density) return {0, SH, U, UH, U, 1, 1.0, dt, c3, false, 1.0, true};
+      if (rho_physical) return {0, SH, U, UH, U, 1, 1.0, dt / rho, c3 / rho, false, 1.0, false};
+      return {0, SH, U, UH, U, 1, rho, dt, c3, false, 1.0, false};
+    case SG_STAGE_SH1: return {1, U, SH, -1, U, 0, 0.0, 0.0, 0.0, true, 1.0, false};
+    case SG_STAGE_UTEMP:
+      // utemp = F(sh1; u1) has one consumer, sh2 = G(utemp) in the stress update s1 = s0 + dt sh1 + dt^3/24 sh2 with
+      // sh1 = G(u1) + S (elastic.py:300-303, :348-352) - and g is LINEAR in the velocity: dt G(u1) + dt^3/24 G(utemp) =
+      // G(dt u1 + dt^3/24 utemp).  So this stage leaves w = dt u1 + dt^3/24 utemp in UH (one more operand in its fused
+      // epilogue, on a stage that waits for the matrix pipe, not for memory) and stage S1 reads w and s0 ONLY: no sh1, no
+      // second right-hand side - 6 of its 21 words per node gone (the halo exchanged after this stage is w's).
+      // (mode 2: the fused form without the self term, out = c_aux aux + c_new rhs; kernel families without an instantiation
+      // of their own run their mode-1 kernels with c_self = 0)
+      return {0, SH, UH, U, U, 2, 0.0, dt, c3, false, 1.0, false};
+    case SG_STAGE_S1:
+      // s1 = s0 + G(w) + (dt + dt^3/24) S   (G stage kernels, fused form: out = c_self out + c_new rhs, no second operand)
+      return {1, UH, S, -1, U, 1, 1.0, 0.0, 1.0, true, dt + c3, false};
+  }
+  return {};
+}
+
 void region_boxes(int d, const int32_t n[3], const int32_t has_nbr[6], int region, std::vector<Box>& out, int xw) {
   out.clear();
   int lo[3] = {0, 0, 0}, hi[3];

@@ -1,5 +1,5 @@
-// Host logic of libseigen_hip that needs no device and no HIP header: which kernel family runs a block, the boxes of
-// the regions of a split stage, node coordinates of a block.  Defined in hostapi.cpp, which - with refelem.cpp,
+// Host logic of libseigen_hip that needs no device and no HIP header: which kernel family runs a block, the six stages
+// of an LF4 step, the boxes of the regions of a split stage, node coordinates of a block.  Defined in hostapi.cpp, which - with refelem.cpp,
 // mesh_tables.cpp and mfma_tables.cpp - also builds on its own for the CPU sanitizer target (`make host-asan`).
 #pragma once
 #include <cstdint>
@@ -45,6 +45,23 @@ inline bool family_pre_lines(Family f) { return f == Family::Mfma; }
 inline bool family_fused_source(Family f) { return f == Family::Tile2d; }
 // a region of whole cell groups runs as a whole-block launch: no cube coordinates, no box tests (StageArgs::all_active)
 inline bool family_whole_groups(Family f) { return f == Family::Mfma || f == Family::Hexm; }
+
+// One launch of a stage kernel as a value (stages.cpp run_op): F or G of a field and the fused epilogue around it
+// (kernels.hpp StageArgs::mode / c_self / c_aux / c_new).  The defaults are the un-fused application out = F(in; u) / G(in).
+struct StageOp {
+  int kind = -1;            // 0 = F (stress -> velocity), 1 = G (velocity -> stress)
+  int in = -1, out = -1, aux = -1, uabs = SG_FIELD_U;   // SG_FIELD_*; aux = -1: none; uabs: what the sponge of an F stage absorbs
+  int mode = 0;
+  double c_self = 0.0, c_aux = 0.0, c_new = 0.0;
+  bool with_source = false;   // a G stage that adds the source: in the kernel (2-D tile family) or by a launch after it
+  double src_coef = 1.0;      // factor on the source
+  bool density = false;       // the per-cell density factors go with the launch (stage U1)
+};
+// The six fused launches of an LF4 step (enum sg_stage), stated here alone: the native exchange takes a stage's input and
+// output field from it, seigen_amd/parallel.py STAGE_INPUT / STAGE_OUTPUT is tested against it.  No such stage: kind = -1.
+StageOp lf4_stage(int stage, double dt, double rho, bool rho_physical, bool per_cell_density);
+inline int lf4_stage_input(int stage) { return lf4_stage(stage, 0.0, 1.0, false, false).in; }
+inline int lf4_stage_output(int stage) { return lf4_stage(stage, 0.0, 1.0, false, false).out; }
 
 struct Box {
   int o[3], n[3];

@@ -21,22 +21,28 @@ static SrcStep source_stepper(const sg_handle* h) {
   if (ss.stride == 0 && ss.weights == nullptr) ss.is_static = 1;
   return ss;
 }
-// separable source: the one stored slice, scaled by this step's weight
-static bool source_one_slice(const sg_handle* h) { return h->src.is_static || !h->src.weights.empty(); }
+// a source launch is due (the graphs of a capture hold source launches only while it is active, ensure_graphs) ...
+static bool source_due(const sg_handle* h) { return h->capture_src || source_active(h); }
+// ... with this step's slice and weight (separable source: the one stored slice, scaled); a capture: source_stepper's
+static const double* source_values(const sg_handle* h) {
+  const bool one_slice = h->capture_src || h->src.is_static || !h->src.weights.empty();
+  return h->src.values.get() + (size_t)(one_slice ? 0 : h->src_step) * h->src.nnz * h->cfg.dim * h->cfg.dim;
+}
 static double source_scale(const sg_handle* h) {
-  return h->src.weights.empty() ? 1.0 : h->src.weights[(size_t)h->src_step];
+  return (h->capture_src || h->src.weights.empty()) ? 1.0 : h->src.weights[(size_t)h->src_step];
 }
 
 // the arguments of a stage launch (kernels.hpp StageArgs) but for the region's boxes and items
-static int stage_args(sg_handle* h, StageArgs& a, int kind, int in_f, int out_f, int aux_f, int mode, double c_self, double c_aux,
-                      double c_new, int region, int uabs_f, bool with_source, bool density, double src_coef) {
+static int stage_args(sg_handle* h, StageArgs& a, const StageOp& op, int region) {
+  const int kind = op.kind;
+  if (kind != 0 && kind != 1) return fail(h, SG_ERR_ARG, "unknown stage");
   std::memset(&a, 0, sizeof(a));
-  a.in = h->field[in_f].get();
-  a.out = h->field[out_f].get();
-  a.aux = aux_f >= 0 ? h->field[aux_f].get() : nullptr;
-  a.uabs = h->field[uabs_f].get();
+  a.in = h->field[op.in].get();
+  a.out = h->field[op.out].get();
+  a.aux = op.aux >= 0 ? h->field[op.aux].get() : nullptr;
+  a.uabs = h->field[op.uabs].get();
   for (int s = 0; s < 6; ++s) {
-    a.ghost[s] = h->ghost[in_f][s];
+    a.ghost[s] = h->ghost[op.in][s];
     // required for interior launches too: masked boundary lanes still form (and load through) the pointer
     if (h->md.has_nbr[s] && !a.ghost[s])
       return fail(h, SG_ERR_STATE, "stage needs a halo buffer that was not attached (sg_halo_attach)");
@@ -59,7 +65,7 @@ static int stage_args(sg_handle* h, StageArgs& a, int kind, int in_f, int out_f,
   a.sym = h->sym ? 1 : 0;
   a.f32 = h->f32;
   const SpongeTables& sp = h->sponge;
-  a.dbg = h->dbg.get() ? h->dbg.get() + 8 * (kind * 2 + (mode ? 1 : 0)) : nullptr;
+  a.dbg = h->dbg.get() ? h->dbg.get() + 8 * (kind * 2 + (op.mode ? 1 : 0)) : nullptr;
   a.sponge_slot = (kind == 0) ? sp.slot.get() : nullptr;
   a.sponge_B = sp.B.get();
   a.sponge_sigma = (kind == 0) ? sp.sigma.get() : nullptr;
@@ -69,28 +75,23 @@ static int stage_args(sg_handle* h, StageArgs& a, int kind, int in_f, int out_f,
   a.lam0 = h->lam0;
   a.mu0 = h->mu0;
   a.per_cell = h->per_cell;
-  a.rho2 = (kind == 0 && mode == 1 && density) ? h->rho2_d.get() : nullptr;   // stage U1 only
-  a.src_coef = src_coef;
-  a.mode = mode;
-  a.c_self = c_self;
-  a.c_aux = c_aux;
-  a.c_new = c_new;
-  if (kind == 0 && in_f == SG_FIELD_S && mode == 0 && h->capture_src && h->src.fused) {
+  a.rho2 = op.density ? h->rho2_d.get() : nullptr;   // stage U1 only
+  a.src_coef = op.src_coef;
+  a.mode = op.mode;
+  a.c_self = op.c_self;
+  a.c_aux = op.c_aux;
+  a.c_new = op.c_new;
+  if (kind == 0 && op.in == SG_FIELD_S && op.mode == 0 && h->capture_src && h->src.fused) {
     // stage UH1 of a captured step on the tile path: the launch that opens the step also names it
     a.src_step = source_stepper(h);
     a.src_bump = 1;
   }
-  if (with_source && h->src.fused && h->capture_src) {     // ... of the step the device-side counter names
+  if (op.with_source && h->src.fused && source_due(h)) {   // tile path: the G kernel adds the source values
     a.src_slot = h->src.slot.get();
     a.src_idx = h->src.idx.get();
-    a.src_vals = h->src.values.get();
-    a.src_scale = 1.0;
-    a.src_step = source_stepper(h);
-  } else if (with_source && h->src.fused && source_active(h)) {  // tile path: the G kernel adds this step's source values
-    a.src_slot = h->src.slot.get();
-    a.src_idx = h->src.idx.get();
-    a.src_vals = h->src.values.get() + (size_t)(source_one_slice(h) ? 0 : h->src_step) * h->src.nnz * h->cfg.dim * h->cfg.dim;
+    a.src_vals = source_values(h);
     a.src_scale = source_scale(h);
+    a.src_step = source_stepper(h);
   }
   return SG_OK;
 }
@@ -98,10 +99,10 @@ static int stage_args(sg_handle* h, StageArgs& a, int kind, int in_f, int out_f,
 // The sponge pre-pass of an F stage (SpongeTables::pre): B_e u_abs of the sponge cells, queued before anything of the stage
 // writes, at the first launch of the stage - whichever region the caller starts with: the same stage again, or a region it
 // has already seen, is the next instance of the stage - unless the buffer already holds it.  A naming pass changes nothing.
-static int sponge_pre_pass(sg_handle* h, int kind, int out_f, int mode, int region, int uabs_f) {
+static int sponge_pre_pass(sg_handle* h, const StageOp& op, int region) {
   SpongeTables& sp = h->sponge;
-  if (kind != 0 || !sp.pre.get() || h->name_out) return SG_OK;
-  const int key = out_f * 4 + mode;
+  if (op.kind != 0 || !sp.pre.get() || h->name_out) return SG_OK;
+  const int key = op.out * 4 + op.mode, uabs_f = op.uabs;
   bool first_of_stage = key != sp.pre_key || (sp.pre_regions & (1 << region)) != 0 || region == SG_REGION_ALL;
   if (first_of_stage) sp.pre_regions = 0;
   sp.pre_key = key;
@@ -221,23 +222,11 @@ static int launch_region(sg_handle* h, int kind, int region, StageArgs& a) {
   return launch_family(h, kind, a);
 }
 
-static int run_op(sg_handle* h, int kind, int in_f, int out_f, int aux_f, int mode, double c_self, double c_aux,
-                  double c_new, int region, int uabs_f = SG_FIELD_U, bool with_source = false, bool density = false,
-                  double src_coef = 1.0) {
-  StageArgs a;
-  if (int rc = stage_args(h, a, kind, in_f, out_f, aux_f, mode, c_self, c_aux, c_new, region, uabs_f, with_source, density, src_coef))
-    return rc;
-  if (int rc = sponge_pre_pass(h, kind, out_f, mode, region, uabs_f)) return rc;
-  if (!h->name_out) mark_field_written(h, out_f);     // (after the pre-pass decision: an in-place stage absorbs the state it overwrites)
-  return launch_region(h, kind, region, a);
-}
-
 // the source lives on single nodes: added to each part of a split stage right after the launch
 // that wrote it (INTERIOR + BOUNDARY: all of it after the second launch)
-static int add_source(sg_handle* h, int field, double coef, int region = SG_REGION_ALL) {
-  if (h->src.fused || h->name_out) return SG_OK;  // added by the stage kernel (run_op with_source) / a naming pass launches nothing
-  if (h->src.nnz == 0 || region == SG_REGION_INTERIOR) return SG_OK;
-  if (!h->capture_src && !h->src.is_static && h->src_step >= h->src.nsteps) return SG_OK;
+static int add_source(sg_handle* h, int field, double coef, int region) {
+  if (h->src.fused || h->name_out) return SG_OK;  // added by the stage kernel (stage_args) / a naming pass launches nothing
+  if (!source_due(h) || region == SG_REGION_INTERIOR) return SG_OK;
   const int d = h->cfg.dim;
   int64_t off = 0, cnt = h->src.nnz;
   if (region == SG_REGION_FIRST) cnt = h->src.nfirst;
@@ -246,50 +235,24 @@ static int add_source(sg_handle* h, int field, double coef, int region = SG_REGI
     cnt = h->src.nnz - h->src.nfirst;
   }
   if (cnt == 0) return SG_OK;
-  const SrcStep ss = source_stepper(h);
-  const double* vals = h->src.values.get() + ((size_t)((source_one_slice(h) || ss.ctr) ? 0 : h->src_step) * h->src.nnz + off) * d * d;
-  int rc = launch_source(h->field[field].get(), d * d, h->md.gw, cnt, h->src.nodes.get() + off, vals, coef, ss.ctr ? 1.0 : source_scale(h), ss,
-                         h->f32, h->stream);
-  if (rc != 0) return fail(h, SG_ERR_DEVICE, "source kernel launch failed");
-  return SG_OK;
+  int rc = launch_source(h->field[field].get(), d * d, h->md.gw, cnt, h->src.nodes.get() + off, source_values(h) + off * d * d, coef,
+                         source_scale(h), source_stepper(h), h->f32, h->stream);
+  return rc != 0 ? fail(h, SG_ERR_DEVICE, "source kernel launch failed") : SG_OK;
+}
+
+// Everything one stage launch queues, in this order: the sponge pre-pass, the region's kernels, and the source of a G
+// stage that has one - inside those kernels (2-D tile family, stage_args) or by add_source: chosen here, for every caller.
+static int run_op(sg_handle* h, const StageOp& op, int region) {
+  StageArgs a;
+  if (int rc = stage_args(h, a, op, region)) return rc;
+  if (int rc = sponge_pre_pass(h, op, region)) return rc;
+  if (!h->name_out) mark_field_written(h, op.out);     // (after the pre-pass decision: an in-place stage absorbs the state it overwrites)
+  if (int rc = launch_region(h, op.kind, region, a)) return rc;
+  return op.with_source ? add_source(h, op.out, op.src_coef, region) : SG_OK;
 }
 
 static int run_stage_impl(sg_handle* h, int stage, int region) {
-  const double dt = h->dt, c3 = dt * dt * dt / 24.0;
-  int rc = SG_OK;
-  switch (stage) {
-    case SG_STAGE_UH1:
-      return run_op(h, 0, SG_FIELD_S, SG_FIELD_UH, -1, 0, 0, 0, 0, region);
-    case SG_STAGE_STEMP:
-      rc = run_op(h, 1, SG_FIELD_UH, SG_FIELD_SH, -1, 0, 0, 0, 0, region, SG_FIELD_U, true);
-      if (rc == SG_OK) rc = add_source(h, SG_FIELD_SH, 1.0, region);
-      return rc;
-    case SG_STAGE_U1:
-      // explicit mode keeps only rhs(form_u1): u1 = rho*u0 + dt*uh1 + dt^3/24*uh2 (elastic.py:341-345, :354-356);
-      // sg_set_density(physical = 1): u1 = u0 + (dt*uh1 + dt^3/24*uh2)/rho; per-cell density: factors in rho2
-      if (h->rho2_d.get()) return run_op(h, 0, SG_FIELD_SH, SG_FIELD_U, SG_FIELD_UH, 1, 1.0, dt, c3, region, SG_FIELD_U, false, true);
-      if (h->rho_physical) return run_op(h, 0, SG_FIELD_SH, SG_FIELD_U, SG_FIELD_UH, 1, 1.0, dt / h->rho, c3 / h->rho, region);
-      return run_op(h, 0, SG_FIELD_SH, SG_FIELD_U, SG_FIELD_UH, 1, h->rho, dt, c3, region);
-    case SG_STAGE_SH1:
-      rc = run_op(h, 1, SG_FIELD_U, SG_FIELD_SH, -1, 0, 0, 0, 0, region, SG_FIELD_U, true);
-      if (rc == SG_OK) rc = add_source(h, SG_FIELD_SH, 1.0, region);
-      return rc;
-    case SG_STAGE_UTEMP:
-      // utemp = F(sh1; u1) has one consumer, sh2 = G(utemp) in the stress update s1 = s0 + dt sh1 + dt^3/24 sh2 with
-      // sh1 = G(u1) + S (elastic.py:300-303, :348-352) - and g is LINEAR in the velocity: dt G(u1) + dt^3/24 G(utemp) =
-      // G(dt u1 + dt^3/24 utemp).  So this stage leaves w = dt u1 + dt^3/24 utemp in UH (one more operand in its fused
-      // epilogue, on a stage that waits for the matrix pipe, not for memory) and stage S1 reads w and s0 ONLY: no sh1, no
-      // second right-hand side - 6 of its 21 words per node gone (the halo exchanged after this stage is w's).
-      // (mode 2: the fused form without the self term, out = c_aux aux + c_new rhs; kernel families without an instantiation
-      // of their own run their mode-1 kernels with c_self = 0)
-      return run_op(h, 0, SG_FIELD_SH, SG_FIELD_UH, SG_FIELD_U, 2, 0.0, dt, c3, region);
-    case SG_STAGE_S1:
-      // s1 = s0 + G(w) + (dt + dt^3/24) S   (G stage kernels, fused form: out = c_self out + c_new rhs, no second operand)
-      rc = run_op(h, 1, SG_FIELD_UH, SG_FIELD_S, -1, 1, 1.0, 0.0, 1.0, region, SG_FIELD_U, true, false, dt + c3);
-      if (rc == SG_OK) rc = add_source(h, SG_FIELD_S, dt + c3, region);
-      return rc;
-  }
-  return fail(h, SG_ERR_ARG, "unknown stage");
+  return run_op(h, lf4_stage(stage, h->dt, h->rho, h->rho_physical != 0, h->rho2_d.get() != nullptr), region);
 }
 
 int resolve_timing(sg_handle* h) {
@@ -317,6 +280,16 @@ int resolve_timing(sg_handle* h) {
     }
   }
   h->ev_stage_ids.clear();
+  return SG_OK;
+}
+
+// the wall clock of a stepping call (sg_last_step_ms): from ev0, which the caller recorded, to the end of what is queued
+int finish_step_call(sg_handle* h) {
+  HIPCHECK(h, hipEventRecord(h->ev1, h->stream));
+  HIPCHECK(h, hipEventSynchronize(h->ev1));
+  float ms = 0;
+  HIPCHECK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
+  h->last_ms = ms;
   return SG_OK;
 }
 
@@ -423,22 +396,41 @@ static int record_step(sg_handle* h) {
   return SG_OK;
 }
 
+// The bookkeeping of n finished steps.  Eager stage launches and record_step have counted themselves; replayed steps
+// count here, and what a replay wrote is new to everything that remembers a field state.
+static void steps_done(sg_handle* h, int64_t n, bool replayed) {
+  h->src_step += n;
+  h->counters.steps += n;
+  if (!replayed) return;
+  for (int st = 0; st < 6; ++st) h->counters.launches[st] += n;
+  if (h->rec.nrec > 0) h->rec.steps += n;
+  for (int f = 0; f < 4; ++f) mark_field_written(h, f);
+  h->sponge.pre_ver = ~0ull;
+}
+
 int sg_end_step(sg_handle* h) {
   if (!h) return SG_ERR_ARG;
   HIPCHECK(h, hipSetDevice(h->cfg.device));
   if (int rc = record_step(h)) return rc;
-  h->src_step += 1;
-  h->counters.steps += 1;
+  steps_done(h, 1, false);
   return SG_OK;
 }
 
-// one LF4 step = six launches on the handle's stream (elastic.py:291-304)
-static int enqueue_step(sg_handle* h) {
+// one LF4 step = six whole-block launches on the handle's stream (elastic.py:291-304).  counted: the eager steps of
+// sg_step, which count their launches, through sg_run_stage (an event pair per launch) when timing is on.
+static int run_stages(sg_handle* h, bool counted) {
   for (int st = 0; st < 6; ++st) {
-    int rc = run_stage_impl(h, st, SG_REGION_ALL);
-    if (rc != SG_OK) return rc;
+    const bool timed = counted && h->timing;
+    if (int rc = timed ? sg_run_stage(h, st, SG_REGION_ALL) : run_stage_impl(h, st, SG_REGION_ALL)) return rc;
+    if (counted && !timed) h->counters.launches[st] += 1;
   }
-  // the next step's slice (tile path: stage UH1 bumps the counter itself, run_op)
+  return SG_OK;
+}
+
+// ... and what ends it on the stream; counted = false: a step of a capture
+static int enqueue_step(sg_handle* h, bool counted) {
+  if (int rc = run_stages(h, counted)) return rc;
+  // the next step's slice (tile path: stage UH1 bumps the counter itself, stage_args)
   if (h->capture_src && !h->src.fused && launch_step_counter(h->src_ctr_d.get(), 1, 1, h->stream) != 0)
     return fail(h, SG_ERR_DEVICE, "step counter launch failed");
   return record_step(h);
@@ -448,20 +440,18 @@ static int enqueue_step(sg_handle* h) {
 static hipGraphExec_t capture_steps(sg_handle* h, int steps, bool with_src) {
   hipGraph_t g = nullptr;
   hipGraphExec_t ge = nullptr;
-  {
-    // a dry pass through the launch code (nothing is queued): what a launcher asks the runtime once per kernel
-    // instantiation - the resident blocks of the 2-D tile kernels - is asked here, outside the capture
-    std::string name;
-    h->name_out = &name;
-    for (int st = 0; st < 6; ++st) (void)run_stage_impl(h, st, SG_REGION_ALL);
-    h->name_out = nullptr;
-  }
+  // a dry pass through the launch code (nothing is queued): what a launcher asks the runtime once per kernel
+  // instantiation - the resident blocks of the 2-D tile kernels - is asked here, outside the capture
+  std::string name;
+  h->name_out = &name;
+  (void)run_stages(h, false);
+  h->name_out = nullptr;
   if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return nullptr;
   int rc = SG_OK;
   h->capture_src = with_src;
   h->capture_rec = h->rec.nrec > 0;
   h->sponge.pre_ver = ~0ull;      // a replay starts from whatever the buffer holds: the captured step computes its own
-  for (int k = 0; k < steps && rc == SG_OK; ++k) rc = enqueue_step(h);
+  for (int k = 0; k < steps && rc == SG_OK; ++k) rc = enqueue_step(h, false);
   h->sponge.pre_ver = ~0ull;      // nothing was launched: the buffer holds what it held
   h->capture_src = false;
   h->capture_rec = false;
@@ -474,14 +464,58 @@ static hipGraphExec_t capture_steps(sg_handle* h, int steps, bool with_src) {
   return ge;
 }
 
+// the receivers' samples of all nsteps steps must fit the trace: checked before anything is queued (native exchange too)
+static int check_receiver_room(sg_handle* h, int64_t nsteps) {
+  const ReceiverTables& rt = h->rec;
+  if (rt.nrec == 0 || (rt.steps + nsteps) / rt.every <= rt.capacity) return SG_OK;
+  return fail(h, SG_ERR_STATE, "sg_step: the receiver trace has room for " + std::to_string(rt.capacity - rt.samples()) +
+                                   " more samples, these steps take " + std::to_string((rt.steps + nsteps) / rt.every - rt.samples()));
+}
+
+// The graphs of one and of eight steps, captured again when a setter changed kernel arguments (epoch) or the source or the
+// receivers came or went.  A source that is still active is part of them: its launches take the step's slice and weight from
+// a device-side counter (kernels.hpp SrcStep); one that has run out, or none: no source launches.  Armed receivers likewise.
+static int ensure_graphs(sg_handle* h) {
+  const bool with_src = source_active(h), with_rec = h->rec.nrec > 0;
+  if (with_src && !h->src_ctr_d.get()) return fail(h, SG_ERR_STATE, "source without a device-side step counter");
+  if (h->graph_epoch == h->epoch && h->graph_src == with_src && h->graph_rec == with_rec) return SG_OK;
+  if (h->graph1) (void)hipGraphExecDestroy(h->graph1);
+  if (h->graph8) (void)hipGraphExecDestroy(h->graph8);
+  h->graph1 = capture_steps(h, 1, with_src);
+  h->graph8 = h->graph1 ? capture_steps(h, 8, with_src) : nullptr;
+  h->graph_epoch = h->epoch;
+  h->graph_src = with_src;
+  h->graph_rec = with_rec;
+  if (!h->graph1 || !h->graph8) h->graph_ok = false;  // same kernels, launched one by one (eager_steps)
+  return SG_OK;
+}
+
+// nsteps steps as graph replays; the device-side counters start from the step the replay starts from
+static int replay_steps(sg_handle* h, int64_t nsteps) {
+  // (tile path: the counter is bumped by the launch that OPENS a step, so it starts one short)
+  if (h->graph_src && launch_step_counter(h->src_ctr_d.get(), h->src_step - (h->src.fused ? 1 : 0), 0, h->stream) != 0)
+    return fail(h, SG_ERR_DEVICE, "step counter launch failed");
+  if (h->rec.nown > 0 && launch_step_counter(h->rec.ctr.get(), h->rec.steps, 0, h->stream) != 0)
+    return fail(h, SG_ERR_DEVICE, "step counter launch failed");
+  int64_t k = 0;
+  for (; k + 8 <= nsteps; k += 8) HIPCHECK(h, hipGraphLaunch(h->graph8, h->stream));
+  for (; k < nsteps; ++k) HIPCHECK(h, hipGraphLaunch(h->graph1, h->stream));
+  steps_done(h, nsteps, true);
+  return SG_OK;
+}
+
+static int eager_steps(sg_handle* h, int64_t nsteps) {
+  for (int64_t k = 0; k < nsteps; ++k) {
+    if (int rc = enqueue_step(h, true)) return rc;
+    steps_done(h, 1, false);
+  }
+  return SG_OK;
+}
+
 int sg_step(sg_handle* h, int64_t nsteps) {
   if (!h || nsteps < 0) return SG_ERR_ARG;
   if (!h->params_set) return fail(h, SG_ERR_STATE, "sg_set_params must be called before stepping");
-  // the receivers' samples of all nsteps steps must fit the trace: checked before anything is queued (native exchange too)
-  if (h->rec.nrec > 0 && (h->rec.steps + nsteps) / h->rec.every > h->rec.capacity)
-    return fail(h, SG_ERR_STATE, "sg_step: the receiver trace has room for " + std::to_string(h->rec.capacity - h->rec.samples()) +
-                                     " more samples, these steps take " +
-                                     std::to_string((h->rec.steps + nsteps) / h->rec.every - h->rec.samples()));
+  if (int rc = check_receiver_room(h, nsteps)) return rc;
   HIPCHECK(h, hipSetDevice(h->cfg.device));
   for (int s = 0; s < 6; ++s)
     if (h->md.has_nbr[s]) {
@@ -489,64 +523,13 @@ int sg_step(sg_handle* h, int64_t nsteps) {
       return fail(h, SG_ERR_STATE, "sg_step on a block with neighbours: attach a communicator (sg_comm_init) or drive "
                                    "stages + halo from the host");
     }
-  int64_t k = 0;
-  // launch-bound blocks: replay captured graphs (no per-stage timing).  A source that is still active is part of the
-  // graphs: its launches take this step's slice and weight from a device-side step counter (kernels.hpp SrcStep),
-  // set here to the step the replay starts from; one that has run out (or none) gives graphs without source launches.
+  // launch-bound blocks: replay captured graphs (no per-stage timing)
   const bool graphs = h->graph_ok && !h->timing && nsteps >= 2;
-  const bool with_src = source_active(h) && h->src_ctr_d.get() != nullptr;
-  if (graphs && source_active(h) && !with_src) return fail(h, SG_ERR_STATE, "source without a device-side step counter");
-  // armed receivers are part of the graphs too: the recorder takes its step from rec.ctr, set here like the source's
-  const bool with_rec = h->rec.nrec > 0;
-  if (graphs && (h->graph_epoch != h->epoch || h->graph_src != with_src || h->graph_rec != with_rec)) {
-    if (h->graph1) (void)hipGraphExecDestroy(h->graph1);
-    if (h->graph8) (void)hipGraphExecDestroy(h->graph8);
-    h->graph1 = capture_steps(h, 1, with_src);
-    h->graph8 = h->graph1 ? capture_steps(h, 8, with_src) : nullptr;
-    h->graph_epoch = h->epoch;
-    h->graph_src = with_src;
-    h->graph_rec = with_rec;
-    if (!h->graph1 || !h->graph8) h->graph_ok = false;  // same kernels, launched one by one below
-  }
+  if (graphs)
+    if (int rc = ensure_graphs(h)) return rc;
   HIPCHECK(h, hipEventRecord(h->ev0, h->stream));
-  if (graphs && h->graph_ok) {
-    // (tile path: the counter is bumped by the launch that OPENS a step, so it starts one short)
-    if (with_src && launch_step_counter(h->src_ctr_d.get(), h->src_step - (h->src.fused ? 1 : 0), 0, h->stream) != 0)
-      return fail(h, SG_ERR_DEVICE, "step counter launch failed");
-    if (h->rec.nown > 0 && launch_step_counter(h->rec.ctr.get(), h->rec.steps, 0, h->stream) != 0)
-      return fail(h, SG_ERR_DEVICE, "step counter launch failed");
-    for (; k + 8 <= nsteps; k += 8) HIPCHECK(h, hipGraphLaunch(h->graph8, h->stream));
-    for (; k < nsteps; ++k) HIPCHECK(h, hipGraphLaunch(h->graph1, h->stream));
-    for (int st = 0; st < 6; ++st) h->counters.launches[st] += nsteps;
-    h->counters.steps += nsteps;
-    h->src_step += nsteps;
-    if (with_rec) h->rec.steps += nsteps;
-    if (nsteps > 0) {
-      for (int f = 0; f < 4; ++f) mark_field_written(h, f);
-      h->sponge.pre_ver = ~0ull;
-    }
-  }
-  for (; k < nsteps; ++k) {
-    for (int st = 0; st < 6; ++st) {
-      if (h->timing) {
-        int rc = sg_run_stage(h, st, SG_REGION_ALL);
-        if (rc != SG_OK) return rc;
-      } else {
-        int rc = run_stage_impl(h, st, SG_REGION_ALL);
-        if (rc != SG_OK) return rc;
-        h->counters.launches[st] += 1;
-      }
-    }
-    if (int rc = record_step(h)) return rc;
-    h->src_step += 1;
-    h->counters.steps += 1;
-  }
-  HIPCHECK(h, hipEventRecord(h->ev1, h->stream));
-  HIPCHECK(h, hipEventSynchronize(h->ev1));
-  float ms = 0;
-  HIPCHECK(h, hipEventElapsedTime(&ms, h->ev0, h->ev1));
-  h->last_ms = ms;
-  return SG_OK;
+  if (int rc = (graphs && h->graph_ok) ? replay_steps(h, nsteps) : eager_steps(h, nsteps)) return rc;
+  return finish_step_call(h);
 }
 
 int sg_last_step_ms(sg_handle* h, double* ms) {
@@ -560,7 +543,7 @@ int sg_apply_F(sg_handle* h, int s_in, int u_abs, int u_out) {
   if (!field_is_stress(s_in) || field_is_stress(u_out) || field_is_stress(u_abs) || u_abs == u_out)
     return fail(h, SG_ERR_ARG, "sg_apply_F: s_in must be a stress field, u_abs/u_out distinct velocity fields");
   HIPCHECK(h, hipSetDevice(h->cfg.device));
-  return run_op(h, 0, s_in, u_out, -1, 0, 0, 0, 0, SG_REGION_ALL, u_abs);
+  return run_op(h, StageOp{0, s_in, u_out, -1, u_abs}, SG_REGION_ALL);
 }
 
 int sg_apply_G(sg_handle* h, int u_in, int s_out, int use_source) {
@@ -569,9 +552,9 @@ int sg_apply_G(sg_handle* h, int u_in, int s_out, int use_source) {
     return fail(h, SG_ERR_ARG, "sg_apply_G: u_in must be a velocity field, s_out a stress field");
   if (!h->params_set) return fail(h, SG_ERR_STATE, "sg_set_params must be called first");
   HIPCHECK(h, hipSetDevice(h->cfg.device));
-  int rc = run_op(h, 1, u_in, s_out, -1, 0, 0, 0, 0, SG_REGION_ALL, SG_FIELD_U, use_source != 0);
-  if (rc == SG_OK && use_source) rc = add_source(h, s_out, 1.0);
-  return rc;
+  StageOp op{1, u_in, s_out};
+  op.with_source = use_source != 0;
+  return run_op(h, op, SG_REGION_ALL);
 }
 
 // ---- halo ---------------------------------------------------------------------------------

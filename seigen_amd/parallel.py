@@ -22,7 +22,8 @@ import sys
 
 from . import _lib
 
-# input field of each fused stage (include/seigen_hip.h, enum sg_stage)
+# input field of each fused stage (include/seigen_hip.h, enum sg_stage): the library states it in lf4_stage
+# (seigen_amd/csrc/hostlogic.hpp); tests/test_host_logic.py holds the two statements together
 STAGE_INPUT = {
     _lib.STAGE_UH1: _lib.FIELD_S,
     _lib.STAGE_STEMP: _lib.FIELD_UH,

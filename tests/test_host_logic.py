@@ -586,6 +586,22 @@ def test_expression_evaluate_times_equals_per_step_evaluation():
                 assert np.array_equal(V[k], e.evaluate(X))
 
 
+def test_stage_fields_of_the_library_and_of_the_host_driven_exchanger_agree():
+    """Which field a stage reads and writes is stated once in the library (hostlogic.hpp lf4_stage: the stage launches
+    and the native exchange take it from there) and once in seigen_amd/parallel.py (STAGE_INPUT / STAGE_OUTPUT, the
+    host-driven exchanger).  The sanitizer driver prints the library's statement, one `stage k: in out` line per stage."""
+    import subprocess
+    from seigen_amd import parallel
+    r = subprocess.run(["make", "-C", os.path.join(ROOT, "seigen_amd", "csrc"), "host-asan"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    r = subprocess.run([os.path.join(ROOT, "build_tools", "host_asan_driver")], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    rows = {int(k): (int(i), int(o)) for k, i, o in re.findall(r"^stage (\d+): (\d+) (\d+)$", r.stdout, flags=re.M)}
+    assert sorted(rows) == list(range(6)), r.stdout
+    assert {k: v[0] for k, v in rows.items()} == parallel.STAGE_INPUT
+    assert {k: v[1] for k, v in rows.items()} == parallel.STAGE_OUTPUT
+
+
 def test_second_region_is_never_empty_for_the_shipped_multi_rank_configurations():
     """The launch that runs beside the halo exchange (SG_REGION_SECOND) must have cubes to work on for every block of
     the process grids the multi-rank configurations use (advisor finding of round 3: a group-thick x shell on both

@@ -86,7 +86,7 @@ def _fact(dtype, P, gq):
 
 
 def _stage_names(dtype, P, sym, fact, ghost=0):
-    """the instantiation each of the six stages launches (stages.cpp run_stage_impl)"""
+    """the instantiation each of the six stages launches (hostlogic.hpp lf4_stage)"""
     return [_f_name(dtype, P, 0, sym, ghost), _g_name(dtype, P, 0, sym, fact), _f_name(dtype, P, 1, sym, ghost),
             _g_name(dtype, P, 0, sym, fact), _f_name(dtype, P, 2, sym, ghost), _g_name(dtype, P, 1, sym, fact)]
 

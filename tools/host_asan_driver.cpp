@@ -446,6 +446,40 @@ static void sponge_plans(int dim, int degree, int kind, int q) {
   }
 }
 
+// The six launches of an LF4 step (hostlogic.hpp lf4_stage) against the rows written out here, for two (dt, rho) and the
+// three density conventions of stage U1; every stage reads what the stage before it wrote, cyclically over the step.
+// The printed lines are what tests/test_host_logic.py compares with seigen_amd/parallel.py STAGE_INPUT / STAGE_OUTPUT.
+static void stage_table() {
+  const int U = SG_FIELD_U, UH = SG_FIELD_UH, S = SG_FIELD_S, SH = SG_FIELD_SH;
+  const double pairs[2][2] = {{1e-3, 1.0}, {0.25, 2.5}};
+  for (const auto& p : pairs)
+    for (int conv = 0; conv < 3; ++conv) {   // 0: rho u0 + ..., 1: u0 + (...) / rho (physical), 2: per-cell factors
+      const double dt = p[0], rho = p[1], c3 = dt * dt * dt / 24.0;
+      const double u_self = conv == 0 ? rho : 1.0, u_div = conv == 1 ? rho : 1.0;
+      const StageOp want[6] = {
+          // kind in out aux uabs mode c_self c_aux c_new with_source src_coef density
+          {0, S, UH, -1, U, 0, 0.0, 0.0, 0.0, false, 1.0, false},
+          {1, UH, SH, -1, U, 0, 0.0, 0.0, 0.0, true, 1.0, false},
+          {0, SH, U, UH, U, 1, u_self, dt / u_div, c3 / u_div, false, 1.0, conv == 2},
+          {1, U, SH, -1, U, 0, 0.0, 0.0, 0.0, true, 1.0, false},
+          {0, SH, UH, U, U, 2, 0.0, dt, c3, false, 1.0, false},
+          {1, UH, S, -1, U, 1, 1.0, 0.0, 1.0, true, dt + c3, false},
+      };
+      for (int k = 0; k < 6; ++k) {
+        // (per-cell density wins over the physical flag, as the handle's rho2 table does)
+        const StageOp got = lf4_stage(k, dt, rho, conv == 1, conv == 2), &w = want[k];
+        EXPECT(got.kind == w.kind && got.in == w.in && got.out == w.out && got.aux == w.aux && got.uabs == w.uabs);
+        EXPECT(got.mode == w.mode && got.c_self == w.c_self && got.c_aux == w.c_aux && got.c_new == w.c_new);
+        EXPECT(got.with_source == w.with_source && got.src_coef == w.src_coef && got.density == w.density);
+        EXPECT(lf4_stage_input(k) == w.in && lf4_stage_output(k) == w.out);
+        EXPECT(lf4_stage_output(k) == lf4_stage_input((k + 1) % 6));
+      }
+    }
+  EXPECT(lf4_stage(2, 0.25, 2.5, true, true).density && lf4_stage(2, 0.25, 2.5, true, true).c_aux == 0.25);
+  EXPECT(lf4_stage(6, 1e-3, 1.0, false, false).kind == -1 && lf4_stage(-1, 1e-3, 1.0, false, false).kind == -1);
+  for (int k = 0; k < 6; ++k) std::printf("stage %d: %d %d\n", k, lf4_stage_input(k), lf4_stage_output(k));
+}
+
 int main() {
   for (int cell_type : {0, 1})
     for (int dim = 1; dim <= 3; ++dim)
@@ -470,6 +504,7 @@ int main() {
   regions_and_coords();
   point_location();
   kernel_family_table();
+  stage_table();
   for (int dim = 1; dim <= 3; ++dim)
     for (int degree : {1, 2, 4})
       for (int kind : {KIND_SIMPLEX, KIND_TENSOR}) {
