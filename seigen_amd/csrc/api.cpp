@@ -3,9 +3,9 @@
 // the fused six-launch LF4 step (seigen/elastic.py:283-313) and halo packs: stages.cpp.
 #include <limits>
 #include <string>
-#include <unordered_map>
 
 #include "handle.hpp"
+#include "source_tables.hpp"
 #include "sponge_tables.hpp"
 
 // the configuration, the reference element and the mesh tables
@@ -541,127 +541,51 @@ int sg_set_absorption(sg_handle* h, const double* sigma_nodes, int sigma_degree)
 }
 
 // sg_set_source and sg_set_source_separable: nsteps slices of values (-1: one that holds at every step), or - weights
-// given - one slice scaled by weights[k] at step k < nsteps
+// given - one slice scaled by weights[k] at step k < nsteps.  Which nodes are merged, their order (SG_REGION_FIRST first),
+// their device offsets, the fused table of the 2-D tile family and whether the values are symmetric is decided by
+// plan_source (source_tables.cpp: plain C++, under the CPU sanitizers); this function uploads the plan and puts it in place.
 static int set_source(sg_handle* h, int64_t nnz, const int64_t* nodes, int64_t nsteps, const double* values, const double* weights) {
   HIPCHECK(h, hipSetDevice(h->cfg.device));
   SourceTables src;
   if (nnz != 0 && nsteps != 0) {
     if (!nodes || !values || nsteps < -1) return SG_ERR_ARG;
-    const int d = h->cfg.dim;
-    src.is_static = nsteps == -1;
-    src.nsteps = src.is_static ? 1 : nsteps;
-    const int64_t nslices = weights ? 1 : src.nsteps;
-    int64_t nscalar = h->ncells * h->re.nd;
-    for (int64_t k = 0; k < nnz; ++k)
-      if (nodes[k] < 0 || nodes[k] >= nscalar) return fail(h, SG_ERR_ARG, "sg_set_source: node index out of range");
-    // A node listed more than once: its entries add up (in the order listed), merged here once so that every node is
-    // written by one thread - the sum is then the same on every run and on every partition of the mesh (an atomic add
-    // per entry gave the right sum in an arbitrary order, i.e. results that differed in the last bit from run to run).
-    std::vector<int64_t> merged_nodes;
-    std::vector<double> merged_values;
-    {
-      std::unordered_map<int64_t, int64_t> slot_of;
-      slot_of.reserve((size_t)nnz * 2);
-      std::vector<int64_t> to((size_t)nnz);
-      for (int64_t k = 0; k < nnz; ++k) {
-        auto it = slot_of.find(nodes[k]);
-        if (it == slot_of.end()) {
-          it = slot_of.emplace(nodes[k], (int64_t)merged_nodes.size()).first;
-          merged_nodes.push_back(nodes[k]);
-        }
-        to[(size_t)k] = it->second;
-      }
-      if ((int64_t)merged_nodes.size() != nnz) {
-        const int64_t nm = (int64_t)merged_nodes.size(), dd = (int64_t)d * d;
-        merged_values.assign((size_t)(nslices * nm * dd), 0.0);
-        for (int64_t s = 0; s < nslices; ++s)
-          for (int64_t k = 0; k < nnz; ++k)
-            for (int64_t c = 0; c < dd; ++c) merged_values[(size_t)((s * nm + to[(size_t)k]) * dd + c)] += values[(s * nnz + k) * dd + c];
-        nodes = merged_nodes.data();
-        values = merged_values.data();
-        nnz = nm;
-      }
+    SourceRequest rq;
+    rq.dim = h->cfg.dim;
+    rq.L = layout(h);
+    rq.ncells = h->ncells;
+    rq.ncube_pad = h->md.ncube_pad;
+    std::copy_n(h->cfg.n, 3, rq.n);
+    region_boxes(h, SG_REGION_FIRST, rq.first);
+    rq.want_fused = family_fused_source(h->family) && !std::getenv("SEIGEN_HIP_SOURCE_LAUNCH");
+    rq.sym = h->sym;
+    SourcePlan pl;
+    try {
+      pl = plan_source(rq, nnz, nodes, nsteps, values, weights);
+    } catch (const std::exception& e) {
+      return fail(h, SG_ERR_ARG, std::string("sg_set_source: ") + e.what());
     }
-    src.nnz = nnz;
-    // Order the nodes so that those in cells of SG_REGION_FIRST come first: a split stage adds the
-    // source to each part right after the launch that wrote it (the traces of FIRST are packed
-    // before SECOND has run).  Then: device offset of component 0 of each node in the field layout.
-    std::vector<int64_t> order((size_t)nnz), offs((size_t)nnz);
-    {
-      const int64_t nd = h->re.nd, ncls = h->ncls, gw = h->md.gw, nc = (int64_t)d * d;
-      std::vector<Box> first;
-      region_boxes(h, SG_REGION_FIRST, first);
-      auto in_first = [&](int64_t node) {
-        const int64_t cube = node / nd / ncls;
-        const int64_t c[3] = {cube % h->cfg.n[0], (cube / h->cfg.n[0]) % h->cfg.n[1], cube / ((int64_t)h->cfg.n[0] * h->cfg.n[1])};
-        for (const Box& b : first) {
-          bool in = true;
-          for (int k = 0; k < 3; ++k) in = in && c[k] >= b.o[k] && c[k] < b.o[k] + b.n[k];
-          if (in) return true;
-        }
-        return false;
-      };
-      int64_t n1 = 0;
-      for (int64_t i = 0; i < nnz; ++i)
-        if (in_first(nodes[i])) order[(size_t)n1++] = i;
-      src.nfirst = n1;
-      for (int64_t i = 0; i < nnz; ++i)
-        if (!in_first(nodes[i])) order[(size_t)n1++] = i;
-      for (int64_t j = 0; j < nnz; ++j) {
-        const int64_t node = nodes[order[(size_t)j]];
-        int64_t e = node / nd, b = node % nd;
-        int64_t cube = e / ncls, cls = e % ncls;
-        offs[(size_t)j] = ((((cube / gw) * ncls + cls) * nd + b) * nc) * gw + cube % gw;
-      }
-    }
-    std::vector<double> vals((size_t)nslices * nnz * d * d);
-    for (int64_t k = 0; k < nslices; ++k)
-      for (int64_t j = 0; j < nnz; ++j)
-        std::memcpy(&vals[((size_t)k * nnz + j) * d * d], &values[((size_t)k * nnz + order[(size_t)j]) * d * d], sizeof(double) * d * d);
-    HIPCHECK(h, src.nodes.upload(offs.data(), offs.size()));
-    HIPCHECK(h, src.values.upload(vals.data(), vals.size()));
+    src.nnz = pl.nnz;
+    src.nfirst = pl.nfirst;
+    src.is_static = pl.is_static;
+    src.nsteps = pl.nsteps;
+    HIPCHECK(h, src.nodes.upload(pl.offs.data(), pl.offs.size()));
+    HIPCHECK(h, src.values.upload(pl.vals.data(), pl.vals.size()));
     if (weights) {
-      src.weights.assign(weights, weights + nsteps);
-      HIPCHECK(h, src.weights_d.upload(weights, (size_t)nsteps));
+      HIPCHECK(h, src.weights_d.upload(pl.weights.data(), pl.weights.size()));
+      src.weights = std::move(pl.weights);
     }
-    if (family_fused_source(h->family) && !std::getenv("SEIGEN_HIP_SOURCE_LAUNCH")) {
-      // tile kernels: item (16 squares of one class) -> slot, and per slot a dense (node, cell) -> value-row table, so
-      // that the G stages add the source themselves (one launch less per G stage).  (Nodes are unique here: entries of a
-      // node listed twice were merged above.)
-      const int64_t nd = h->re.nd, ncl = h->ncls, nitems = h->md.ncube_pad / 16 * ncl;
-      std::vector<int32_t> slot((size_t)nitems, -1), idx;
-      bool dup = false;
-      for (int64_t j = 0; j < nnz && !dup; ++j) {
-        const int64_t node = nodes[order[(size_t)j]];
-        const int64_t e = node / nd, b = node % nd, cube = e / ncl, cls = e % ncl;
-        const int64_t item = (cube / 16) * ncl + cls;
-        if (slot[(size_t)item] < 0) {
-          slot[(size_t)item] = (int32_t)(idx.size() / (size_t)(nd * 16));
-          idx.resize(idx.size() + (size_t)(nd * 16), -1);
-        }
-        int32_t& cell = idx[((size_t)slot[(size_t)item] * nd + b) * 16 + cube % 16];
-        dup = cell >= 0;
-        cell = (int32_t)j;
-      }
-      if (!dup) {
-        HIPCHECK(h, src.slot.upload(slot.data(), slot.size()));
-        HIPCHECK(h, src.idx.upload(idx.data(), idx.size()));
-        src.fused = true;
-      }
+    if (!pl.slot.empty()) {   // the G stage kernels add the source themselves (StageArgs::src_slot / src_idx)
+      HIPCHECK(h, src.slot.upload(pl.slot.data(), pl.slot.size()));
+      HIPCHECK(h, src.idx.upload(pl.idx.data(), pl.idx.size()));
+      src.fused = true;
     }
     if (!h->src_ctr_d.get()) {   // device-side step counter for graph replay (stages.cpp sg_step), kept across sources
       const int64_t zero = 0;
       HIPCHECK(h, h->src_ctr_d.upload(&zero, 1));
     }
-    if (h->sym) {
-      bool symmetric = true;
-      for (int64_t i = 0; i < nslices * nnz && symmetric; ++i)
-        for (int a = 0; a < d; ++a)
-          for (int b = a + 1; b < d; ++b) symmetric = symmetric && vals[i * d * d + a * d + b] == vals[i * d * d + b * d + a];
-      if (!symmetric) {
-        int rc = leave_sym_mode(h);
-        if (rc != SG_OK) return rc;
-      }
+    if (h->sym && !pl.symmetric) {
+      int rc = leave_sym_mode(h);
+      if (rc != SG_OK) return rc;
     }
   }
   HIPCHECK(h, sync_all(h));
@@ -689,43 +613,22 @@ int sg_set_source_box_ricker(sg_handle* h, const double* lo, const double* hi, d
   const int d = h->cfg.dim;
   NodeGeom G;
   if (!G.init(&h->cfg, h->cfg.degree)) return SG_ERR_ARG;
-  // cubes that can hold a node of the box: those overlapping it (closed on both sides)
-  int c0[3] = {0, 0, 0}, c1[3] = {0, 0, 0};
-  for (int i = 0; i < d; ++i) {
-    if (!(lo[i] <= hi[i])) return fail(h, SG_ERR_ARG, "source box: lo must not exceed hi");
-    const double t0c = std::floor((lo[i] - h->cfg.origin[i]) / h->cfg.h[i]) - (double)h->cfg.cube0[i] - 1.0;
-    const double t1c = std::floor((hi[i] - h->cfg.origin[i]) / h->cfg.h[i]) - (double)h->cfg.cube0[i] + 1.0;
-    c0[i] = (int)std::max(0.0, std::min(t0c, (double)h->cfg.n[i]));
-    c1[i] = (int)std::max(-1.0, std::min(t1c, (double)h->cfg.n[i] - 1.0));
-  }
   std::vector<int64_t> nodes;
-  for (int ck = c0[2]; ck <= c1[2]; ++ck)
-    for (int cj = c0[1]; cj <= c1[1]; ++cj)
-      for (int ci = c0[0]; ci <= c1[0]; ++ci) {
-        const int c[3] = {ci, cj, ck};
-        const int64_t cube = ci + (int64_t)h->cfg.n[0] * (cj + (int64_t)h->cfg.n[1] * ck);
-        for (int k = 0; k < G.ncls; ++k)
-          for (int b = 0; b < G.nq; ++b) {
-            double x[3];
-            G.node(c, k, b, x);
-            bool in = true;
-            for (int i = 0; i < d; ++i) in = in && x[i] >= lo[i] && x[i] <= hi[i];
-            if (in) nodes.push_back((cube * G.ncls + k) * G.nq + b);
-          }
-      }
+  try {
+    nodes = box_nodes(G, lo, hi);
+  } catch (const std::exception& e) {
+    return fail(h, SG_ERR_ARG, std::string("source box: ") + e.what());
+  }
   if (nodes.empty() || nsteps == 0) return sg_set_source(h, 0, nullptr, 0, nullptr);
-  std::vector<double> pattern(nodes.size() * (size_t)d * d, 0.0), w((size_t)nsteps);
+  std::vector<double> pattern(nodes.size() * (size_t)d * d, 0.0);
   for (size_t j = 0; j < nodes.size(); ++j)
     for (int i = 0; i < d; ++i) pattern[(j * d + i) * d + i] = 1.0;
-  for (int64_t k = 0; k < nsteps; ++k) {
-    const double t = t_first + (double)k * dt_step, q = (t - t0) * (t - t0);
-    w[(size_t)k] = (-1.0 + 2.0 * a * q) * std::exp(-a * q);
-  }
+  const std::vector<double> w = ricker_weights(a, t0, t_first, dt_step, nsteps);
   return sg_set_source_separable(h, (int64_t)nodes.size(), nodes.data(), pattern.data(), nsteps, w.data());
 }
 
-// The receivers: located on the host (hostlogic.hpp locate_point, the rule of sg_locate_points), tabulated with the
-// element's basis, uploaded into locals, and moved into the handle once nothing can fail any more.
+// The receivers: located on the host and tabulated with the element's basis (hostlogic.hpp plan_receivers: locate_point,
+// the rule of sg_locate_points), uploaded into locals, and moved into the handle once nothing can fail any more.
 int sg_set_receivers(sg_handle* h, int64_t nrec, const double* pts, int what, int64_t every, int64_t capacity,
                      int32_t* owned) {
   if (!h) return SG_ERR_ARG;
@@ -735,49 +638,36 @@ int sg_set_receivers(sg_handle* h, int64_t nrec, const double* pts, int what, in
   if (nrec > 0 && every < 1) return fail(h, SG_ERR_ARG, "sg_set_receivers: every must be >= 1");
   if (nrec > 0 && capacity < 0) return fail(h, SG_ERR_ARG, "sg_set_receivers: capacity must be >= 0");
   HIPCHECK(h, hipSetDevice(h->cfg.device));
-  const int d = h->cfg.dim, nd = h->re.nd;
   ReceiverTables rt;
-  std::vector<int32_t> own((size_t)nrec, 0);
+  ReceiverPlan pl;
   if (nrec > 0) {
     NodeGeom G;
     if (!G.init(&h->cfg, h->cfg.degree)) return fail(h, SG_ERR_ARG, "sg_set_receivers: cell type");
-    const int64_t gw = h->md.gw;
-    std::vector<int64_t> item;
-    std::vector<int32_t> lane;
-    std::vector<double> phi;
-    for (int64_t k = 0; k < nrec; ++k) {
-      double xi[3] = {0, 0, 0};
-      const int64_t cell = locate_point(G, pts + k * d, xi);
-      if (cell < 0) continue;
-      const int64_t cube = cell / h->ncls, cls = cell % h->ncls;
-      own[(size_t)k] = 1;
-      rt.row.push_back(k);
-      item.push_back((cube / gw) * h->ncls + cls);
-      lane.push_back((int32_t)(cube % gw));
-      phi.resize(phi.size() + (size_t)nd);
-      tabulate(d, h->cfg.degree, 1, xi, phi.data() + phi.size() - nd, h->re.kind);
+    try {
+      pl = plan_receivers(G, layout(h), h->re.kind, nrec, pts, what, capacity);
+    } catch (const std::exception& e) {
+      return fail(h, SG_ERR_ARG, std::string("sg_set_receivers: ") + e.what());
     }
     rt.nrec = nrec;
-    rt.nown = (int64_t)rt.row.size();
+    rt.nown = (int64_t)pl.row.size();
     rt.what = what;
-    rt.ncomp = ((what & 1) ? d : 0) + ((what & 2) ? d * d : 0);
+    rt.ncomp = pl.ncomp;
     rt.every = every;
     rt.capacity = capacity;
-    if (rt.nown > 0 && capacity > ((int64_t)1 << 40) / (rt.nown * rt.ncomp))
-      return fail(h, SG_ERR_ARG, "sg_set_receivers: capacity too large");
     const size_t tlen = (size_t)(capacity * rt.nown * rt.ncomp);
     const int64_t zero = 0;
-    HIPCHECK(h, rt.item.upload(item.data(), item.size()));
-    HIPCHECK(h, rt.lane.upload(lane.data(), lane.size()));
-    HIPCHECK(h, rt.phi.upload(phi.data(), phi.size()));
+    HIPCHECK(h, rt.item.upload(pl.item.data(), pl.item.size()));
+    HIPCHECK(h, rt.lane.upload(pl.lane.data(), pl.lane.size()));
+    HIPCHECK(h, rt.phi.upload(pl.phi.data(), pl.phi.size()));
     if (rt.trace.alloc(tlen) != hipSuccess) return fail(h, SG_ERR_NOMEM, "sg_set_receivers: hipMalloc of the trace failed");
     HIPCHECK(h, hipMemset(rt.trace.get(), 0, std::max<size_t>(tlen, 1) * sizeof(double)));
     HIPCHECK(h, rt.ctr.upload(&zero, 1));
+    rt.row = std::move(pl.row);
   }
   HIPCHECK(h, sync_all(h));
   h->rec = std::move(rt);
   h->epoch += 1;
-  if (owned) std::memcpy(owned, own.data(), own.size() * sizeof(int32_t));
+  if (owned) std::memcpy(owned, pl.own.data(), pl.own.size() * sizeof(int32_t));
   return SG_OK;
 }
 

@@ -1,7 +1,11 @@
 // The handle behind the C-ABI (include/seigen_hip.h) and what its translation units share:
-//   api.cpp      create / destroy, parameters, sponge, source, table exports
+//   api.cpp      create / destroy, parameters, sponge, source, receivers: device checks, uploads, the move into the handle
 //   transfer.cpp host <-> device field transfers (layout conversion, pinned pipeline)
 //   stages.cpp   regions, stage launches, the LF4 step, graphs, halo packs, timing
+// and, without a device or a HIP header (the CPU sanitizer build, `make host-asan`):
+//   hostapi.cpp (hostlogic.hpp)  family choice, field layout, stage table, region boxes / items, point location, receiver plan
+//   sponge_tables.cpp            what sg_set_absorption derives from the nodal sigma
+//   source_tables.cpp            what the source setters derive from the caller's nodes and values
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -111,8 +115,8 @@ struct ReceiverTables {
   int64_t nrec = 0;           // receivers armed (0: none; every block of a mesh is handed all of them)
   int64_t nown = 0;           // ... of which this block owns these, in the order given
   std::vector<int64_t> row;   // [nown] -> receiver index (the row of sg_get_receivers' output)
-  DevBuf<int64_t> item;       // [nown] (cube / gw) * ncls + class of the owning cell: node a, component c of a field with
-  DevBuf<int32_t> lane;       // [nown] cube % gw                  ncomp components at ((item * nd + a) * ncomp + c) * gw + lane
+  DevBuf<int64_t> item;       // [nown] item and
+  DevBuf<int32_t> lane;       // [nown] lane of the owning cell in the layout of the fields (hostlogic.hpp Layout)
   DevBuf<double> phi;         // [nown][nd] basis of the cell at the point
   int what = 0;               // bit 0: velocity (dim values), bit 1: stress (dim x dim, row-major)
   int ncomp = 0;
@@ -262,6 +266,8 @@ inline hipError_t sync_all(sg_handle* h) {
 // transfer.cpp: make the (i > j) lines of both stress buffers valid again and continue with the full-tensor kernels
 int leave_sym_mode(sg_handle* h);
 
+// hostlogic.hpp: the layout of the block's fields
+inline Layout layout(const sg_handle* h) { return Layout{h->md.gw, h->ncls, h->re.nd}; }
 // hostapi.cpp (hostlogic.hpp): the regions of a split stage
 inline void region_boxes(const sg_handle* h, int region, std::vector<Box>& out) {
   region_boxes(h->cfg.dim, h->cfg.n, h->md.has_nbr, region, out,

@@ -1,10 +1,12 @@
 // The device-free part of the C-ABI (include/seigen_hip.h "device-free setup queries") and the host logic behind
-// sg_create that involves no device: kernel-family choice, regions of a split stage, node coordinates, the exports of the
-// reference-element operators and mesh tables.  No HIP header, no HIP call: this file, refelem.cpp, mesh_tables.cpp and
-// mfma_tables.cpp are what `make host-asan` builds with -fsanitize=address,undefined and runs on the CPU.
+// sg_create that involves no device: kernel-family choice, regions of a split stage and their items, node coordinates,
+// point location and the receiver plan, the exports of the reference-element operators and mesh tables.  No HIP header,
+// no HIP call: this file, refelem.cpp, mesh_tables.cpp, mfma_tables.cpp, sponge_tables.cpp and source_tables.cpp are what
+// `make host-asan` builds with -fsanitize=address,undefined and runs on the CPU.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <stdexcept>
 
 #include "hostlogic.hpp"
 
@@ -145,6 +147,25 @@ void region_boxes(int d, const int32_t n[3], const int32_t has_nbr[6], int regio
   }
 }
 
+RegionItems region_items(const std::vector<Box>& boxes, const int32_t n[3], const Layout& L, int64_t ncube, int64_t ncube_pad) {
+  const int64_t ngroups = L.group(ncube_pad);
+  std::vector<int32_t> cnt((size_t)ngroups, 0);
+  for (const Box& b : boxes)
+    for (int ck = b.o[2]; ck < b.o[2] + b.n[2]; ++ck)
+      for (int cj = b.o[1]; cj < b.o[1] + b.n[1]; ++cj)
+        for (int ci = b.o[0]; ci < b.o[0] + b.n[0]; ++ci) cnt[(size_t)L.group(ci + (int64_t)n[0] * (cj + (int64_t)n[1] * ck))] += 1;
+  // Whole groups only (always, on meshes whose rows are a multiple of the group width: a shell in x is one
+  // group thick): the kernels then skip the cube coordinates and the box tests, as in a whole-block launch.
+  // (The boxes of a region are disjoint, so the count of a group tells.)
+  RegionItems r;
+  for (int64_t g = 0; g < ngroups; ++g) {
+    if (cnt[(size_t)g] == 0) continue;
+    if (cnt[(size_t)g] != std::min<int64_t>(L.gw, ncube - g * L.gw)) r.whole = false;
+    for (int64_t k = 0; k < L.ncls; ++k) r.items.push_back((int32_t)(g * L.ncls + k));
+  }
+  return r;
+}
+
 // J xi = r for a dim x dim system, Gaussian elimination with partial pivoting (what np.linalg.solve does in
 // functionspace.py locate); false if J is singular
 static bool solve_small(int d, double J[3][3], double r[3], double xi[3]) {
@@ -234,6 +255,28 @@ int64_t locate_point(const NodeGeom& G, const double* p, double* xi) {
         }
       }
   return -1;
+}
+
+ReceiverPlan plan_receivers(const NodeGeom& G, const Layout& L, int kind, int64_t nrec, const double* pts, int what, int64_t capacity) {
+  const int d = G.d;
+  ReceiverPlan pl;
+  pl.own.assign((size_t)nrec, 0);
+  pl.ncomp = ((what & 1) ? d : 0) + ((what & 2) ? d * d : 0);
+  for (int64_t k = 0; k < nrec; ++k) {
+    double xi[3] = {0, 0, 0};
+    const int64_t cell = locate_point(G, pts + k * d, xi);
+    if (cell < 0) continue;
+    const int64_t cube = cell / L.ncls, cls = cell % L.ncls;
+    pl.own[(size_t)k] = 1;
+    pl.row.push_back(k);
+    pl.item.push_back(L.item(cube, cls));
+    pl.lane.push_back((int32_t)L.lane(cube));
+    pl.phi.resize(pl.phi.size() + (size_t)L.nd);
+    tabulate(d, G.degree, 1, xi, pl.phi.data() + pl.phi.size() - L.nd, kind);
+  }
+  const int64_t nown = (int64_t)pl.row.size();
+  if (nown > 0 && capacity > ((int64_t)1 << 40) / (nown * pl.ncomp)) throw std::invalid_argument("capacity too large");
+  return pl;
 }
 
 extern "C" {

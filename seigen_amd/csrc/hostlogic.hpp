@@ -1,6 +1,7 @@
-// Host logic of libseigen_hip that needs no device and no HIP header: which kernel family runs a block, the six stages
-// of an LF4 step, the boxes of the regions of a split stage, node coordinates of a block.  Defined in hostapi.cpp, which - with refelem.cpp,
-// mesh_tables.cpp and mfma_tables.cpp - also builds on its own for the CPU sanitizer target (`make host-asan`).
+// Host logic of libseigen_hip that needs no device and no HIP header: which kernel family runs a block, the layout of its
+// fields, the six stages of an LF4 step, the boxes and items of the regions of a split stage, node coordinates of a block,
+// point location and the receiver plan.  Defined in hostapi.cpp, which - with refelem.cpp, mesh_tables.cpp, mfma_tables.cpp,
+// sponge_tables.cpp and source_tables.cpp - also builds on its own for the CPU sanitizer target (`make host-asan`).
 #pragma once
 #include <cstdint>
 #include <cstring>
@@ -30,6 +31,25 @@ Family choose_kernel_path(const sg_config& cfg);
 // What the host code asks about a family.  The layout's group width (MeshDev::gw): 16 cubes per 128-byte line for the
 // matrix-pipe families, 64 for the lane kernels, 1 = host layout for the generic kernels.
 inline int family_gw(Family f) { return f == Family::Generic ? 1 : (f == Family::Lane ? 64 : 16); }
+// The interleaved layout of a block's fields, stated here once for the host code (the kernels keep their own arithmetic):
+// gw consecutive cubes - a group - put the cells of one class side by side on the lanes of an ITEM, and node b, component c
+// of a field with ncomp components of cell (cube, cls) lives at
+//   ((((cube / gw) * ncls + cls) * nd + b) * ncomp + c) * gw + cube % gw
+// (gw = 1: the host layout [cell][node][comp]).  The host numbers a scalar node (cube * ncls + cls) * nd + b.
+struct Layout {
+  int64_t gw = 1, ncls = 1, nd = 1;
+  int64_t group(int64_t cube) const { return cube / gw; }   // (of ncube_pad: the number of groups)
+  int64_t lane(int64_t cube) const { return cube % gw; }
+  int64_t item(int64_t cube, int64_t cls) const { return group(cube) * ncls + cls; }
+  int64_t offset(int64_t cube, int64_t cls, int64_t b, int64_t ncomp, int64_t c) const {
+    return ((item(cube, cls) * nd + b) * ncomp + c) * gw + lane(cube);
+  }
+  struct Node {
+    int64_t cube, cls, b;
+  };
+  Node split(int64_t node) const { return {node / nd / ncls, node / nd % ncls, node % nd}; }
+};
+
 // Every family but the generic one: interleaved layout, one launch per region over (cell group, class) items, the
 // symmetric-stress mode, and a sigma that is one value on all nodes of a cell applied as sigma u at the node.
 inline bool family_interleaved(Family f) { return f != Family::Generic; }
@@ -79,6 +99,13 @@ inline int shell_width_x(int gw, int n0, bool nbr_lo, bool nbr_hi) {
   return 2 * (n0 - sides * gw) >= n0 ? gw : 1;
 }
 void region_boxes(int d, const int32_t n[3], const int32_t has_nbr[6], int region, std::vector<Box>& out, int xw);
+// The (cell group, class) items that the boxes of a region touch, ascending, and whether every group they touch is whole
+// (then the kernels skip the cube coordinates and the box tests, as in a whole-block launch).  The boxes are disjoint.
+struct RegionItems {
+  std::vector<int32_t> items;
+  bool whole = true;
+};
+RegionItems region_items(const std::vector<Box>& boxes, const int32_t n[3], const Layout& L, int64_t ncube, int64_t ncube_pad);
 
 // Node coordinates of a block: the affine image of the reference lattice under every cell's vertex map (one
 // arithmetic, shared by sg_block_node_coords and the source box test of sg_set_source_box_ricker).
@@ -125,3 +152,16 @@ struct NodeGeom {
 // wins.  Every block of a partition finds the same winner; the block that holds it owns the point.
 // Returns the block-local cell (xi[dim] its reference coordinates) or -1: another block's, or outside the mesh.
 int64_t locate_point(const NodeGeom& G, const double* p, double* xi);
+
+// What sg_set_receivers derives from the points: of the nrec points pts[nrec][dim] the ones this block owns (own[k] = 1),
+// in the order given - their row of the output, the item and lane of the owning cell (Layout) and the cell's basis at the
+// point.  Throws std::invalid_argument where capacity x owned x ncomp values of trace are more than 2^40.
+struct ReceiverPlan {
+  std::vector<int32_t> own;    // [nrec]
+  std::vector<int64_t> row;    // [nown] -> receiver index
+  std::vector<int64_t> item;   // [nown]
+  std::vector<int32_t> lane;   // [nown]
+  std::vector<double> phi;     // [nown][nd]
+  int ncomp = 0;               // what bit 0: velocity (dim values), bit 1: stress (dim x dim)
+};
+ReceiverPlan plan_receivers(const NodeGeom& G, const Layout& L, int kind, int64_t nrec, const double* pts, int what, int64_t capacity);

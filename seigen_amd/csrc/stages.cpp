@@ -132,34 +132,14 @@ static int sponge_pre_pass(sg_handle* h, const StageOp& op, int region) {
 // are static).  The interior launch then splits ACTIVE items evenly over the XCDs (a shell is whole z-layers of groups,
 // i.e. the first items of XCD 0 and the last of XCD 7: skipping them inside an even split of all items would leave the
 // launch as long as before); the shell launch deals its few items round-robin over all waves.
-static int region_items(sg_handle* h, int region, const StageArgs& a) {
+static int region_items(sg_handle* h, int region, const std::vector<Box>& boxes) {
   if (h->region_nitems[region] >= 0) return SG_OK;
-  const int64_t gw = h->md.gw, ngroups = h->md.ncube_pad / gw;
-  std::vector<char> hit((size_t)ngroups, 0);
-  std::vector<int32_t> cnt((size_t)ngroups, 0);
-  for (int bx = 0; bx < a.nbox; ++bx)
-    for (int ck = a.boxes_o[bx][2]; ck < a.boxes_o[bx][2] + a.boxes_n[bx][2]; ++ck)
-      for (int cj = a.boxes_o[bx][1]; cj < a.boxes_o[bx][1] + a.boxes_n[bx][1]; ++cj)
-        for (int ci = a.boxes_o[bx][0]; ci < a.boxes_o[bx][0] + a.boxes_n[bx][0]; ++ci) {
-          int64_t cube = ci + (int64_t)h->cfg.n[0] * (cj + (int64_t)h->cfg.n[1] * ck);
-          hit[(size_t)(cube / gw)] = 1;
-          cnt[(size_t)(cube / gw)] += 1;
-        }
-  // Whole groups only (always, on meshes whose rows are a multiple of the group width: a shell in x is one
-  // group thick): the kernels then skip the cube coordinates and the box tests, as in a whole-block launch.
-  // (The boxes of a region are disjoint, so the count of a group tells.)
-  bool whole = true;
-  for (int64_t g = 0; g < ngroups; ++g)
-    if (hit[(size_t)g] && cnt[(size_t)g] != std::min<int64_t>(gw, h->md.ncube - g * gw)) whole = false;
-  std::vector<int32_t> items;
-  for (int64_t g = 0; g < ngroups; ++g)
-    if (hit[(size_t)g])
-      for (int k = 0; k < h->ncls; ++k) items.push_back((int32_t)(g * h->ncls + k));
+  const RegionItems r = region_items(boxes, h->cfg.n, layout(h), h->md.ncube, h->md.ncube_pad);
   DevBuf<int32_t> list;
-  if (!items.empty()) HIPCHECK(h, list.upload(items.data(), items.size()));
+  if (!r.items.empty()) HIPCHECK(h, list.upload(r.items.data(), r.items.size()));
   h->region_items[region] = std::move(list);
-  h->region_nitems[region] = (int32_t)items.size();
-  h->region_whole[region] = whole;
+  h->region_nitems[region] = (int32_t)r.items.size();
+  h->region_whole[region] = r.whole;
   return SG_OK;
 }
 
@@ -213,7 +193,7 @@ static int launch_region(sg_handle* h, int kind, int region, StageArgs& a) {
   a.nlist = 0;
   a.order_chunk = (h->family == Family::Mfma && !a.spread && kind == 0) ? h->order_chunk : 0;
   if (region != SG_REGION_ALL) {
-    if (int rc = region_items(h, region, a)) return rc;
+    if (int rc = region_items(h, region, boxes)) return rc;
     a.item_list = h->region_items[region].get();
     a.nlist = h->region_nitems[region];
     if (family_whole_groups(h->family) && h->region_whole[region] && !h->no_whole) a.all_active = 1;

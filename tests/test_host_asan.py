@@ -1,7 +1,8 @@
 """CPU sanitizer runs (SURVEY 5 "race detection / sanitizers": ASAN on the CPU restatement; GPU ASAN is not available on
 this pool): the device-free host code of libseigen_hip - reference elements, mesh tables, MFMA fragment tables, the
-device-free C-ABI entry points (seigen_amd/csrc: refelem.cpp, mesh_tables.cpp, mfma_tables.cpp, hostapi.cpp) - and the
-oracle's C port (oracle/c/seigen_oracle.c), both built with -fsanitize=address,undefined and run on the CPU."""
+sponge, source and receiver plans of the setters, the item lists of split-stage regions, the device-free C-ABI entry
+points (seigen_amd/csrc: refelem.cpp, mesh_tables.cpp, mfma_tables.cpp, sponge_tables.cpp, source_tables.cpp,
+hostapi.cpp) - and the oracle's C port (oracle/c/seigen_oracle.c), both built with -fsanitize=address,undefined and run on the CPU."""
 import os
 import shutil
 import subprocess

@@ -1,16 +1,21 @@
 // CPU sanitizer driver (SURVEY 5 "sanitizers"; `make -C seigen_amd/csrc host-asan`): everything of libseigen_hip that
-// needs no device - reference elements, mesh tables, MFMA fragment tables, the device-free C-ABI entry points - built with
+// needs no device - reference elements, mesh tables, MFMA fragment tables, the sponge, source and receiver plans, the items
+// of split-stage regions, the device-free C-ABI entry points - built with
 // -fsanitize=address,undefined and walked over every (dim, degree, cell type, diagonal) the library accepts, plus the
 // argument errors the entry points must refuse.  Exit code 0 and no sanitizer report = clean.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <map>
+#include <set>
+#include <stdexcept>
 #include <vector>
 
 #include "hostlogic.hpp"
 #include "kernels.hpp"
 #include "mfma_tables.hpp"
+#include "source_tables.hpp"
 #include "sponge_tables.hpp"
 
 using namespace sg;
@@ -446,6 +451,368 @@ static void sponge_plans(int dim, int degree, int kind, int q) {
   }
 }
 
+// The interleaved layout (hostlogic.hpp Layout) restated without its arithmetic: walk the storage of a field with ncomp
+// components in the order it lies in memory - groups of gw cubes, classes, nodes, components, lanes - and count.
+struct NaiveLayout {
+  std::vector<int64_t> item, lane;   // [cube * ncls + cls]
+  std::vector<int64_t> pos;          // [(cube * ncls + cls) * nd + b] -> position of component 0
+  std::vector<int64_t> group;        // [cube]
+  int64_t nitems = 0, len = 0;       // items, values allocated
+  NaiveLayout(int64_t gw, int64_t ncls, int64_t nd, int64_t ncomp, int64_t ncube) {
+    int64_t ngroups = 0;
+    while (ngroups * gw < ncube) ngroups += 1;
+    item.assign((size_t)(ngroups * gw * ncls), -1);
+    lane = item;
+    pos.assign((size_t)(ngroups * gw * ncls * nd), -1);
+    group.assign((size_t)(ngroups * gw), -1);
+    for (int64_t g = 0; g < ngroups; ++g)
+      for (int64_t k = 0; k < ncls; ++k, ++nitems)
+        for (int64_t b = 0; b < nd; ++b)
+          for (int64_t c = 0; c < ncomp; ++c)
+            for (int64_t w = 0; w < gw; ++w, ++len) {
+              const int64_t cube = g * gw + w;
+              group[(size_t)cube] = g;
+              item[(size_t)(cube * ncls + k)] = nitems;
+              lane[(size_t)(cube * ncls + k)] = w;
+              if (c == 0) pos[(size_t)((cube * ncls + k) * nd + b)] = len;
+            }
+  }
+};
+
+template <typename F>
+static bool throws_invalid(F&& f) {
+  try {
+    f();
+  } catch (const std::invalid_argument&) {
+    return true;
+  }
+  return false;
+}
+
+static int classes_of(int dim, int kind) { return kind == KIND_TENSOR || dim == 1 ? 1 : (dim == 2 ? 2 : 6); }
+
+// The host half of sg_set_source / sg_set_source_separable (csrc/source_tables.cpp plan_source) against the definition:
+// ragged blocks in every layout, FIRST regions that are empty / partial / everything, node lists with no / some / all
+// duplicates and all nodes in one cell, table / static / separable sources, symmetric and non-symmetric values
+static void source_plans(int dim, int kind) {
+  const int degree = dim == 3 ? 1 : 2, nd = num_nodes(dim, degree, kind), ncls = classes_of(dim, kind), dd = dim * dim;
+  const int32_t n[3] = {19, dim > 1 ? 3 : 1, dim > 2 ? 2 : 1};
+  const int64_t ncube = (int64_t)n[0] * n[1] * n[2], ncells = ncube * ncls, nscalar = ncells * nd;
+  unsigned seed = 777u + (unsigned)(dim * 10 + kind);
+  auto rnd = [&]() { seed = seed * 1664525u + 1013904223u; return (double)(seed >> 8) / (double)(1u << 24); };
+  for (int gw : {1, 16, 64}) {
+    const NaiveLayout NL(gw, ncls, nd, dd, ncube);
+    SourceRequest rq;
+    rq.dim = dim;
+    rq.L = Layout{gw, ncls, nd};
+    rq.ncells = ncells;
+    rq.ncube_pad = (int64_t)NL.group.size();
+    std::copy(n, n + 3, rq.n);
+    rq.want_fused = true;      // (only the 2-D tile family asks; the table is defined for every layout)
+    rq.sym = true;
+    // FIRST: of a block with neighbours on no / some / all sides, and the two extremes - no box, the whole block
+    for (int first = 0; first < 5; ++first) {
+      rq.first.clear();
+      if (first < 3) {
+        const int mask = first == 0 ? 0 : (first == 1 ? 0x25 & ((1 << (2 * dim)) - 1) : (1 << (2 * dim)) - 1);
+        int32_t has_nbr[6];
+        for (int s2 = 0; s2 < 6; ++s2) has_nbr[s2] = (mask >> s2) & 1;
+        region_boxes(dim, n, has_nbr, SG_REGION_FIRST, rq.first, shell_width_x(gw, n[0], has_nbr[0] != 0, has_nbr[1] != 0));
+      } else if (first == 4) {
+        rq.first.push_back(Box{{0, 0, 0}, {n[0], n[1], n[2]}});
+      }
+      std::vector<char> in_first((size_t)ncube, 0);
+      for (const Box& b : rq.first)
+        for (int ck = b.o[2]; ck < b.o[2] + b.n[2]; ++ck)
+          for (int cj = b.o[1]; cj < b.o[1] + b.n[1]; ++cj)
+            for (int ci = b.o[0]; ci < b.o[0] + b.n[0]; ++ci) in_first[(size_t)(ci + n[0] * (cj + n[1] * ck))] = 1;
+      for (int lists = 0; lists < 4; ++lists)        // 0 no duplicates, 1 some, 2 every node twice or more, 3 all in one cell
+        for (int mode = 0; mode < 3; ++mode)          // 0 table of 3 slices, 1 static, 2 separable
+          for (int sym = 0; sym < 2; ++sym) {
+            const int64_t nnz = lists == 3 ? 3 * nd : 40;
+            std::vector<int64_t> nodes;
+            const int64_t one_cell = (int64_t)(rnd() * ncells);
+            while ((int64_t)nodes.size() < nnz) {
+              const size_t have = nodes.size();
+              int64_t nx = lists == 3 ? one_cell * nd + (int64_t)(rnd() * nd) : (int64_t)(rnd() * nscalar);
+              if (lists == 2 && have >= (size_t)nnz / 2) nx = nodes[have - (size_t)nnz / 2];
+              if (lists == 1 && have % 5 == 4) nx = nodes[(size_t)(rnd() * have)];
+              const bool seen = std::find(nodes.begin(), nodes.end(), nx) != nodes.end();
+              if (seen && (lists == 0 || (lists <= 2 && have < (size_t)nnz / 2 && !(lists == 1 && have % 5 == 4)))) continue;
+              nodes.push_back(nx);
+            }
+            const int64_t nsteps = mode == 0 ? 3 : (mode == 1 ? -1 : 5), nslices = mode == 0 ? 3 : 1;
+            std::vector<double> values((size_t)(nslices * nnz * dd)), weights;
+            for (int64_t i = 0; i < nslices * nnz; ++i)
+              for (int a = 0; a < dim; ++a)
+                for (int b = a; b < dim; ++b) {
+                  const double v = std::ldexp(rnd() - 0.5, (int)(rnd() * 40) - 20);
+                  values[(size_t)(i * dd + a * dim + b)] = v;
+                  values[(size_t)(i * dd + b * dim + a)] = (sym || dim == 1 || i != nnz / 2) ? v : v + 1.0;
+                }
+            if (mode == 2)
+              for (int k = 0; k < 5; ++k) weights.push_back(rnd());
+            const SourcePlan pl = plan_source(rq, nnz, nodes.data(), nsteps, values.data(), mode == 2 ? weights.data() : nullptr);
+            // the nodes: each listed node once, FIRST ones first, in listed order on both sides
+            std::map<int64_t, int64_t> first_listed;
+            for (int64_t k = nnz - 1; k >= 0; --k) first_listed[NL.pos[(size_t)nodes[(size_t)k]]] = k;
+            EXPECT(pl.nnz == (int64_t)first_listed.size() && (int64_t)pl.offs.size() == pl.nnz);
+            EXPECT(lists == 0 ? pl.nnz == nnz : pl.nnz < nnz);
+            EXPECT(lists != 2 || pl.nnz == nnz / 2);
+            EXPECT(pl.is_static == (mode == 1) && pl.nsteps == (mode == 1 ? 1 : nsteps));
+            EXPECT(pl.weights == weights && (int64_t)pl.vals.size() == nslices * pl.nnz * dd);
+            EXPECT(std::set<int64_t>(pl.offs.begin(), pl.offs.end()).size() == pl.offs.size());
+            int64_t nfirst = 0;
+            for (const auto& kv : first_listed) {
+              int64_t cube = 0;      // the cube of the node at this position: the one whose nodes' positions hold it
+              for (int64_t k = 0; k < nnz; ++k)
+                if (NL.pos[(size_t)nodes[(size_t)k]] == kv.first) cube = nodes[(size_t)k] / ((int64_t)nd * ncls);
+              nfirst += in_first[(size_t)cube];
+            }
+            EXPECT(pl.nfirst == nfirst);
+            EXPECT(first == 3 ? pl.nfirst == 0 : (first == 4 ? pl.nfirst == pl.nnz : true));
+            for (int64_t j = 0; j < (int64_t)pl.offs.size(); ++j) {
+              const auto it = first_listed.find(pl.offs[(size_t)j]);
+              EXPECT(pl.offs[(size_t)j] >= 0 && pl.offs[(size_t)j] + (int64_t)(dd - 1) * gw < NL.len && it != first_listed.end());
+              if (it == first_listed.end()) continue;
+              EXPECT((in_first[(size_t)(nodes[(size_t)it->second] / ((int64_t)nd * ncls))] != 0) == (j < pl.nfirst));
+              if (j > 0 && j != pl.nfirst && first_listed.count(pl.offs[(size_t)j - 1]))
+                EXPECT(first_listed[pl.offs[(size_t)j - 1]] < it->second);
+            }
+            // the values: scattering the plan = adding the caller's entries one by one in the order listed, bit for bit
+            bool symmetric = true;
+            for (int64_t sl = 0; sl < nslices && (int64_t)pl.vals.size() == nslices * pl.nnz * dd; ++sl) {
+              std::vector<double> A((size_t)NL.len, 0.0), B((size_t)NL.len, 0.0);
+              for (int64_t j = 0; j < pl.nnz; ++j)
+                for (int c = 0; c < dd; ++c) A[(size_t)(pl.offs[(size_t)j] + (int64_t)c * gw)] = pl.vals[(size_t)((sl * pl.nnz + j) * dd + c)];
+              for (int64_t k = 0; k < nnz; ++k)
+                for (int c = 0; c < dd; ++c) B[(size_t)(NL.pos[(size_t)nodes[(size_t)k]] + (int64_t)c * gw)] += values[(size_t)((sl * nnz + k) * dd + c)];
+              EXPECT(A == B);
+              for (const auto& kv : first_listed)
+                for (int a = 0; a < dim; ++a)
+                  for (int b = 0; b < dim; ++b)
+                    symmetric = symmetric && B[(size_t)(kv.first + (int64_t)(a * dim + b) * gw)] == B[(size_t)(kv.first + (int64_t)(b * dim + a) * gw)];
+            }
+            EXPECT(pl.symmetric == symmetric && (sym || dim == 1 || !symmetric));
+            // the fused table: every source node is reached through slot / idx exactly once, every other entry is -1
+            EXPECT((int64_t)pl.slot.size() == NL.nitems);
+            std::vector<int> reached((size_t)pl.nnz, 0);
+            std::set<int32_t> slots;
+            for (int64_t cell = 0; cell < (int64_t)NL.item.size() && (int64_t)pl.slot.size() == NL.nitems; ++cell) {
+              const int32_t sl = pl.slot[(size_t)NL.item[(size_t)cell]];
+              if (sl < 0) continue;
+              slots.insert(sl);
+              EXPECT(((size_t)sl + 1) * nd * gw <= pl.idx.size());
+              for (int b = 0; b < nd && ((size_t)sl + 1) * nd * gw <= pl.idx.size(); ++b) {
+                const int32_t j = pl.idx[((size_t)sl * nd + b) * gw + (size_t)NL.lane[(size_t)cell]];
+                if (j < 0) continue;
+                EXPECT(j < pl.nnz && pl.offs[(size_t)j] == NL.pos[(size_t)(cell * nd + b)]);
+                if (j < pl.nnz) reached[(size_t)j] += 1;
+              }
+            }
+            EXPECT(std::count(reached.begin(), reached.end(), 1) == pl.nnz);
+            EXPECT(pl.idx.size() == slots.size() * nd * gw && (slots.empty() || *slots.rbegin() == (int32_t)slots.size() - 1));
+            EXPECT(std::count_if(pl.idx.begin(), pl.idx.end(), [](int32_t v) { return v >= 0; }) == pl.nnz);
+            // not wanted: no table; nothing else changes
+            SourceRequest plain = rq;
+            plain.want_fused = false;
+            const SourcePlan p2 = plan_source(plain, nnz, nodes.data(), nsteps, values.data(), mode == 2 ? weights.data() : nullptr);
+            EXPECT(p2.slot.empty() && p2.idx.empty() && p2.offs == pl.offs && p2.vals == pl.vals && p2.nfirst == pl.nfirst);
+          }
+    }
+    // no source, and what must be refused
+    const int64_t node0[2] = {0, nscalar - 1}, low[1] = {-1}, high[1] = {nscalar};
+    const std::vector<double> v((size_t)(2 * 3 * dd), 1.0);
+    EXPECT(plan_source(rq, 0, nullptr, 5, nullptr, nullptr).nnz == 0 && plan_source(rq, 2, node0, 0, v.data(), nullptr).nnz == 0);
+    EXPECT(plan_source(rq, 0, nullptr, 5, nullptr, nullptr).offs.empty() && plan_source(rq, 0, nullptr, 5, nullptr, nullptr).slot.empty());
+    EXPECT(plan_source(rq, 2, node0, 3, v.data(), nullptr).nnz == 2);
+    EXPECT(throws_invalid([&] { plan_source(rq, 2, nullptr, 3, v.data(), nullptr); }));
+    EXPECT(throws_invalid([&] { plan_source(rq, 2, node0, 3, nullptr, nullptr); }));
+    EXPECT(throws_invalid([&] { plan_source(rq, 2, node0, -2, v.data(), nullptr); }));
+    EXPECT(throws_invalid([&] { plan_source(rq, -1, node0, 3, v.data(), nullptr); }));
+    EXPECT(throws_invalid([&] { plan_source(rq, 2, node0, -1, v.data(), v.data()); }));
+    EXPECT(throws_invalid([&] { plan_source(rq, 1, low, 3, v.data(), nullptr); }));
+    EXPECT(throws_invalid([&] { plan_source(rq, 1, high, 3, v.data(), nullptr); }));
+  }
+}
+
+// sg_set_source_box_ricker's host half: box_nodes against testing every node of the block, ricker_weights against the formula
+static void box_ricker(int dim, int diagonal, int degree) {
+  sg_config cfg;
+  std::memset(&cfg, 0, sizeof(cfg));
+  cfg.dim = dim;
+  cfg.degree = degree;
+  cfg.diagonal = diagonal;
+  const int nn[3] = {5, 3, 2};
+  for (int a = 0; a < 3; ++a) {
+    cfg.n[a] = a < dim ? nn[a] : 1;
+    cfg.h[a] = a < dim ? 0.25 * (a + 1) : 1.0;
+    cfg.origin[a] = a < dim ? -0.5 + a : 0.0;
+    cfg.cube0[a] = a < dim ? 2 - a : 0;
+  }
+  NodeGeom G;
+  EXPECT(G.init(&cfg, degree));
+  const size_t nnodes = (size_t)cfg.n[0] * cfg.n[1] * cfg.n[2] * G.ncls * G.nq;
+  std::vector<double> X(nnodes * dim);
+  EXPECT(sg_block_node_coords(&cfg, degree, X.data(), X.size() * sizeof(double)) == SG_OK);
+  unsigned seed = 4242u + (unsigned)(dim * 100 + diagonal * 10 + degree);
+  auto rnd = [&]() { seed = seed * 1664525u + 1013904223u; return (double)(seed >> 8) / (double)(1u << 24); };
+  for (int trial = 0; trial < 40; ++trial) {
+    // boxes inside, across the block's sides, outside, around the whole block; planes through grid lines (lo = hi)
+    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    for (int a = 0; a < dim; ++a) {
+      const double x0 = cfg.origin[a] + cfg.cube0[a] * cfg.h[a], len = cfg.n[a] * cfg.h[a];
+      lo[a] = x0 + (rnd() * 2.0 - 0.5) * len;
+      hi[a] = lo[a] + rnd() * len;
+      if (trial % 4 == 1) lo[a] = hi[a] = x0 + (int)(rnd() * (cfg.n[a] + 1)) * cfg.h[a];
+      if (trial % 4 == 2 && a == 0) lo[a] = x0 - 10.0, hi[a] = x0 + len + 10.0;
+      if (trial == 3) lo[a] = x0 + 2 * len, hi[a] = x0 + 3 * len;
+    }
+    std::vector<int64_t> want;
+    for (size_t k = 0; k < nnodes; ++k) {
+      bool in = true;
+      for (int a = 0; a < dim; ++a) in = in && X[k * dim + a] >= lo[a] && X[k * dim + a] <= hi[a];
+      if (in) want.push_back((int64_t)k);
+    }
+    EXPECT(box_nodes(G, lo, hi) == want);
+    if (trial == 3) EXPECT(want.empty());
+  }
+  const double lo[3] = {0.5, 0.5, 0.5}, hi[3] = {0.4, 0.6, 0.6}, nan[3] = {std::nan(""), 0.0, 0.0};
+  EXPECT(throws_invalid([&] { box_nodes(G, lo, hi); }));
+  EXPECT(throws_invalid([&] { box_nodes(G, nan, lo); }));
+  const double a = 159.42, t0 = 0.3, tf = 1.25e-3, dts = 2.5e-3;
+  const std::vector<double> w = ricker_weights(a, t0, tf, dts, 300);
+  EXPECT(w.size() == 300);
+  for (size_t k = 0; k < w.size(); ++k) {
+    const double dt_ = tf + (double)k * dts - t0, want = (2.0 * a * dt_ * dt_ - 1.0) * std::exp(-a * dt_ * dt_);
+    EXPECT(std::fabs(w[k] - want) <= 1e-13 * std::fmax(1.0, std::fabs(want)));
+  }
+  EXPECT(ricker_weights(a, t0, tf, dts, 0).empty());
+}
+
+// sg_set_receivers' host half (hostapi.cpp plan_receivers) on the split of point_location(): the rows are the points that
+// locate_point gives the block, in order; item and lane are the owning cell's in every layout; phi is the basis at the point
+static void receiver_plans(int dim, int diagonal, int degree) {
+  const int kind = diagonal == SG_DIAGONAL_QUAD ? KIND_TENSOR : KIND_SIMPLEX, nd = num_nodes(dim, degree, kind), ncls = classes_of(dim, kind);
+  sg_config whole;
+  std::memset(&whole, 0, sizeof(whole));
+  whole.dim = dim;
+  whole.degree = degree;
+  whole.diagonal = diagonal;
+  for (int a = 0; a < 3; ++a) {
+    whole.n[a] = a < dim ? 4 : 1;
+    whole.h[a] = a < dim ? 0.25 * (a + 1) : 1.0;
+  }
+  std::vector<double> pts;
+  const double fr[] = {0.0, 0.5, 0.3};
+  for (int cz = (dim > 2 ? -1 : 0); cz <= (dim > 2 ? 4 : 0); ++cz)
+    for (int cy = (dim > 1 ? -1 : 0); cy <= (dim > 1 ? 4 : 0); ++cy)
+      for (int cx = -1; cx <= 4; ++cx)
+        for (int f = 0; f < 3; ++f) {
+          const int c[3] = {cx, cy, cz};
+          for (int a = 0; a < dim; ++a) pts.push_back((c[a] + (a == 1 ? 1.0 - fr[f] : fr[f])) * whole.h[a]);
+        }
+  const int64_t np = (int64_t)pts.size() / dim;
+  std::vector<int64_t> cell(np);
+  std::vector<double> xi(pts.size());
+  std::vector<int> owners(np, 0);
+  for (int b = 0; b < (1 << dim); ++b) {
+    sg_config blk = whole;
+    for (int a = 0; a < dim; ++a) {
+      const int hi = (b >> a) & 1;
+      blk.n[a] = 2;
+      blk.cube0[a] = 2 * hi;
+      blk.nbr_mask |= 1 << (2 * a + (1 - hi));
+    }
+    NodeGeom G;
+    EXPECT(G.init(&blk, degree));
+    EXPECT(sg_locate_points(&blk, np, pts.data(), cell.data(), xi.data()) == SG_OK);
+    const int64_t ncube = 1 << dim;
+    for (int gw : {1, 16, 64})
+      for (int what = 1; what <= 3; ++what) {
+        const NaiveLayout NL(gw, ncls, nd, 1, ncube);
+        const ReceiverPlan pl = plan_receivers(G, Layout{gw, ncls, nd}, kind, np, pts.data(), what, 7);
+        EXPECT(pl.ncomp == (what == 1 ? dim : (what == 2 ? dim * dim : dim + dim * dim)));
+        EXPECT((int64_t)pl.own.size() == np && pl.item.size() == pl.row.size() && pl.lane.size() == pl.row.size() && pl.phi.size() == pl.row.size() * nd);
+        size_t r = 0;
+        for (int64_t k = 0; k < np && (int64_t)pl.own.size() == np; ++k) {
+          EXPECT((pl.own[(size_t)k] != 0) == (cell[(size_t)k] >= 0));
+          if (cell[(size_t)k] < 0) continue;
+          if (gw == 1 && what == 1) owners[(size_t)k] += 1;
+          EXPECT(r < pl.row.size() && pl.row[r] == k);
+          if (r >= pl.row.size() || pl.phi.size() != pl.row.size() * nd) break;
+          EXPECT(pl.item[r] == NL.item[(size_t)cell[(size_t)k]] && pl.lane[r] == NL.lane[(size_t)cell[(size_t)k]]);
+          std::vector<double> phi((size_t)nd);
+          EXPECT(sg_tabulate_cell(kind, dim, degree, 1, &xi[(size_t)k * dim], phi.data()) == SG_OK);
+          double sum = 0.0;
+          for (int a = 0; a < nd; ++a) {
+            EXPECT(pl.phi[r * nd + a] == phi[(size_t)a]);
+            sum += phi[(size_t)a];
+          }
+          EXPECT(std::fabs(sum - 1.0) < 1e-9);
+          r += 1;
+        }
+        EXPECT(r == pl.row.size());
+        // a trace of more than 2^40 values is refused - where the block owns a receiver at all
+        EXPECT(throws_invalid([&] { plan_receivers(G, Layout{gw, ncls, nd}, kind, np, pts.data(), what, ((int64_t)1 << 40) + 1); }) == !pl.row.empty());
+      }
+    const double far[3] = {-5.0, -5.0, -5.0};
+    EXPECT(plan_receivers(G, Layout{16, ncls, nd}, kind, 1, far, 3, ((int64_t)1 << 40) + 1).row.empty());
+    EXPECT(plan_receivers(G, Layout{16, ncls, nd}, kind, 0, nullptr, 3, 0).own.empty());
+  }
+  std::vector<int64_t> cell1(np);
+  EXPECT(sg_locate_points(&whole, np, pts.data(), cell1.data(), xi.data()) == SG_OK);
+  for (int64_t k = 0; k < np; ++k) EXPECT(owners[(size_t)k] == (cell1[(size_t)k] >= 0 ? 1 : 0));
+}
+
+// The items of the regions of a split stage (hostapi.cpp region_items) against a per-cube brute force, on the ragged block
+// and the neighbour masks of regions_and_coords(), in every layout
+static void region_item_lists() {
+  for (int dim = 1; dim <= 3; ++dim)
+    for (int ncls : {1, dim == 1 ? 1 : (dim == 2 ? 2 : 6)})
+      for (int gw : {1, 16, 64})
+        for (int mask = 0; mask < (1 << (2 * dim)); mask += (dim == 3 ? 7 : 1)) {
+          const int32_t n[3] = {19, dim > 1 ? 5 : 1, dim > 2 ? 4 : 1};
+          int32_t has_nbr[6];
+          for (int s2 = 0; s2 < 6; ++s2) has_nbr[s2] = (mask >> s2) & 1;
+          const int64_t ncube = (int64_t)n[0] * n[1] * n[2];
+          const NaiveLayout NL(gw, ncls, 1, 1, ncube);
+          const int64_t ngroups = NL.nitems / ncls;
+          for (int region = 0; region <= 4; ++region) {
+            std::vector<Box> boxes;
+            region_boxes(dim, n, has_nbr, region, boxes, shell_width_x(gw, n[0], has_nbr[0] != 0, has_nbr[1] != 0));
+            const RegionItems got = region_items(boxes, n, Layout{gw, ncls, 1}, ncube, (int64_t)NL.group.size());
+            std::vector<int> hit((size_t)ngroups, 0), real((size_t)ngroups, 0);
+            int64_t cube = 0;
+            for (int ck = 0; ck < n[2]; ++ck)
+              for (int cj = 0; cj < n[1]; ++cj)
+                for (int ci = 0; ci < n[0]; ++ci, ++cube) {
+                  const int c[3] = {ci, cj, ck};
+                  int inside = 0;
+                  for (const Box& b : boxes) {
+                    bool in = true;
+                    for (int a = 0; a < 3; ++a) in = in && c[a] >= b.o[a] && c[a] < b.o[a] + b.n[a];
+                    inside += in;
+                  }
+                  EXPECT(inside <= 1);      // the boxes of a region are disjoint
+                  real[(size_t)NL.group[(size_t)cube]] += 1;
+                  hit[(size_t)NL.group[(size_t)cube]] += inside;
+                }
+            std::vector<int32_t> items;
+            bool whole = true;
+            for (int64_t g = 0; g < ngroups; ++g) {
+              if (hit[(size_t)g] == 0) continue;
+              whole = whole && hit[(size_t)g] == real[(size_t)g];
+              for (int k = 0; k < ncls; ++k) items.push_back((int32_t)NL.item[(size_t)(g * gw * ncls + k)]);
+            }
+            EXPECT(got.items == items && got.whole == whole);
+            if (region == SG_REGION_ALL) EXPECT(got.whole && (int64_t)got.items.size() == NL.nitems);
+          }
+        }
+  const int32_t n1[3] = {4, 1, 1};
+  EXPECT(region_items({}, n1, Layout{16, 2, 1}, 4, 16).items.empty() && region_items({}, n1, Layout{16, 2, 1}, 4, 16).whole);
+}
+
 // The six launches of an LF4 step (hostlogic.hpp lf4_stage) against the rows written out here, for two (dt, rho) and the
 // three density conventions of stage U1; every stage reads what the stage before it wrote, cyclically over the step.
 // The printed lines are what tests/test_host_logic.py compares with seigen_amd/parallel.py STAGE_INPUT / STAGE_OUTPUT.
@@ -512,6 +879,16 @@ int main() {
         if (kind == KIND_TENSOR && dim == 3 && degree == 4) continue;      // 125^3 sponge tensor: minutes under the sanitizers
         for (int q : {1, 4}) sponge_plans(dim, degree, kind, q);
       }
+  region_item_lists();
+  for (int dim = 1; dim <= 3; ++dim)
+    for (int kind : {KIND_SIMPLEX, KIND_TENSOR}) {
+      if (kind == KIND_TENSOR && dim == 1) continue;
+      source_plans(dim, kind);
+      for (int degree : {1, 3}) {
+        box_ricker(dim, kind == KIND_TENSOR ? SG_DIAGONAL_QUAD : dim % 2, degree);
+        receiver_plans(dim, kind == KIND_TENSOR ? SG_DIAGONAL_QUAD : dim % 2, degree);
+      }
+    }
   // arguments the entry points must refuse
   EXPECT(sg_reference_operator_cell(7, 2, 2, 0, 0, nullptr, 0) == SG_ERR_ARG);
   EXPECT(sg_reference_operator_cell(0, 2, 2, 9, 0, nullptr, 0) == SG_ERR_ARG);
