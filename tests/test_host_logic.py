@@ -50,6 +50,25 @@ def test_mfma_family_instantiations_are_the_listed_ones():
     assert len(found) == 140
 
 
+@pytest.mark.parametrize("family,count", [("tile2d_stage", 320), ("hexm_stage", 20), ("hex_stage", 16)])
+def test_tile2d_and_hexahedral_family_instantiations_are_the_listed_ones(family, count):
+    """The kernel objects of the 2-D tile family and of the two hexahedral families in the built library are exactly
+    TILE2D_KERNELS, HEXM_KERNELS and HEX_LANE_KERNELS, the lists tests/test_tile2d_family_gpu.py and
+    tests/test_hex_family_gpu.py check row by row against the oracle: no instantiation joins or leaves unseen."""
+    import subprocess
+    from tests.test_hex_family_gpu import HEXM_KERNELS, HEX_LANE_KERNELS
+    from tests.test_tile2d_family_gpu import TILE2D_KERNELS
+    listed = {"tile2d_stage": TILE2D_KERNELS, "hexm_stage": HEXM_KERNELS, "hex_stage": HEX_LANE_KERNELS}[family]
+    readelf = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin", "llvm-readelf")
+    assert os.path.exists(readelf), "llvm-readelf (shipped with ROCm) not found at %s: set ROCM_PATH" % readelf
+    out = subprocess.run([readelf, "--dyn-syms", "--demangle", _lib.lib_path()], capture_output=True, text=True, check=True).stdout
+    pat = re.compile(r"\bOBJECT\b.*?\b(sg::%s<[^>]*>)\(" % family)
+    found = {m.group(1) for m in map(pat.search, out.splitlines()) if m}
+    assert not listed - found, "listed but not in the library: %s" % sorted(listed - found)
+    assert not found - listed, "in the library but not listed: %s" % sorted(found - listed)
+    assert len(found) == count
+
+
 def test_create_fails_loudly_without_device_or_bad_args():
     L = lib()
     cfg = _lib.SgConfig()
