@@ -222,10 +222,11 @@ def _err(what, family, dtype, got, want):
     return e
 
 
-def check_block(family, make_block, m, hmin, P, cell, dtype, sym, names, density, sponge, seed):
+def check_block(family, make_block, m, hmin, P, cell, dtype, sym, names, density, sponge, seed, reports_sym=None):
     """One application of F and G, then three steps with every extra, against the oracle on mesh m (also the rows of
-    tests/test_hex_family_gpu.py).  make_block() builds the block under test; hmin: its smallest cell width; names: the six
-    kernels it must report."""
+    tests/test_hex_family_gpu.py and tests/test_lane_generic_family_gpu.py).  make_block() builds the block under test;
+    hmin: its smallest cell width; names: the six kernels it must report; sponge: None for a run without one; reports_sym:
+    what is_sym() must say where that is not `sym` (the generic kernels have no symmetric-stress storage)."""
     from seigen_amd import _lib
     dim = m.dim
     tol1, tol3 = _tolerances(dtype, P, cell)
@@ -233,6 +234,7 @@ def check_block(family, make_block, m, hmin, P, cell, dtype, sym, names, density
     orc = OracleLF4(m, P)
     nc = m.ncells
     lam, mu = rng.uniform(0.4, 0.8, nc), rng.uniform(0.2, 0.4, nc)
+    reports_sym = sym if reports_sym is None else reports_sym
 
     # the instantiations, before anything runs
     blk = make_block()
@@ -242,7 +244,7 @@ def check_block(family, make_block, m, hmin, P, cell, dtype, sym, names, density
     blk.set_params(1.0, 0.01, lam, mu)
     blk.set_field(_lib.FIELD_S, T)
     blk.set_field(_lib.FIELD_U, u)
-    assert blk.is_sym() == sym
+    assert blk.is_sym() == reports_sym
     assert [blk.stage_kernel_name(st) for st in range(6)] == names
 
     # one application of each operator (the MODE 0 kernels)
@@ -266,15 +268,16 @@ def check_block(family, make_block, m, hmin, P, cell, dtype, sym, names, density
         orc.density_physical = density == "physical"
         blk.set_params(1.0, orc.dt, lam, mu)
         blk.set_density(orc.density, physical=orc.density_physical)
-    sigma = sponge(m, rng)
-    orc.E.set_absorption(sigma, 4)
-    blk.set_absorption(sigma, 4)
+    if sponge is not None:
+        sigma = sponge(m, rng)
+        orc.E.set_absorption(sigma, 4)
+        blk.set_absorption(sigma, 4)
     nodes = _source_nodes(nc, nd, rng)
     vals = _stress((3, len(nodes), dim, dim), rng, sym)
     blk.set_source(nodes, vals)
     blk.set_field(_lib.FIELD_U, orc.u0)
     blk.set_field(_lib.FIELD_S, orc.s0)
-    assert blk.is_sym() == sym
+    assert blk.is_sym() == reports_sym
     assert [blk.stage_kernel_name(st) for st in range(6)] == names
     blk.step(3)
     for k in range(3):
