@@ -85,8 +85,9 @@ struct SpongeTables {
   DevBuf<double> aff_frag;    // 3-D MFMA family in double: the X_k as row tiles (mfma_frags_dense)
   int aff_grid = 0;           // persistent grid of the affine pre-pass (sponge_affine_mfma where aff_frag is set), on the handle's device
   // The pre-pass is B_e u_abs of a FIELD STATE: stages UH1 and U1 both absorb u0 (elastic.py:206-208 in form_uh1 and form_uh2),
-  // UTEMP absorbs the u1 that U1 wrote, and the next step's UH1 and U1 absorb that same u1 - so in the steady state UH1 finds
-  // UTEMP's pre-pass and a step runs ONE pre-pass (UTEMP's); a captured graph computes it afresh at its own first step.
+  // UTEMP absorbs the u1 that U1 wrote, and the next step's UH1 and U1 absorb that same u1 - so in the steady state of eager
+  // and host-driven steps UH1 finds UTEMP's pre-pass and a step runs ONE pre-pass (UTEMP's), not three.  A captured graph
+  // computes it afresh at its own first step (two in graph1, nine in graph8), and a replay leaves nothing to reuse.
   // pre_ver / pre_field name the state the buffer holds (sg_handle::fver; ~0: none), pre_key the F stage (output field,
   // mode) whose pre-pass ran last, pre_regions the regions launched since.
   int pre_key = -1, pre_regions = 0;
@@ -240,8 +241,11 @@ inline int fail(sg_handle* h, int code, const std::string& msg) {
 
 inline bool field_is_stress(int f) { return f == SG_FIELD_S || f == SG_FIELD_SH; }
 
-// Every path that changes h->field[f] - stage outputs, uploads, graph replays, the mirror of leave_sym_mode - calls this:
-// the sponge pre-pass of a field state (SpongeTables::pre_ver) is reused as long as fver says the field still holds it.
+// INVARIANT: every writer of h->field[f] calls this - today run_op (stage outputs, sg_apply_F / sg_apply_G), transfer() on
+// uploads, steps_done after a graph replay (all four fields) and the mirror launch of leave_sym_mode.  The sponge pre-pass of
+// a field state (SpongeTables::pre_ver) is reused as long as fver says the field still holds that state: a writer that
+// forgets the bump - a restore, a device-pointer interop - makes the next F stage absorb the velocity of the step before,
+// with no fault and no NaN (tests/test_lifetime_gpu.py uploads velocities between stepping calls for this).
 inline void mark_field_written(sg_handle* h, int f) { h->fver[f] += 1; }
 
 // work queued on `stream` from here on comes after the SECOND launch that may still run on stream2
