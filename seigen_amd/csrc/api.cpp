@@ -206,8 +206,8 @@ static int init_fields(sg_handle* h, const Frags& fr) {
     h->field_len[f] = (size_t)h->ncells * nd * comps;
     h->field_alloc[f] = (size_t)h->md.ncube_pad * h->ncls * nd * comps;
     const size_t n = h->f32 ? (h->field_alloc[f] + 1) / 2 : h->field_alloc[f];   // in doubles
-    if (h->field[f].alloc(n) != hipSuccess) return fail(h, SG_ERR_NOMEM, "hipMalloc of a field buffer failed");
-    HIPCHECK(h, hipMemset(h->field[f].get(), 0, n * sizeof(double)));
+    if (h->field.alloc(f, n) != hipSuccess) return fail(h, SG_ERR_NOMEM, "hipMalloc of a field buffer failed");
+    HIPCHECK(h, hipMemset(h->field.write(f), 0, n * sizeof(double)));
   }
   DevBuf<double>* frag[5] = {&h->fragF, &h->fragG, &h->fragL, &h->fragQ, &h->fragP};
   for (int i = 0; i < 5; ++i)
@@ -652,8 +652,8 @@ int sg_set_receivers(sg_handle* h, int64_t nrec, const double* pts, int what, in
     rt.nown = (int64_t)pl.row.size();
     rt.what = what;
     rt.ncomp = pl.ncomp;
-    rt.every = every;
-    rt.capacity = capacity;
+    rt.clock.every = every;
+    rt.clock.capacity = capacity;
     const size_t tlen = (size_t)(capacity * rt.nown * rt.ncomp);
     const int64_t zero = 0;
     HIPCHECK(h, rt.item.upload(pl.item.data(), pl.item.size()));
@@ -674,12 +674,12 @@ int sg_set_receivers(sg_handle* h, int64_t nrec, const double* pts, int what, in
 int sg_get_receivers(sg_handle* h, double* out, size_t nbytes, int64_t* nsamples) {
   if (!h || !nsamples) return SG_ERR_ARG;
   const ReceiverTables& rt = h->rec;
-  const size_t want = (size_t)(rt.capacity * rt.nrec * rt.ncomp) * sizeof(double);
+  const size_t want = (size_t)(rt.clock.capacity * rt.nrec * rt.ncomp) * sizeof(double);
   if (nbytes != want || (want > 0 && !out))
     return fail(h, SG_ERR_ARG, "sg_get_receivers: the buffer must hold capacity x nrec x ncomp doubles (" + std::to_string(want) + " bytes)");
   HIPCHECK(h, hipSetDevice(h->cfg.device));
   HIPCHECK(h, sync_all(h));
-  const int64_t n = rt.samples();
+  const int64_t n = rt.clock.samples();
   std::vector<double> t((size_t)(n * rt.nown * rt.ncomp));
   if (!t.empty()) HIPCHECK(h, hipMemcpy(t.data(), rt.trace.get(), t.size() * sizeof(double), hipMemcpyDeviceToHost));
   if (want > 0) std::memset(out, 0, want);

@@ -3,7 +3,9 @@
 //   transfer.cpp host <-> device field transfers (layout conversion, pinned pipeline)
 //   stages.cpp   regions, stage launches, the LF4 step, graphs, halo packs, timing
 // and, without a device or a HIP header (the CPU sanitizer build, `make host-asan`):
-//   hostapi.cpp (hostlogic.hpp)  family choice, field layout, stage table, region boxes / items, point location, receiver plan
+//   hostapi.cpp (hostlogic.hpp)  family choice, field layout, stage table, region boxes / items, point location, receiver plan;
+//                                what stepping remembers between calls: field write counts, the sponge pre-pass's state,
+//                                the source's slice at a step, the receivers' clock
 //   sponge_tables.cpp            what sg_set_absorption derives from the nodal sigma
 //   source_tables.cpp            what the source setters derive from the caller's nodes and values
 #pragma once
@@ -84,15 +86,7 @@ struct SpongeTables {
   DevBuf<int32_t> aff_col;    // [nd][W], empty where the rows are dense
   DevBuf<double> aff_frag;    // 3-D MFMA family in double: the X_k as row tiles (mfma_frags_dense)
   int aff_grid = 0;           // persistent grid of the affine pre-pass (sponge_affine_mfma where aff_frag is set), on the handle's device
-  // The pre-pass is B_e u_abs of a FIELD STATE: stages UH1 and U1 both absorb u0 (elastic.py:206-208 in form_uh1 and form_uh2),
-  // UTEMP absorbs the u1 that U1 wrote, and the next step's UH1 and U1 absorb that same u1 - so in the steady state of eager
-  // and host-driven steps UH1 finds UTEMP's pre-pass and a step runs ONE pre-pass (UTEMP's), not three.  A captured graph
-  // computes it afresh at its own first step (two in graph1, nine in graph8), and a replay leaves nothing to reuse.
-  // pre_ver / pre_field name the state the buffer holds (sg_handle::fver; ~0: none), pre_key the F stage (output field,
-  // mode) whose pre-pass ran last, pre_regions the regions launched since.
-  int pre_key = -1, pre_regions = 0;
-  uint64_t pre_ver = ~0ull;
-  int pre_field = -1;
+  PrePass pre_state;          // what `pre` holds and when it is due again (hostlogic.hpp); new tables start with none
 };
 
 // The source of sg_set_source / sg_set_source_separable, on the device
@@ -121,13 +115,29 @@ struct ReceiverTables {
   DevBuf<double> phi;         // [nown][nd] basis of the cell at the point
   int what = 0;               // bit 0: velocity (dim values), bit 1: stress (dim x dim, row-major)
   int ncomp = 0;
-  int64_t every = 1, capacity = 0;
+  ReceiverClock clock;        // every, capacity, steps completed since arming (hostlogic.hpp)
   DevBuf<double> trace;       // [capacity][nown][ncomp]
-  int64_t steps = 0;          // steps completed since arming; sample j is taken after step (j + 1) * every
   // graph replay: the step index of the launches of a capture (RecvArgs::ctr), set by sg_step before it replays and
   // bumped by a one-thread launch after the recorder (the role of sg_handle::src_ctr_d for the receivers)
   DevBuf<int64_t> ctr;
-  int64_t samples() const { return nrec > 0 ? steps / every : 0; }
+};
+
+// The four fields of a block.  Whoever writes one asks for it with write(), which counts the write: what remembers a field
+// state (the sponge pre-pass, hostlogic.hpp PrePass) can then tell that the field has moved on - from a stage, a source
+// launch, an upload or the mirror launch alike.  Readers take the const pointer.
+struct Fields {
+  const double* read(int f) const { return buf_[f].get(); }
+  double* write(int f) {
+    ver_.written(f);
+    return buf_[f].get();
+  }
+  void replayed() { ver_.replayed(); }
+  const FieldVersions& versions() const { return ver_; }
+  hipError_t alloc(int f, size_t n) { return buf_[f].alloc(n); }
+
+ private:
+  DevBuf<double> buf_[4];   // double, or float where f32
+  FieldVersions ver_;
 };
 
 struct sg_handle {
@@ -137,7 +147,7 @@ struct sg_handle {
   MeshDev md;
   DevBuf<MeshDev> md_dev;
   DevBuf<double> Dt, Lt;
-  DevBuf<double> field[4];               // double, or float where f32
+  Fields field;
   size_t field_len[4] = {0, 0, 0, 0};    // doubles, host layout (ncells * nd * comps)
   size_t field_alloc[4] = {0, 0, 0, 0};  // values allocated on the device (layout padding included)
   Family family = Family::Generic;   // the kernels that run the block (hostlogic.hpp); md.gw = family_gw(family)
@@ -170,17 +180,14 @@ struct sg_handle {
   DevBuf<double> rho2_d;     // per-cell density factors [cell][2] (kernels.hpp), or empty
   int rho_physical = 0;      // scalar density: 0 = rho*u0 + ..., 1 = u0 + (...)/rho
   SpongeTables sponge;
-  uint64_t fver[4] = {0, 0, 0, 0};   // writes to each field (mark_field_written)
   SourceTables src;
   int64_t src_step = 0;
   // graph replay with a source: the step index lives in a device word that the captured launches read and a one-thread
   // launch bumps at the end of every step (kernels.hpp SrcStep); sg_step sets it to src_step before it replays.
   // Allocated by the first source and kept.
   DevBuf<int64_t> src_ctr_d;
-  bool capture_src = false;   // stage launches issued now (a capture) take slice and weight from src_ctr_d
   bool graph_src = false;     // the captured graphs contain the source launches
   ReceiverTables rec;
-  bool capture_rec = false;   // a capture: the recorder takes the step from rec.ctr
   bool graph_rec = false;     // the captured graphs contain the recorder launches
   // halo
   const double* ghost[4][6] = {};
@@ -218,7 +225,6 @@ struct sg_handle {
   double first_ms_pending[6] = {-1, -1, -1, -1, -1, -1};
   int first_recorded_stage = -1;         // stage whose FIRST launch recorded ev_stage last (SECOND must follow it)
   sg_counters_t counters = {};
-  std::string* name_out = nullptr;   // sg_stage_kernel_name: stage launches only name their kernel (StageArgs::name_out)
   bool no_whole = false;             // SEIGEN_HIP_NO_WHOLE (diagnostic): region launches always test the boxes
   std::string err;
 };
@@ -240,13 +246,6 @@ inline int fail(sg_handle* h, int code, const std::string& msg) {
 }
 
 inline bool field_is_stress(int f) { return f == SG_FIELD_S || f == SG_FIELD_SH; }
-
-// INVARIANT: every writer of h->field[f] calls this - today run_op (stage outputs, sg_apply_F / sg_apply_G), transfer() on
-// uploads, steps_done after a graph replay (all four fields) and the mirror launch of leave_sym_mode.  The sponge pre-pass of
-// a field state (SpongeTables::pre_ver) is reused as long as fver says the field still holds that state: a writer that
-// forgets the bump - a restore, a device-pointer interop - makes the next F stage absorb the velocity of the step before,
-// with no fault and no NaN (tests/test_lifetime_gpu.py uploads velocities between stepping calls for this).
-inline void mark_field_written(sg_handle* h, int f) { h->fver[f] += 1; }
 
 // work queued on `stream` from here on comes after the SECOND launch that may still run on stream2
 inline int join_second(sg_handle* h) {

@@ -83,6 +83,96 @@ StageOp lf4_stage(int stage, double dt, double rho, bool rho_physical, bool per_
 inline int lf4_stage_input(int stage) { return lf4_stage(stage, 0.0, 1.0, false, false).in; }
 inline int lf4_stage_output(int stage) { return lf4_stage(stage, 0.0, 1.0, false, false).out; }
 
+// What the stepping calls remember from one call to the next, as values: written by stages.cpp and the transfers, stated and
+// walked without a device (tools/host_asan_driver.cpp stepping_state).
+
+// Writes to each of the four fields, counted: a field whose count stands still holds the state it held.
+struct FieldVersions {
+  uint64_t v[4] = {0, 0, 0, 0};
+  void written(int f) { v[f] += 1; }
+  void replayed() {   // a graph replay wrote all four
+    for (uint64_t& x : v) x += 1;
+  }
+};
+
+// The sponge pre-pass buffer of the F stages (handle.hpp SpongeTables::pre) holds B_e u_abs of a FIELD STATE: stages UH1 and
+// U1 both absorb u0 (elastic.py:206-208 in form_uh1 and form_uh2), UTEMP absorbs the u1 that U1 wrote, and the next step's
+// UH1 and U1 absorb that same u1 - so in the steady state of eager and host-driven steps UH1 finds UTEMP's pre-pass and a
+// step runs ONE pre-pass (UTEMP's), not three.  A captured graph computes it afresh at its own first step (two in graph1,
+// nine in graph8), and a replay leaves nothing to reuse.
+struct PrePass {
+  // A launch of `op` on `region` is about to be queued: does the pre-pass run first?  It does at the first launch of a stage
+  // - whichever region the caller starts with: the same stage again, or a region it has already seen, is the next instance
+  // of the stage - unless the buffer already holds that state of op.uabs.  Asked BEFORE the launch counts as a write of its
+  // output: an in-place stage (U1) absorbs the state it overwrites, and its later regions find the pre-pass of the first.
+  bool due(const StageOp& op, int region, const FieldVersions& fv) {
+    if (op.kind != 0) return false;
+    const int k = op.out * 4 + op.mode;
+    const bool first_of_stage = k != key || (regions & (1 << region)) != 0 || region == SG_REGION_ALL;
+    if (first_of_stage) regions = 0;
+    key = k;
+    regions |= 1 << region;
+    if (!first_of_stage || (field == op.uabs && ver == fv.v[op.uabs])) return false;
+    field = op.uabs;
+    ver = fv.v[op.uabs];
+    return true;
+  }
+  // the buffer holds nothing known: the launches of a capture compute their own, and so does whatever follows a replay
+  void forget() { ver = ~0ull; }
+
+ private:
+  int key = -1, regions = 0;   // the F stage (output field, mode) whose pre-pass was asked for last, the regions launched since
+  int field = -1;              // the state the buffer holds: this field at ...
+  uint64_t ver = ~0ull;        // ... this count of its writes (~0: none)
+};
+
+// The source at one step (seigen_hip.h sg_set_source / sg_set_source_separable): which slice of the value table, which
+// weight.  Eager launches get both from the host; the launches of a capture made while the source was active read them
+// off a device-side step counter (kernels.hpp SrcStep) and are due at every replayed step - the kernel adds nothing
+// once the source has run out.
+struct SourceFacts {
+  int64_t nnz = 0, nsteps = 0;
+  bool is_static = false;            // one slice that holds at every step
+  const double* weights = nullptr;   // [nsteps] on the host: a separable source (one slice, scaled), else null
+  int dim = 0;
+};
+struct SourceSlice {
+  bool active = false;    // the source has a slice for this step
+  bool due = false;       // ... and a launch adds it
+  int64_t offset = 0;     // doubles from the start of the value table to the slice (a capture: the kernel's business)
+  double scale = 1.0;
+  // SrcStep but for its device pointers; all zero outside a capture
+  int64_t nsteps = 0, stride = 0;
+  bool is_static = false, use_weights = false;
+};
+inline SourceSlice source_slice(const SourceFacts& s, int64_t step, bool capture) {
+  SourceSlice r;
+  r.active = s.nnz != 0 && (s.is_static || step < s.nsteps);
+  r.due = capture || r.active;
+  const int64_t stride = (s.is_static || s.weights) ? 0 : s.nnz * s.dim * s.dim;
+  if (capture) {
+    r.nsteps = s.nsteps;
+    r.stride = stride;
+    r.use_weights = s.weights != nullptr;
+    r.is_static = s.is_static || (stride == 0 && !s.weights);
+  } else if (r.active) {
+    r.offset = step * stride;
+    if (s.weights) r.scale = s.weights[step];
+  }
+  return r;
+}
+
+// The receivers' clock (seigen_hip.h sg_set_receivers): sample j is taken after step (j + 1) * every, and the trace holds
+// `capacity` samples.
+struct ReceiverClock {
+  int64_t every = 1, capacity = 0;
+  int64_t steps = 0;   // completed since arming
+  int64_t samples_after(int64_t n) const { return (steps + n) / every; }
+  int64_t samples() const { return samples_after(0); }
+  bool fits(int64_t n) const { return samples_after(n) <= capacity; }                       // n more steps
+  bool no_room_at(int64_t s) const { return s % every == 0 && s / every > capacity; }       // step s is due a sample and has none
+};
+
 struct Box {
   int o[3], n[3];
 };

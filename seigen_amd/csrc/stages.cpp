@@ -4,43 +4,49 @@
 
 // ---- stage launches --------------------------------------------------------------------
 
-static bool source_active(const sg_handle* h) {
-  return h->src.nnz != 0 && (h->src.is_static || h->src_step < h->src.nsteps);
+// What a launch is queued with, as a value that its caller builds and every function below is handed: nothing on the handle
+// says "a capture is under way" or "only name the kernels", so nothing has to be put back afterwards.
+struct LaunchCtx {
+  hipStream_t stream;                 // the stream of this launch and of what belongs to it (pre-pass, source)
+  std::string* name_out = nullptr;    // a naming pass: every launcher names its kernel and launches nothing (kernels.hpp SG_LAUNCH)
+  bool capture_src = false;           // a capture: slice and weight of the source come from the device-side counter src_ctr_d ...
+  bool capture_rec = false;           // ... and the recorder's step from rec.ctr
+};
+
+// the source at the handle's step (hostlogic.hpp source_slice), with the device pointers of a capture's SrcStep
+struct SourceNow {
+  SourceSlice at;
+  const double* values;
+  SrcStep stepper;
+};
+static SourceSlice source_at(const sg_handle* h, bool capture) {
+  const SourceTables& src = h->src;
+  return source_slice({src.nnz, src.nsteps, src.is_static, src.weights.empty() ? nullptr : src.weights.data(), h->cfg.dim}, h->src_step,
+                      capture);
 }
-// launches of a capture: slice and weight of the step the device-side counter names (kernels.hpp SrcStep)
-static SrcStep source_stepper(const sg_handle* h) {
-  SrcStep ss;
-  std::memset(&ss, 0, sizeof(ss));
-  if (!h->capture_src) return ss;
-  const int64_t dd = (int64_t)h->cfg.dim * h->cfg.dim;
-  ss.ctr = h->src_ctr_d.get();
-  ss.nsteps = h->src.nsteps;
-  ss.is_static = h->src.is_static ? 1 : 0;
-  ss.weights = h->src.weights.empty() ? nullptr : h->src.weights_d.get();
-  ss.stride = (h->src.is_static || !h->src.weights.empty()) ? 0 : h->src.nnz * dd;
-  if (ss.stride == 0 && ss.weights == nullptr) ss.is_static = 1;
-  return ss;
-}
-// a source launch is due (the graphs of a capture hold source launches only while it is active, ensure_graphs) ...
-static bool source_due(const sg_handle* h) { return h->capture_src || source_active(h); }
-// ... with this step's slice and weight (separable source: the one stored slice, scaled); a capture: source_stepper's
-static const double* source_values(const sg_handle* h) {
-  const bool one_slice = h->capture_src || h->src.is_static || !h->src.weights.empty();
-  return h->src.values.get() + (size_t)(one_slice ? 0 : h->src_step) * h->src.nnz * h->cfg.dim * h->cfg.dim;
-}
-static double source_scale(const sg_handle* h) {
-  return (h->capture_src || h->src.weights.empty()) ? 1.0 : h->src.weights[(size_t)h->src_step];
+static SourceNow source_now(const sg_handle* h, const LaunchCtx& ctx) {
+  SourceNow sn;
+  sn.at = source_at(h, ctx.capture_src);
+  sn.values = h->src.values.get() + sn.at.offset;
+  std::memset(&sn.stepper, 0, sizeof(sn.stepper));
+  if (ctx.capture_src) {
+    sn.stepper.ctr = h->src_ctr_d.get();
+    sn.stepper.nsteps = sn.at.nsteps;
+    sn.stepper.stride = sn.at.stride;
+    sn.stepper.weights = sn.at.use_weights ? h->src.weights_d.get() : nullptr;
+    sn.stepper.is_static = sn.at.is_static ? 1 : 0;
+  }
+  return sn;
 }
 
-// the arguments of a stage launch (kernels.hpp StageArgs) but for the region's boxes and items
-static int stage_args(sg_handle* h, StageArgs& a, const StageOp& op, int region) {
+// the arguments of a stage launch (kernels.hpp StageArgs) but for the region's boxes and items and the output (run_op)
+static int stage_args(sg_handle* h, const LaunchCtx& ctx, StageArgs& a, const StageOp& op, int region) {
   const int kind = op.kind;
   if (kind != 0 && kind != 1) return fail(h, SG_ERR_ARG, "unknown stage");
   std::memset(&a, 0, sizeof(a));
-  a.in = h->field[op.in].get();
-  a.out = h->field[op.out].get();
-  a.aux = op.aux >= 0 ? h->field[op.aux].get() : nullptr;
-  a.uabs = h->field[op.uabs].get();
+  a.in = h->field.read(op.in);
+  a.aux = op.aux >= 0 ? h->field.read(op.aux) : nullptr;
+  a.uabs = h->field.read(op.uabs);
   for (int s = 0; s < 6; ++s) {
     a.ghost[s] = h->ghost[op.in][s];
     // required for interior launches too: masked boundary lanes still form (and load through) the pointer
@@ -53,7 +59,7 @@ static int stage_args(sg_handle* h, StageArgs& a, const StageOp& op, int region)
   a.mk = h->mk_dev.get();
   a.ftab = h->ftab_dev.get();
   a.nbr_tab = h->nbr_tab.get();
-  a.name_out = h->name_out;
+  a.name_out = ctx.name_out;
   a.all_active = region == SG_REGION_ALL ? 1 : 0;
   a.tensor = h->re.kind == KIND_TENSOR ? 1 : 0;
   a.fragV = (kind == 0) ? h->fragF.get() : h->fragG.get();
@@ -81,50 +87,43 @@ static int stage_args(sg_handle* h, StageArgs& a, const StageOp& op, int region)
   a.c_self = op.c_self;
   a.c_aux = op.c_aux;
   a.c_new = op.c_new;
-  if (kind == 0 && op.in == SG_FIELD_S && op.mode == 0 && h->capture_src && h->src.fused) {
+  if (!h->src.fused) return SG_OK;
+  const SourceNow sn = source_now(h, ctx);
+  if (kind == 0 && op.in == SG_FIELD_S && op.mode == 0 && ctx.capture_src) {
     // stage UH1 of a captured step on the tile path: the launch that opens the step also names it
-    a.src_step = source_stepper(h);
+    a.src_step = sn.stepper;
     a.src_bump = 1;
   }
-  if (op.with_source && h->src.fused && source_due(h)) {   // tile path: the G kernel adds the source values
+  if (op.with_source && sn.at.due) {   // tile path: the G kernel adds the source values
     a.src_slot = h->src.slot.get();
     a.src_idx = h->src.idx.get();
-    a.src_vals = source_values(h);
-    a.src_scale = source_scale(h);
-    a.src_step = source_stepper(h);
+    a.src_vals = sn.values;
+    a.src_scale = sn.at.scale;
+    a.src_step = sn.stepper;
   }
   return SG_OK;
 }
 
 // The sponge pre-pass of an F stage (SpongeTables::pre): B_e u_abs of the sponge cells, queued before anything of the stage
-// writes, at the first launch of the stage - whichever region the caller starts with: the same stage again, or a region it
-// has already seen, is the next instance of the stage - unless the buffer already holds it.  A naming pass changes nothing.
-static int sponge_pre_pass(sg_handle* h, const StageOp& op, int region) {
+// writes, when the buffer does not hold it yet (hostlogic.hpp PrePass).  A naming pass changes nothing.
+static int sponge_pre_pass(sg_handle* h, const LaunchCtx& ctx, const StageOp& op, int region) {
   SpongeTables& sp = h->sponge;
-  if (op.kind != 0 || !sp.pre.get() || h->name_out) return SG_OK;
-  const int key = op.out * 4 + op.mode, uabs_f = op.uabs;
-  bool first_of_stage = key != sp.pre_key || (sp.pre_regions & (1 << region)) != 0 || region == SG_REGION_ALL;
-  if (first_of_stage) sp.pre_regions = 0;
-  sp.pre_key = key;
-  sp.pre_regions |= 1 << region;
-  if (!first_of_stage || (sp.pre_field == uabs_f && sp.pre_ver == h->fver[uabs_f])) return SG_OK;   // the buffer holds it
-  sp.pre_field = uabs_f;
-  sp.pre_ver = h->fver[uabs_f];
-  const void* uabs = h->field[uabs_f].get();
+  if (!sp.pre.get() || ctx.name_out || !sp.pre_state.due(op, region, h->field.versions())) return SG_OK;
+  const void* uabs = h->field.read(op.uabs);
   // the cells with a sponge matrix
   if (launch_sponge_pre(uabs, sp.B.get(), sp.cells.get(), sp.mat.get(), sp.mat_slots.get(), sp.pre.get(), sp.nmat_slots, h->re.nd,
-                        h->cfg.dim, h->ncls, (int)h->md.gw, sp.pre_lines, h->f32, h->stream) != 0)
+                        h->cfg.dim, h->ncls, (int)h->md.gw, sp.pre_lines, h->f32, ctx.stream) != 0)
     return fail(h, SG_ERR_DEVICE, "sponge pre-pass launch failed");
   // ... and the cells whose sigma is affine in the reference coordinates: dim + 1 numbers per cell, element-constant matrices
   const int arc = sp.aff_frag.get()
                       ? launch_sponge_affine_mfma(h->cfg.degree, uabs, sp.aff_frag.get(), sp.aff_items.get(), sp.aff_slots.get(),
-                                                  sp.aff_coef.get(), sp.pre.get(), sp.aff_nitems, sp.aff_grid, h->stream)
+                                                  sp.aff_coef.get(), sp.pre.get(), sp.aff_nitems, sp.aff_grid, ctx.stream)
                       : launch_sponge_pre_affine(uabs, sp.aff_X.get(), sp.aff_col.get(), sp.aff_W, sp.aff_items.get(),
                                                  sp.aff_slots.get(), sp.aff_coef.get(), sp.pre.get(), sp.aff_nitems, h->re.nd,
-                                                 h->cfg.dim, (int)h->md.gw, sp.pre_lines, h->f32, sp.aff_grid, h->stream);
+                                                 h->cfg.dim, (int)h->md.gw, sp.pre_lines, h->f32, sp.aff_grid, ctx.stream);
   if (arc != 0) return fail(h, SG_ERR_DEVICE, "affine-sigma sponge pre-pass launch failed");
   // SECOND runs on its own stream after ev_stage - "everything before this stage's FIRST" - and reads the pre-pass too
-  if (region == SG_REGION_FIRST && h->overlap && h->first_recorded_stage >= 0) HIPCHECK(h, hipEventRecord(h->ev_stage, h->stream));
+  if (region == SG_REGION_FIRST && h->overlap && h->first_recorded_stage >= 0) HIPCHECK(h, hipEventRecord(h->ev_stage, ctx.stream));
   return SG_OK;
 }
 
@@ -144,23 +143,23 @@ static int region_items(sg_handle* h, int region, const std::vector<Box>& boxes)
 }
 
 // one launch of the family's stage kernel (a naming pass: its name, kernels.hpp SG_LAUNCH)
-static int launch_family(sg_handle* h, int kind, const StageArgs& a) {
+static int launch_family(sg_handle* h, const LaunchCtx& ctx, int kind, const StageArgs& a) {
   const int P = h->cfg.degree;
   const long ngroups = (long)(h->md.ncube_pad / h->md.gw);
   int rc = 0;
   switch (h->family) {
-    case Family::Generic: rc = launch_stage(kind, h->cfg.dim, P, a, h->stream); break;
-    case Family::Lane: rc = launch_stage_lane(kind, h->cfg.dim, P, a, ngroups * h->ncls, h->stream); break;
-    case Family::Mfma: rc = launch_stage_mfma(kind, P, a, h->stream); break;
-    case Family::Tile2d: rc = launch_stage_tile2d(kind, P, a, h->t2c, ngroups * h->ncls, h->stream); break;
-    case Family::Hexm: rc = launch_stage_hexm(kind, P, a, ngroups, h->stream); break;
+    case Family::Generic: rc = launch_stage(kind, h->cfg.dim, P, a, ctx.stream); break;
+    case Family::Lane: rc = launch_stage_lane(kind, h->cfg.dim, P, a, ngroups * h->ncls, ctx.stream); break;
+    case Family::Mfma: rc = launch_stage_mfma(kind, P, a, ctx.stream); break;
+    case Family::Tile2d: rc = launch_stage_tile2d(kind, P, a, h->t2c, ngroups * h->ncls, ctx.stream); break;
+    case Family::Hexm: rc = launch_stage_hexm(kind, P, a, ngroups, ctx.stream); break;
   }
   return rc != 0 ? fail(h, SG_ERR_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString((hipError_t)rc)) : SG_OK;
 }
 
 // the launches of a region: one per box for the generic kernels; the other families scan all cell groups and mask lanes
 // by box in one launch
-static int launch_region(sg_handle* h, int kind, int region, StageArgs& a) {
+static int launch_region(sg_handle* h, const LaunchCtx& ctx, int kind, int region, StageArgs& a) {
   std::vector<Box> boxes;
   region_boxes(h, region, boxes);
   if (!family_interleaved(h->family)) {
@@ -168,7 +167,7 @@ static int launch_region(sg_handle* h, int kind, int region, StageArgs& a) {
       if (b.n[0] <= 0 || b.n[1] <= 0 || b.n[2] <= 0) continue;
       std::memcpy(a.box_o, b.o, sizeof(a.box_o));
       std::memcpy(a.box_n, b.n, sizeof(a.box_n));
-      if (int rc = launch_family(h, kind, a)) return rc;
+      if (int rc = launch_family(h, ctx, kind, a)) return rc;
     }
     return SG_OK;
   }
@@ -199,14 +198,15 @@ static int launch_region(sg_handle* h, int kind, int region, StageArgs& a) {
     if (family_whole_groups(h->family) && h->region_whole[region] && !h->no_whole) a.all_active = 1;
   }
   a.nitems = a.item_list ? a.nlist : (int32_t)std::min<int64_t>((h->md.ncube_pad / h->md.gw) * h->ncls, INT32_MAX);
-  return launch_family(h, kind, a);
+  return launch_family(h, ctx, kind, a);
 }
 
 // the source lives on single nodes: added to each part of a split stage right after the launch
 // that wrote it (INTERIOR + BOUNDARY: all of it after the second launch)
-static int add_source(sg_handle* h, int field, double coef, int region) {
-  if (h->src.fused || h->name_out) return SG_OK;  // added by the stage kernel (stage_args) / a naming pass launches nothing
-  if (!source_due(h) || region == SG_REGION_INTERIOR) return SG_OK;
+static int add_source(sg_handle* h, const LaunchCtx& ctx, int field, double coef, int region) {
+  if (h->src.fused || ctx.name_out) return SG_OK;  // added by the stage kernel (stage_args) / a naming pass launches nothing
+  const SourceNow sn = source_now(h, ctx);
+  if (!sn.at.due || region == SG_REGION_INTERIOR) return SG_OK;
   const int d = h->cfg.dim;
   int64_t off = 0, cnt = h->src.nnz;
   if (region == SG_REGION_FIRST) cnt = h->src.nfirst;
@@ -215,24 +215,26 @@ static int add_source(sg_handle* h, int field, double coef, int region) {
     cnt = h->src.nnz - h->src.nfirst;
   }
   if (cnt == 0) return SG_OK;
-  int rc = launch_source(h->field[field].get(), d * d, h->md.gw, cnt, h->src.nodes.get() + off, source_values(h) + off * d * d, coef,
-                         source_scale(h), source_stepper(h), h->f32, h->stream);
+  int rc = launch_source(h->field.write(field), d * d, h->md.gw, cnt, h->src.nodes.get() + off, sn.values + off * d * d, coef, sn.at.scale,
+                         sn.stepper, h->f32, ctx.stream);
   return rc != 0 ? fail(h, SG_ERR_DEVICE, "source kernel launch failed") : SG_OK;
 }
 
 // Everything one stage launch queues, in this order: the sponge pre-pass, the region's kernels, and the source of a G
 // stage that has one - inside those kernels (2-D tile family, stage_args) or by add_source: chosen here, for every caller.
-static int run_op(sg_handle* h, const StageOp& op, int region) {
+static int run_op(sg_handle* h, const LaunchCtx& ctx, const StageOp& op, int region) {
   StageArgs a;
-  if (int rc = stage_args(h, a, op, region)) return rc;
-  if (int rc = sponge_pre_pass(h, op, region)) return rc;
-  if (!h->name_out) mark_field_written(h, op.out);     // (after the pre-pass decision: an in-place stage absorbs the state it overwrites)
-  if (int rc = launch_region(h, op.kind, region, a)) return rc;
-  return op.with_source ? add_source(h, op.out, op.src_coef, region) : SG_OK;
+  if (int rc = stage_args(h, ctx, a, op, region)) return rc;
+  if (int rc = sponge_pre_pass(h, ctx, op, region)) return rc;
+  // the output counts as written from here on, i.e. after the pre-pass was decided (hostlogic.hpp PrePass::due); a naming
+  // pass writes nothing
+  a.out = ctx.name_out ? nullptr : h->field.write(op.out);
+  if (int rc = launch_region(h, ctx, op.kind, region, a)) return rc;
+  return op.with_source ? add_source(h, ctx, op.out, op.src_coef, region) : SG_OK;
 }
 
-static int run_stage_impl(sg_handle* h, int stage, int region) {
-  return run_op(h, lf4_stage(stage, h->dt, h->rho, h->rho_physical != 0, h->rho2_d.get() != nullptr), region);
+static int run_stage_impl(sg_handle* h, const LaunchCtx& ctx, int stage, int region) {
+  return run_op(h, ctx, lf4_stage(stage, h->dt, h->rho, h->rho_physical != 0, h->rho2_d.get() != nullptr), region);
 }
 
 int resolve_timing(sg_handle* h) {
@@ -321,18 +323,16 @@ int sg_run_stage(sg_handle* h, int stage, int region) {
       h->first_recorded_stage = stage;
     }
   }
-  hipStream_t const main_stream = h->stream, s = second ? h->stream2 : h->stream;
+  const LaunchCtx ctx{second ? h->stream2 : h->stream};
   size_t k = 0;
-  int rc = timing_begin(h, s, k);     // (a flush of the pending pairs resolves them on the main stream: h->stream is still that)
+  int rc = timing_begin(h, ctx.stream, k);
   if (rc != SG_OK) return rc;
-  h->stream = s;
-  rc = run_stage_impl(h, stage, region);
-  if (rc == SG_OK) rc = timing_end(h, s, k, stage + ((h->overlap && region == SG_REGION_FIRST) ? 16 : (second ? 32 : 0)));
+  rc = run_stage_impl(h, ctx, stage, region);
+  if (rc == SG_OK) rc = timing_end(h, ctx.stream, k, stage + ((h->overlap && region == SG_REGION_FIRST) ? 16 : (second ? 32 : 0)));
   if (second) {
     if (rc == SG_OK && hipEventRecord(h->ev_second, h->stream2) != hipSuccess) rc = fail(h, SG_ERR_DEVICE, "hipEventRecord failed");
     h->second_pending = rc == SG_OK;
   }
-  h->stream = main_stream;
   if (rc != SG_OK) return rc;
   h->counters.launches[stage] += 1;
   return SG_OK;
@@ -342,20 +342,20 @@ int sg_run_stage(sg_handle* h, int stage, int region) {
 // the main stream behind stage S1's SECOND launch.  Eager launches name the step by value and count it here; the launches
 // of a capture read it from rec.ctr and bump that (sg_step sets it before it replays and counts the replayed steps).
 // SG_ERR_STATE, nothing queued and nothing counted: the step is due a sample the trace has no room for.
-static int record_step(sg_handle* h) {
+static int record_step(sg_handle* h, const LaunchCtx& ctx) {
   ReceiverTables& rt = h->rec;
-  if (rt.nrec == 0 || h->name_out) return SG_OK;
-  const int64_t step = rt.steps + 1;
-  if (!h->capture_rec && step % rt.every == 0 && step / rt.every > rt.capacity)
+  if (rt.nrec == 0 || ctx.name_out) return SG_OK;
+  const int64_t step = rt.clock.steps + 1;
+  if (!ctx.capture_rec && rt.clock.no_room_at(step))
     return fail(h, SG_ERR_STATE, "receiver trace full: read it out (sg_get_receivers) and re-arm before stepping on");
   if (rt.nown > 0) {
     if (int rc = join_second(h)) return rc;
     RecvArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.ctr = h->capture_rec ? rt.ctr.get() : nullptr;
+    a.ctr = ctx.capture_rec ? rt.ctr.get() : nullptr;
     a.step = step;
-    a.every = rt.every;
-    a.capacity = rt.capacity;
+    a.every = rt.clock.every;
+    a.capacity = rt.clock.capacity;
     a.item = rt.item.get();
     a.lane = rt.lane.get();
     a.phi = rt.phi.get();
@@ -367,12 +367,12 @@ static int record_step(sg_handle* h) {
     a.nd = h->re.nd;
     a.gw = (int32_t)h->md.gw;
     a.sym = h->sym ? 1 : 0;
-    if (launch_receivers(h->field[SG_FIELD_U].get(), h->field[SG_FIELD_S].get(), a, h->f32, h->stream) != 0)
+    if (launch_receivers(h->field.read(SG_FIELD_U), h->field.read(SG_FIELD_S), a, h->f32, ctx.stream) != 0)
       return fail(h, SG_ERR_DEVICE, "receiver launch failed");
-    if (h->capture_rec && launch_step_counter(rt.ctr.get(), 1, 1, h->stream) != 0)
+    if (ctx.capture_rec && launch_step_counter(rt.ctr.get(), 1, 1, ctx.stream) != 0)
       return fail(h, SG_ERR_DEVICE, "step counter launch failed");
   }
-  if (!h->capture_rec) rt.steps = step;
+  if (!ctx.capture_rec) rt.clock.steps = step;
   return SG_OK;
 }
 
@@ -383,37 +383,37 @@ static void steps_done(sg_handle* h, int64_t n, bool replayed) {
   h->counters.steps += n;
   if (!replayed) return;
   for (int st = 0; st < 6; ++st) h->counters.launches[st] += n;
-  if (h->rec.nrec > 0) h->rec.steps += n;
-  for (int f = 0; f < 4; ++f) mark_field_written(h, f);
-  h->sponge.pre_ver = ~0ull;
+  if (h->rec.nrec > 0) h->rec.clock.steps += n;
+  h->field.replayed();
+  h->sponge.pre_state.forget();
 }
 
 int sg_end_step(sg_handle* h) {
   if (!h) return SG_ERR_ARG;
   HIPCHECK(h, hipSetDevice(h->cfg.device));
-  if (int rc = record_step(h)) return rc;
+  if (int rc = record_step(h, LaunchCtx{h->stream})) return rc;
   steps_done(h, 1, false);
   return SG_OK;
 }
 
 // one LF4 step = six whole-block launches on the handle's stream (elastic.py:291-304).  counted: the eager steps of
 // sg_step, which count their launches, through sg_run_stage (an event pair per launch) when timing is on.
-static int run_stages(sg_handle* h, bool counted) {
+static int run_stages(sg_handle* h, const LaunchCtx& ctx, bool counted) {
   for (int st = 0; st < 6; ++st) {
     const bool timed = counted && h->timing;
-    if (int rc = timed ? sg_run_stage(h, st, SG_REGION_ALL) : run_stage_impl(h, st, SG_REGION_ALL)) return rc;
+    if (int rc = timed ? sg_run_stage(h, st, SG_REGION_ALL) : run_stage_impl(h, ctx, st, SG_REGION_ALL)) return rc;
     if (counted && !timed) h->counters.launches[st] += 1;
   }
   return SG_OK;
 }
 
 // ... and what ends it on the stream; counted = false: a step of a capture
-static int enqueue_step(sg_handle* h, bool counted) {
-  if (int rc = run_stages(h, counted)) return rc;
+static int enqueue_step(sg_handle* h, const LaunchCtx& ctx, bool counted) {
+  if (int rc = run_stages(h, ctx, counted)) return rc;
   // the next step's slice (tile path: stage UH1 bumps the counter itself, stage_args)
-  if (h->capture_src && !h->src.fused && launch_step_counter(h->src_ctr_d.get(), 1, 1, h->stream) != 0)
+  if (ctx.capture_src && !h->src.fused && launch_step_counter(h->src_ctr_d.get(), 1, 1, ctx.stream) != 0)
     return fail(h, SG_ERR_DEVICE, "step counter launch failed");
-  return record_step(h);
+  return record_step(h, ctx);
 }
 
 // capture `steps` steps into an executable graph; on any failure graphs are switched off for the handle
@@ -423,18 +423,13 @@ static hipGraphExec_t capture_steps(sg_handle* h, int steps, bool with_src) {
   // a dry pass through the launch code (nothing is queued): what a launcher asks the runtime once per kernel
   // instantiation - the resident blocks of the 2-D tile kernels - is asked here, outside the capture
   std::string name;
-  h->name_out = &name;
-  (void)run_stages(h, false);
-  h->name_out = nullptr;
+  (void)run_stages(h, LaunchCtx{h->stream, &name}, false);
   if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return nullptr;
   int rc = SG_OK;
-  h->capture_src = with_src;
-  h->capture_rec = h->rec.nrec > 0;
-  h->sponge.pre_ver = ~0ull;      // a replay starts from whatever the buffer holds: the captured step computes its own
-  for (int k = 0; k < steps && rc == SG_OK; ++k) rc = enqueue_step(h, false);
-  h->sponge.pre_ver = ~0ull;      // nothing was launched: the buffer holds what it held
-  h->capture_src = false;
-  h->capture_rec = false;
+  const LaunchCtx ctx{h->stream, nullptr, with_src, h->rec.nrec > 0};
+  h->sponge.pre_state.forget();      // a replay starts from whatever the buffer holds: the captured step computes its own
+  for (int k = 0; k < steps && rc == SG_OK; ++k) rc = enqueue_step(h, ctx, false);
+  h->sponge.pre_state.forget();      // nothing was launched: the buffer does not hold what the capture asked for
   hipError_t e = hipStreamEndCapture(h->stream, &g);
   if (rc == SG_OK && e == hipSuccess && g) {
     if (hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) != hipSuccess) ge = nullptr;
@@ -446,17 +441,17 @@ static hipGraphExec_t capture_steps(sg_handle* h, int steps, bool with_src) {
 
 // the receivers' samples of all nsteps steps must fit the trace: checked before anything is queued (native exchange too)
 static int check_receiver_room(sg_handle* h, int64_t nsteps) {
-  const ReceiverTables& rt = h->rec;
-  if (rt.nrec == 0 || (rt.steps + nsteps) / rt.every <= rt.capacity) return SG_OK;
-  return fail(h, SG_ERR_STATE, "sg_step: the receiver trace has room for " + std::to_string(rt.capacity - rt.samples()) +
-                                   " more samples, these steps take " + std::to_string((rt.steps + nsteps) / rt.every - rt.samples()));
+  const ReceiverClock& c = h->rec.clock;
+  if (h->rec.nrec == 0 || c.fits(nsteps)) return SG_OK;
+  return fail(h, SG_ERR_STATE, "sg_step: the receiver trace has room for " + std::to_string(c.capacity - c.samples()) +
+                                   " more samples, these steps take " + std::to_string(c.samples_after(nsteps) - c.samples()));
 }
 
 // The graphs of one and of eight steps, captured again when a setter changed kernel arguments (epoch) or the source or the
 // receivers came or went.  A source that is still active is part of them: its launches take the step's slice and weight from
 // a device-side counter (kernels.hpp SrcStep); one that has run out, or none: no source launches.  Armed receivers likewise.
 static int ensure_graphs(sg_handle* h) {
-  const bool with_src = source_active(h), with_rec = h->rec.nrec > 0;
+  const bool with_src = source_at(h, false).active, with_rec = h->rec.nrec > 0;
   if (with_src && !h->src_ctr_d.get()) return fail(h, SG_ERR_STATE, "source without a device-side step counter");
   if (h->graph_epoch == h->epoch && h->graph_src == with_src && h->graph_rec == with_rec) return SG_OK;
   if (h->graph1) (void)hipGraphExecDestroy(h->graph1);
@@ -475,7 +470,7 @@ static int replay_steps(sg_handle* h, int64_t nsteps) {
   // (tile path: the counter is bumped by the launch that OPENS a step, so it starts one short)
   if (h->graph_src && launch_step_counter(h->src_ctr_d.get(), h->src_step - (h->src.fused ? 1 : 0), 0, h->stream) != 0)
     return fail(h, SG_ERR_DEVICE, "step counter launch failed");
-  if (h->rec.nown > 0 && launch_step_counter(h->rec.ctr.get(), h->rec.steps, 0, h->stream) != 0)
+  if (h->rec.nown > 0 && launch_step_counter(h->rec.ctr.get(), h->rec.clock.steps, 0, h->stream) != 0)
     return fail(h, SG_ERR_DEVICE, "step counter launch failed");
   int64_t k = 0;
   for (; k + 8 <= nsteps; k += 8) HIPCHECK(h, hipGraphLaunch(h->graph8, h->stream));
@@ -486,7 +481,7 @@ static int replay_steps(sg_handle* h, int64_t nsteps) {
 
 static int eager_steps(sg_handle* h, int64_t nsteps) {
   for (int64_t k = 0; k < nsteps; ++k) {
-    if (int rc = enqueue_step(h, true)) return rc;
+    if (int rc = enqueue_step(h, LaunchCtx{h->stream}, true)) return rc;
     steps_done(h, 1, false);
   }
   return SG_OK;
@@ -523,7 +518,7 @@ int sg_apply_F(sg_handle* h, int s_in, int u_abs, int u_out) {
   if (!field_is_stress(s_in) || field_is_stress(u_out) || field_is_stress(u_abs) || u_abs == u_out)
     return fail(h, SG_ERR_ARG, "sg_apply_F: s_in must be a stress field, u_abs/u_out distinct velocity fields");
   HIPCHECK(h, hipSetDevice(h->cfg.device));
-  return run_op(h, StageOp{0, s_in, u_out, -1, u_abs}, SG_REGION_ALL);
+  return run_op(h, LaunchCtx{h->stream}, StageOp{0, s_in, u_out, -1, u_abs}, SG_REGION_ALL);
 }
 
 int sg_apply_G(sg_handle* h, int u_in, int s_out, int use_source) {
@@ -534,7 +529,7 @@ int sg_apply_G(sg_handle* h, int u_in, int s_out, int use_source) {
   HIPCHECK(h, hipSetDevice(h->cfg.device));
   StageOp op{1, u_in, s_out};
   op.with_source = use_source != 0;
-  return run_op(h, op, SG_REGION_ALL);
+  return run_op(h, LaunchCtx{h->stream}, op, SG_REGION_ALL);
 }
 
 // ---- halo ---------------------------------------------------------------------------------
@@ -576,7 +571,7 @@ int sg_halo_pack_sides(sg_handle* h, int field, void* const* dev_out) {
   size_t k = 0, total = 0;
   int rc = timing_begin(h, h->stream, k);     // pack launches are timed like stage launches (stage id 6)
   if (rc != SG_OK) return rc;
-  rc = launch_pack(h->md_dev.get(), h->md, h->field[field].get(), comps, n, sides, outs,
+  rc = launch_pack(h->md_dev.get(), h->md, h->field.read(field), comps, n, sides, outs,
                    (h->sym && field_is_stress(field)) ? 1 : 0, h->f32, h->stream);
   if (rc != 0) return fail(h, SG_ERR_DEVICE, "pack kernel launch failed");
   for (int i = 0; i < n; ++i) {
@@ -624,10 +619,7 @@ int sg_stage_kernel_name(sg_handle* h, int stage, int region, char* buf, size_t 
   // the stage's own launch code with StageArgs::name_out set: the dispatch that picks the instantiation is the one
   // that would launch it (kernels.hpp SG_LAUNCH); nothing is queued on the stream
   std::string name;
-  h->name_out = &name;
-  const int rc = run_stage_impl(h, stage, region);
-  h->name_out = nullptr;
-  if (rc != SG_OK) return rc;
+  if (int rc = run_stage_impl(h, LaunchCtx{h->stream, &name}, stage, region)) return rc;
   std::snprintf(buf, n, "%s", name.c_str());
   return SG_OK;
 }

@@ -8,8 +8,7 @@ int leave_sym_mode(sg_handle* h) {
   h->epoch += 1;
   if (!h->sym) return SG_OK;
   for (int f : {SG_FIELD_S, SG_FIELD_SH}) {
-    mark_field_written(h, f);
-    if (launch_mirror(h->md, h->field[f].get(), h->f32, h->stream) != 0) return fail(h, SG_ERR_DEVICE, "mirror kernel launch failed");
+    if (launch_mirror(h->md, h->field.write(f), h->f32, h->stream) != 0) return fail(h, SG_ERR_DEVICE, "mirror kernel launch failed");
   }
   HIPCHECK(h, sync_all(h));
   h->sym = false;
@@ -42,7 +41,7 @@ static constexpr size_t XFER_CHUNK_BYTES = (size_t)64 << 20;
 // copies the previous pinned slot into the caller's (pageable) array on several threads.  Downloads only:
 // uploads from pageable memory already run at 47 GB/s inside the runtime.  A plain hipMemcpy to pageable memory runs at 11 GB/s (one staging thread inside the
 // runtime); this pipeline is bound by the link.
-static int download_pipelined(sg_handle* h, int field, int64_t cell0, int64_t ncells, double* host) {
+static int download_pipelined(sg_handle* h, int field, double* dev, int64_t cell0, int64_t ncells, double* host) {
   const size_t per_cell = h->field_len[field] / (size_t)h->ncells;
   const int comps = (int)(per_cell / h->re.nd);
   const size_t chunk_cells = std::max<size_t>(1, XFER_CHUNK_BYTES / (per_cell * sizeof(double)));
@@ -65,9 +64,9 @@ static int download_pipelined(sg_handle* h, int field, int64_t cell0, int64_t nc
       range(c, c0, n);
       const size_t nb = (size_t)n * per_cell * sizeof(double);
       if (h->md.gw == 1) {
-        HIPCHECK(h, hipMemcpyAsync(h->pin[sl], h->field[field].get() + (size_t)(cell0 + c0) * per_cell, nb, hipMemcpyDeviceToHost, h->stream));
+        HIPCHECK(h, hipMemcpyAsync(h->pin[sl], dev + (size_t)(cell0 + c0) * per_cell, nb, hipMemcpyDeviceToHost, h->stream));
       } else {
-        if (launch_layout(h->md, comps, 1, h->field[field].get(), h->dstage[sl].get(), cell0 + c0, n, symdl, nullptr, h->f32, h->stream) != 0)
+        if (launch_layout(h->md, comps, 1, dev, h->dstage[sl].get(), cell0 + c0, n, symdl, nullptr, h->f32, h->stream) != 0)
           return fail(h, SG_ERR_DEVICE, "layout kernel launch failed");
         HIPCHECK(h, hipMemcpyAsync(h->pin[sl], h->dstage[sl].get(), nb, hipMemcpyDeviceToHost, h->stream));
       }
@@ -89,15 +88,16 @@ static int transfer(sg_handle* h, int field, int64_t cell0, int64_t ncells, doub
   HIPCHECK(h, hipSetDevice(h->cfg.device));
   if (int rc = join_second(h)) return rc;
   HIPCHECK(h, sync_all(h));
-  if (to_device) mark_field_written(h, field);
+  // (the layout kernel takes one pointer for both directions: a download reads through it)
+  double* const dev_field = to_device ? h->field.write(field) : const_cast<double*>(h->field.read(field));
   const size_t per_cell = h->field_len[field] / (size_t)h->ncells;
   // downloads only: uploads from pageable memory already run at 47 GB/s inside the runtime (measured,
   // tools/transfer_rate.py: 35 GB/s through this pipeline)
   if (!to_device && (size_t)ncells * per_cell * sizeof(double) >= ((size_t)16 << 20) && !std::getenv("SEIGEN_HIP_PLAIN_COPY")) {
-    return download_pipelined(h, field, cell0, ncells, host);
+    return download_pipelined(h, field, dev_field, cell0, ncells, host);
   }
   if (h->md.gw == 1) {
-    double* dev = h->field[field].get() + (size_t)cell0 * per_cell;
+    double* dev = dev_field + (size_t)cell0 * per_cell;
     size_t nb = (size_t)ncells * per_cell * sizeof(double);
     if (to_device)
       HIPCHECK(h, hipMemcpy(dev, host, nb, hipMemcpyHostToDevice));
@@ -123,12 +123,12 @@ static int transfer(sg_handle* h, int field, int64_t cell0, int64_t ncells, doub
     if (to_device) {
       HIPCHECK(h, hipMemcpy(h->staging.get(), host + (size_t)done * per_cell, nb, hipMemcpyHostToDevice));
       int* flag = (h->sym && field_is_stress(field)) ? h->sym_flag.get() : nullptr;
-      if (launch_layout(h->md, comps, 0, h->field[field].get(), h->staging.get(), cell0 + done, n, 0, flag, h->f32, h->stream) != 0)
+      if (launch_layout(h->md, comps, 0, dev_field, h->staging.get(), cell0 + done, n, 0, flag, h->f32, h->stream) != 0)
         return fail(h, SG_ERR_DEVICE, "layout kernel launch failed");
       HIPCHECK(h, sync_all(h));
     } else {
       const int symdl = (h->sym && field_is_stress(field)) ? 1 : 0;
-      if (launch_layout(h->md, comps, 1, h->field[field].get(), h->staging.get(), cell0 + done, n, symdl, nullptr, h->f32, h->stream) != 0)
+      if (launch_layout(h->md, comps, 1, dev_field, h->staging.get(), cell0 + done, n, symdl, nullptr, h->f32, h->stream) != 0)
         return fail(h, SG_ERR_DEVICE, "layout kernel launch failed");
       HIPCHECK(h, sync_all(h));
       HIPCHECK(h, hipMemcpy(host + (size_t)done * per_cell, h->staging.get(), nb, hipMemcpyDeviceToHost));

@@ -1,6 +1,6 @@
 // CPU sanitizer driver (SURVEY 5 "sanitizers"; `make -C seigen_amd/csrc host-asan`): everything of libseigen_hip that
 // needs no device - reference elements, mesh tables, MFMA fragment tables, the sponge, source and receiver plans, the items
-// of split-stage regions, the device-free C-ABI entry points - built with
+// of split-stage regions, the stage table, what stepping remembers between calls, the device-free C-ABI entry points - built with
 // -fsanitize=address,undefined and walked over every (dim, degree, cell type, diagonal) the library accepts, plus the
 // argument errors the entry points must refuse.  Exit code 0 and no sanitizer report = clean.
 #include <algorithm>
@@ -847,6 +847,244 @@ static void stage_table() {
   for (int k = 0; k < 6; ++k) std::printf("stage %d: %d %d\n", k, lf4_stage_input(k), lf4_stage_output(k));
 }
 
+// What stepping remembers between calls (hostlogic.hpp FieldVersions, PrePass, source_slice, ReceiverClock), against models
+// written out here that share nothing with them.
+//
+// The pre-pass: the model gives every field a content id, raised whenever a launch or an upload writes the field, and tags the
+// pre-pass buffer with the (field, content id) it was computed from.  A launch is described by the caller as the driver of a
+// real run would know it: the op, the region, and whether it is the first launch of a stage instance.
+struct PrePassModel {
+  FieldVersions fv;     // the values under test ...
+  PrePass pp;
+  int content[4] = {0, 0, 0, 0};   // ... and the model
+  int tag_field = -1, tag_id = -1;           // what the buffer holds (-1: nothing known)
+  int want_field = -1, want_id = -1;         // what the running F stage must find in it
+  int passes = 0;
+
+  void launch(const StageOp& op, int region, bool first_of_instance) {
+    const bool due = pp.due(op, region, fv);
+    if (op.kind == 0) {
+      if (first_of_instance) {
+        want_field = op.uabs;
+        want_id = content[op.uabs];
+      }
+      // the model's rule: compute at the first launch of an instance, unless the buffer holds exactly that state
+      EXPECT(due == (first_of_instance && !(tag_field == want_field && tag_id == want_id)));
+      if (due) {
+        passes += 1;
+        tag_field = op.uabs;
+        tag_id = content[op.uabs];
+      }
+      EXPECT(tag_field == want_field && tag_id == want_id);   // (a): every region of the stage reads the state of its first
+    } else {
+      EXPECT(!due);
+    }
+    fv.written(op.out);      // the launch writes its output: after the decision, as stages.cpp run_op takes the pointer
+    content[op.out] += 1;
+  }
+  void upload(int f) {
+    fv.written(f);
+    content[f] += 1;
+  }
+  void forget() {
+    pp.forget();
+    tag_field = tag_id = -1;
+  }
+  // one LF4 step under a region schedule (0: whole block, 1: FIRST + SECOND, 2: INTERIOR + BOUNDARY); the pre-passes it ran
+  int step(int schedule) {
+    const int regions[3][2] = {{SG_REGION_ALL, -1}, {SG_REGION_FIRST, SG_REGION_SECOND}, {SG_REGION_INTERIOR, SG_REGION_BOUNDARY}};
+    const int before = passes;
+    for (int st = 0; st < 6; ++st) {
+      const StageOp op = lf4_stage(st, 1e-3, 1.0, false, false);
+      for (int r = 0; r < 2; ++r)
+        if (regions[schedule][r] >= 0) launch(op, regions[schedule][r], r == 0);
+    }
+    return passes - before;
+  }
+  // n captured steps: the capture forgets, walks the launch code (which counts writes although nothing runs), forgets again
+  int capture(int n) {
+    forget();
+    int total = 0;
+    for (int k = 0; k < n; ++k) total += step(0);
+    forget();
+    return total;
+  }
+  void replay() {    // whatever the graphs ran wrote all four fields; the model: new content everywhere, the buffer unknown
+    fv.replayed();
+    for (int& c : content) c += 1;
+    forget();
+  }
+};
+
+static void stepping_state() {
+  const int U = SG_FIELD_U, UH = SG_FIELD_UH, S = SG_FIELD_S, SH = SG_FIELD_SH;
+  // (b) two pre-passes in a handle's first step, one in every later step, under every region schedule
+  for (int schedule = 0; schedule < 3; ++schedule) {
+    PrePassModel m;
+    const int first = m.step(schedule);
+    EXPECT(first == 2);
+    for (int k = 0; k < 3; ++k) EXPECT(m.step(schedule) == 1);
+    // (c) what makes the next step compute UH1's pre-pass again: a new U, not a new stress; a forgotten buffer; a replay
+    m.upload(U);
+    EXPECT(m.step(schedule) == 2);
+    m.upload(S);
+    EXPECT(m.step(schedule) == 1);
+    m.upload(SH);
+    EXPECT(m.step(schedule) == 1);
+    m.upload(UH);     // (UTEMP overwrites it before anything absorbs it)
+    EXPECT(m.step(schedule) == 1);
+    m.forget();
+    EXPECT(m.step(schedule) == 2);
+    for (int n : {1, 2, 8, 11}) {
+      m.replay();
+      (void)n;        // (however many steps the replay ran: the host saw none of their launches)
+      EXPECT(m.step(schedule) == 2);
+      EXPECT(m.step(schedule) == 1);
+    }
+    // the graphs of one and of eight steps, captured between eager steps; the step after them starts afresh
+    EXPECT(m.capture(1) == 2);
+    EXPECT(m.capture(8) == 9);
+    EXPECT(m.step(schedule) == 2);
+    EXPECT(m.step(schedule) == 1);
+    // the schedules mixed from step to step: a stage's regions change, the field states do not
+    for (int k = 0; k < 6; ++k) EXPECT(m.step((schedule + k) % 3) == 1);
+  }
+  // the order run_op keeps - decide, then count the output as written - is what (a) rests on for the in-place stage U1:
+  // counted first, U1's pre-pass of u0 would pass for one of the u1 it writes, and UTEMP would absorb the step before
+  {
+    FieldVersions fv;
+    PrePass pp;
+    const StageOp u1 = lf4_stage(2, 1e-3, 1.0, false, false), utemp = lf4_stage(4, 1e-3, 1.0, false, false);
+    fv.written(u1.out);
+    EXPECT(pp.due(u1, SG_REGION_ALL, fv) && !pp.due(utemp, SG_REGION_ALL, fv));
+  }
+  // un-fused F applications (sg_apply_F) absorbing U and UH in turn, G applications and stage launches between them
+  {
+    PrePassModel m;
+    const StageOp f_u{0, S, UH, -1, U}, f_uh{0, SH, U, -1, UH}, g{1, UH, S}, g2{1, U, SH};
+    m.launch(f_u, SG_REGION_ALL, true);
+    m.launch(f_u, SG_REGION_ALL, true);       // the same application again: the buffer holds it
+    EXPECT(m.passes == 1);
+    m.launch(g, SG_REGION_ALL, true);
+    m.launch(f_uh, SG_REGION_ALL, true);      // absorbs UH, which f_u wrote; writes U
+    EXPECT(m.passes == 2);
+    m.launch(f_u, SG_REGION_ALL, true);       // U is new
+    EXPECT(m.passes == 3);
+    m.launch(f_uh, SG_REGION_ALL, true);      // ... and so is UH
+    m.launch(g2, SG_REGION_ALL, true);
+    m.launch(f_uh, SG_REGION_FIRST, true);    // UH untouched since: the buffer holds it
+    EXPECT(m.passes == 4);
+    m.launch(f_uh, SG_REGION_SECOND, false);
+    m.launch(f_uh, SG_REGION_FIRST, true);    // a region seen before: the next instance, same state of UH
+    m.launch(f_u, SG_REGION_INTERIOR, true);
+    m.launch(f_u, SG_REGION_BOUNDARY, false);
+    EXPECT(m.step(0) == 1 && m.step(2) == 1);   // U has not moved since f_u absorbed it
+    m.launch(f_uh, SG_REGION_ALL, true);
+    EXPECT(m.step(0) == 2);                   // f_uh wrote U and left its own pre-pass behind
+  }
+  // a new state of the absorbed field between two instances of ONE stage: a region seen before, or the whole block after
+  // some regions, opens the next instance; and equal write counts of two fields are not the same state
+  {
+    PrePassModel m;
+    const StageOp f_u{0, S, UH, -1, U}, f_uh{0, S, U, -1, UH};
+    m.launch(f_u, SG_REGION_FIRST, true);
+    m.upload(U);
+    m.launch(f_u, SG_REGION_FIRST, true);
+    EXPECT(m.passes == 2);
+    m.launch(f_u, SG_REGION_INTERIOR, true);
+    m.launch(f_u, SG_REGION_BOUNDARY, false);
+    m.upload(U);
+    m.launch(f_u, SG_REGION_ALL, true);
+    EXPECT(m.passes == 3);
+    PrePassModel e;
+    e.upload(UH);
+    e.launch(f_uh, SG_REGION_ALL, true);     // absorbs UH after its one write, writes U once
+    e.launch(f_u, SG_REGION_ALL, true);      // absorbs U after its one write
+    EXPECT(e.passes == 2 && e.fv.v[U] == 1);
+  }
+  // G stages never ask, and a PrePass that has seen nothing asks at the first F launch
+  {
+    FieldVersions fv;
+    PrePass pp;
+    EXPECT(!pp.due(StageOp{1, U, S}, SG_REGION_ALL, fv));
+    EXPECT(pp.due(StageOp{0, S, UH, -1, U}, SG_REGION_ALL, fv));
+  }
+
+  // The source (seigen_hip.h sg_set_source, sg_set_source_separable): entry i of step k < nsteps adds values[k][i][dim * dim]
+  // of a table, weights[k] * pattern[i][dim * dim] of a separable source, values[0][i] at every step of a static one; nothing
+  // afterwards.  A capture made while the source is active hands slice and weight to the device (offset 0, scale 1, the
+  // strides and flags of kernels.hpp SrcStep); one made after it ran out holds no source launch.
+  for (int dim = 1; dim <= 3; ++dim)
+    for (int64_t nnz : {1, 5})
+      for (int64_t nsteps : {1, 3})
+        for (int form = 0; form < 3; ++form) {    // 0: table, 1: static, 2: separable
+          const std::vector<double> w = {0.5, -2.0, 4.0};
+          SourceFacts s;
+          s.nnz = nnz;
+          s.nsteps = form == 1 ? 1 : nsteps;      // (source_tables.cpp plan_source: a static source has one slice)
+          s.is_static = form == 1;
+          s.weights = form == 2 ? w.data() : nullptr;
+          s.dim = dim;
+          for (int64_t k = 0; k <= nsteps + 1; ++k) {
+            const bool runs = form == 1 || k < nsteps;
+            const SourceSlice e = source_slice(s, k, false);
+            EXPECT(e.active == runs && e.due == runs);
+            if (runs) {
+              EXPECT(e.offset == (form == 0 ? k * nnz * dim * dim : 0));
+              EXPECT(e.scale == (form == 2 ? w[(size_t)k] : 1.0));
+            }
+            EXPECT(e.nsteps == 0 && e.stride == 0 && !e.is_static && !e.use_weights);   // the host chose: no stepper
+            // the graphs are captured with the source exactly while it is active (stages.cpp ensure_graphs)
+            const SourceSlice c = source_slice(s, k, /*capture=*/runs);
+            EXPECT(c.due == runs && c.active == runs);
+            if (runs) {
+              EXPECT(c.offset == 0 && c.scale == 1.0);
+              EXPECT(c.nsteps == s.nsteps && c.stride == (form == 0 ? nnz * dim * dim : 0));
+              EXPECT(c.use_weights == (form == 2) && c.is_static == (form == 1));
+            }
+            // ... and replayed past its end: still launched, the kernel adds nothing beyond nsteps
+            if (form != 1 && k >= nsteps) EXPECT(source_slice(s, k, true).due && !source_slice(s, k, true).active);
+          }
+        }
+  EXPECT(!source_slice(SourceFacts{}, 0, false).active && !source_slice(SourceFacts{}, 0, false).due);
+
+  // The receivers (seigen_hip.h sg_set_receivers): sample j is taken after step (j + 1) * every; capacity samples fit.
+  for (int64_t every : {1, 2, 5})
+    for (int64_t capacity : {0, 1, 3})
+      for (int64_t call = 1; call <= 7; ++call) {
+        ReceiverClock c;
+        c.every = every;
+        c.capacity = capacity;
+        int64_t done = 0;      // the model: steps completed, and the multiples of `every` among 1..done counted one by one
+        auto multiples = [&](int64_t upto) {
+          int64_t n = 0;
+          for (int64_t s = 1; s <= upto; ++s) n += s % every == 0 ? 1 : 0;
+          return n;
+        };
+        // calls of `call` steps (sg_step) while they fit ...
+        for (int guard = 0; guard < 64; ++guard) {
+          EXPECT(c.samples() == multiples(done));
+          const bool fits = multiples(done + call) <= capacity;
+          EXPECT(c.fits(call) == fits);
+          EXPECT(c.samples_after(call) == multiples(done + call));
+          if (!fits) break;
+          c.steps += call;
+          done += call;
+        }
+        // ... then one step at a time (sg_end_step) up to the step that would write sample capacity + 1
+        for (int guard = 0; guard < 64; ++guard) {
+          const bool refused = (done + 1) % every == 0 && multiples(done + 1) == capacity + 1;
+          EXPECT(c.no_room_at(done + 1) == refused);
+          EXPECT(c.fits(1) == !refused);
+          if (refused) break;
+          c.steps += 1;
+          done += 1;
+          EXPECT(c.samples() == multiples(done) && c.samples() <= capacity);
+        }
+        EXPECT(c.samples() == capacity);
+      }
+}
+
 int main() {
   for (int cell_type : {0, 1})
     for (int dim = 1; dim <= 3; ++dim)
@@ -872,6 +1110,7 @@ int main() {
   point_location();
   kernel_family_table();
   stage_table();
+  stepping_state();
   for (int dim = 1; dim <= 3; ++dim)
     for (int degree : {1, 2, 4})
       for (int kind : {KIND_SIMPLEX, KIND_TENSOR}) {
