@@ -243,6 +243,7 @@ static int init_launch(sg_handle* h) {
   // some of its own slots taken would run the late blocks' static shares one after the other.
   hipDeviceProp_t prop;
   HIPCHECK(h, hipGetDeviceProperties(&prop, cfg->device));
+  h->ncu = prop.multiProcessorCount;
   const int slots = blocks_per_cu(h) * prop.multiProcessorCount;
   h->grid_full = slots / 8 * 8;
   h->grid_blocks = (cfg->nbr_mask != 0 ? slots - slots / 16 : slots) / 8 * 8;
@@ -259,8 +260,8 @@ static int init_launch(sg_handle* h) {
   }
   if (const char* oc = std::getenv("SEIGEN_HIP_ORDER_CHUNK")) h->order_chunk = std::max(0, std::atoi(oc));
   h->no_whole = std::getenv("SEIGEN_HIP_NO_WHOLE") != nullptr;
-  // 2-D tile kernels: a persistent grid of exactly the blocks the device holds of the stage's kernel (0 = the launcher
-  // asks the runtime per instantiation, kernels_tile2d.hip) - a wave sets up once and works through its share of the
+  // 2-D tile kernels: a persistent grid of exactly the blocks the device holds of the stage's kernel (0 = asked of
+  // the runtime per instantiation, stages.cpp tile_resident) - a wave sets up once and works through its share of the
   // items: 2-D P4 at N = 256 (the reference's benchmark protocol) 84.5 -> 93.4 G DoF-updates/s against one item per
   // wave, P3 +8 %, level elsewhere (profiles/r05/tile_grid_sweep.txt).  With a sponge the items differ in cost and a
   // static share can collect the expensive ones: then 251 blocks per XCD label - with an odd (prime) stride of 4 * 251

@@ -409,61 +409,35 @@ __global__ __launch_bounds__(256) void stage_kernel(StageArgs A) {
   }
 }
 
-template <int DIM, int P, int TP = 0>
-static int launch_dp(int kind, const StageArgs& a, hipStream_t s) {
-  using G = Geo<DIM, P, TP>;
-  long nelem = (long)a.box_n[0] * a.box_n[1] * a.box_n[2] * G::NCLS;
-  if (nelem <= 0) return 0;
-  long nbatch = (nelem + G::EB - 1) / G::EB;
-  long grid = nbatch < 256L * 8 ? nbatch : 256L * 8;
-  if (kind == 0)
-    SG_LAUNCH((stage_kernel<DIM, P, 0, TP>), dim3((unsigned)grid), dim3(256), s, a, a);
-  else
-    SG_LAUNCH((stage_kernel<DIM, P, 1, TP>), dim3((unsigned)grid), dim3(256), s, a, a);
+// The element of a generic launch as a type: f(Geo<DIM, P, TP>()) - simplices, and where a.tensor the quadrilaterals (TP = 1:
+// the same kernel over the tables of build_quad_tables) and the hexahedra, sum-factorised (TP = 2: DQ_1 .. DQ_4 have
+// 8 / 27 / 64 / 125 nodes and facets of 4 / 9 / 16 / 25) - or a zero of f's result type where there is none
+template <typename F>
+static auto with_geo(int dim, int P, int tensor, F f) {
+  return sg_pick<1, 2, 3, 4>(P, [&](auto p) {
+    constexpr int PP = decltype(p)::value;
+    if (tensor) return dim == 2 ? f(Geo<2, PP, 1>()) : dim == 3 ? f(Geo<3, PP, 2>()) : decltype(f(Geo<1, PP>()))();
+    return sg_pick<1, 2, 3>(dim, [&](auto d) { return f(Geo<decltype(d)::value, PP>()); });
+  });
+}
+template <int DIM, int P, int TP>
+static const void* stage_kernel_of(Geo<DIM, P, TP>, int kind) {
+  return kind == 0 ? (const void*)&stage_kernel<DIM, P, 0, TP> : (const void*)&stage_kernel<DIM, P, 1, TP>;
+}
+
+// (no MODE argument: the generic kernels read a.mode, 0 / 1 / 2, at run time)
+const void* stage_kernel_generic(int kind, int dim, int P, const StageArgs& a) {
+  return with_geo(dim, P, a.tensor, [&](auto g) { return stage_kernel_of(g, kind); });
+}
+
+int launch_stage(const void* kernel, int dim, int P, const StageArgs& a, void* stream) {
+  const long ncube = (long)a.box_n[0] * a.box_n[1] * a.box_n[2];
+  const long nbatch = with_geo(dim, P, a.tensor, [&](auto g) { return (ncube * g.NCLS + g.EB - 1) / g.EB; });
+  if (nbatch <= 0) return 0;
+  const long grid = nbatch < 256L * 8 ? nbatch : 256L * 8;
+  void* args[] = {const_cast<StageArgs*>(&a)};
+  (void)hipLaunchKernel(kernel, dim3((unsigned)grid), dim3(256), args, 0, (hipStream_t)stream);
   return (int)hipGetLastError();
-}
-
-// quadrilateral cells (tensor-product element): the same kernel over the tables of build_quad_tables
-static int launch_quad(int kind, int P, const StageArgs& a, hipStream_t s) {
-  switch (P) {
-    case 1: return launch_dp<2, 1, 1>(kind, a, s);
-    case 2: return launch_dp<2, 2, 1>(kind, a, s);
-    case 3: return launch_dp<2, 3, 1>(kind, a, s);
-    case 4: return launch_dp<2, 4, 1>(kind, a, s);
-  }
-  return -1;
-}
-
-template <int DIM>
-static int launch_d(int kind, int P, const StageArgs& a, hipStream_t s) {
-  switch (P) {
-    case 1: return launch_dp<DIM, 1>(kind, a, s);
-    case 2: return launch_dp<DIM, 2>(kind, a, s);
-    case 3: return launch_dp<DIM, 3>(kind, a, s);
-    case 4: return launch_dp<DIM, 4>(kind, a, s);
-  }
-  return -1;
-}
-
-int launch_stage(int kind, int dim, int P, const StageArgs& a, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (a.tensor) {
-    if (dim == 2) return launch_quad(kind, P, a, s);
-    if (dim != 3) return -1;
-    switch (P) {                                                        // hexahedra, sum-factorised (TP = 2)
-      case 1: return launch_dp<3, 1, 2>(kind, a, s);                    // 8 nodes, facets of 4
-      case 2: return launch_dp<3, 2, 2>(kind, a, s);                    // 27 / 9
-      case 3: return launch_dp<3, 3, 2>(kind, a, s);                    // 64 / 16
-      case 4: return launch_dp<3, 4, 2>(kind, a, s);                    // 125 / 25
-    }
-    return -1;
-  }
-  switch (dim) {
-    case 1: return launch_d<1>(kind, P, a, s);
-    case 2: return launch_d<2>(kind, P, a, s);
-    case 3: return launch_d<3>(kind, P, a, s);
-  }
-  return -1;
 }
 
 // ---- halo pack ------------------------------------------------------------------------

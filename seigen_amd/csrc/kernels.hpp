@@ -2,6 +2,7 @@
 #pragma once
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "mesh_tables.hpp"
@@ -141,9 +142,7 @@ struct StageArgs {
   // layer together, so the z-neighbour traces and the own rows of the next layer meet in the Infinity Cache.
   int32_t order_chunk;
   int32_t nitems;               // MFMA path: items of this launch (the item list's length, or cell groups x classes)
-  // Host side only (sg_stage_kernel_name): when set, the launch functions below launch NOTHING and write the name of the
-  // kernel instantiation they would have launched - taken from the same function pointer the launch uses (SG_LAUNCH)
-  std::string* name_out;
+  void* reserved_;              // unused: keeps every later member, and the tile kernels' T2Const behind StageArgs, at its kernarg offset
   // 2-D tile path, G stages: the sparse nodal source (elastic.py:217-218) added inside the stage kernel instead of
   // by a launch of its own.  src_slot[item] = slot of an item (16 cells of one class) that holds source nodes, or -1;
   // src_idx[slot][node][cell] = row of that node in this step's value table src_vals[row][dim*dim], or -1.
@@ -160,32 +159,44 @@ struct StageArgs {
 // handle of the instantiation (kernels.hip: dladdr + demangling) - the library names its kernels itself, nobody re-derives
 // template arguments from switches.
 std::string kernel_name_of(const void* host_fn);
-#if defined(__HIPCC__)
-// every stage launch goes through here: launch, or (StageArgs::name_out) only name what would be launched
-#define SG_LAUNCH(kernel, grid, block, stream, A, ...)                                           \
-  do {                                                                                           \
-    if ((A).name_out)                                                                            \
-      *(A).name_out = ::sg::kernel_name_of(reinterpret_cast<const void*>(&kernel));              \
-    else                                                                                         \
-      hipLaunchKernelGGL(kernel, grid, block, 0, stream, __VA_ARGS__);                           \
-  } while (0)
-#endif
 
-// kind: 0 = F (velocity RHS), 1 = G (stress RHS)
-int launch_stage(int kind, int dim, int P, const StageArgs& a, void* stream);
+// A run-time value as a compile-time constant: f(std::integral_constant<int, V>()) for the V among V0, Vs... that equals v,
+// a zero of f's result type where none does.  Every family's choice of a stage kernel is a nest of these.
+template <int V0, int... Vs, typename F>
+auto sg_pick(int v, F&& f) {
+  decltype(f(std::integral_constant<int, V0>())) r{};
+  auto take = [&](auto c) { return v == c.value && ((r = f(c)), true); };
+  (void)(take(std::integral_constant<int, V0>()) || ... || take(std::integral_constant<int, Vs>()));
+  return r;
+}
+inline int any_ghost(const StageArgs& a, int nsides) {   // blocks without neighbour blocks never meet a packed remote trace
+  int g = 0;
+  for (int sd = 0; sd < nsides; ++sd) g |= a.ghost[sd] != nullptr;
+  return g;
+}
+
+// A stage kernel is CHOSEN first and launched second.  stage_kernel_*: the host-side handle of the instantiation that a launch
+// with these arguments runs - read from kind (0 = F, velocity RHS; 1 = G, stress RHS), the degree and a.mode, a.sym, a.f32,
+// a.tensor, whether a.ghost[] / a.fragQ are set - or null where the family has no such kernel; nothing is launched or asked of
+// the runtime.  launch_stage_*: sizes the grid and launches the handle it is given.  kernel_name_of names the same handle.
+const void* stage_kernel_generic(int kind, int dim, int P, const StageArgs& a);
+int launch_stage(const void* kernel, int dim, int P, const StageArgs& a, void* stream);
 
 // MFMA path (3-D, degree >= 3; fields in the gw = 16 interleaved layout)
 int mfma_blocks_per_cu(int P, int f32);
-int launch_stage_mfma(int kind, int P, const StageArgs& a, void* stream);
+const void* stage_kernel_mfma(int kind, int P, const StageArgs& a);
+int launch_stage_mfma(const void* kernel, const StageArgs& a, void* stream);
 
 // lane-per-cell path (1-D / 2-D; fields in the gw = 64 interleaved layout; a.Dt = E[r][a][b],
 // a.Lt = L[f][a][b'] row-major; a.tensor: hexahedra, sum-factorised, a.Dt = {D1, lift1})
-int launch_stage_lane(int kind, int dim, int P, const StageArgs& a, long nitems, void* stream);
+const void* stage_kernel_lane(int kind, int dim, int P, const StageArgs& a);
+int launch_stage_lane(const void* kernel, const StageArgs& a, long nitems, void* stream);
 // hexahedra DQ_3 / DQ_4 with the lines of a cube in registers and the x lines on the matrix pipe (kernels_hexm.hip; fields
 // in the gw = 16 interleaved layout; a.Dt = hexm_table(): line operators E_k, trace lifts, x-pass A operands)
 int hexm_blocks_per_cu(int P);
 std::vector<double> hexm_table(int P, const double* D1, const double* lift1, const MeshDev& md_host);
-int launch_stage_hexm(int kind, int P, const StageArgs& a, long nitems, void* stream);
+const void* stage_kernel_hexm(int kind, int P, const StageArgs& a);
+int launch_stage_hexm(const void* kernel, int P, const StageArgs& a, long nitems, void* stream);
 
 // 2-D MFMA tile path (P1..P4; fields in the gw = 16 interleaved layout; a.fragV / a.fragL = tile2d_frags_*).
 // T2Const is the part of MeshDev these kernels use, passed by value in the kernarg segment so that no load
@@ -209,7 +220,10 @@ struct T2Const {
   T2Class cls[2];
 };
 T2Const tile2d_const(const MeshDev& md_host);
-int launch_stage_tile2d(int kind, int P, const StageArgs& a, const T2Const& c, long nitems, void* stream);
+const void* stage_kernel_tile2d(int kind, int P, const StageArgs& a);
+// resident: the blocks of four waves the device holds of `kernel` (asked by the caller, outside any stream capture) - the
+// persistent grid where a.grid_blocks names none
+int launch_stage_tile2d(const void* kernel, int resident, const StageArgs& a, const T2Const& c, long nitems, void* stream);
 
 // host layout [cell][node][comp] <-> device layout (MeshDev::gw) for `ncells` cells from `cell0`
 // dir = 0: staging -> field, 1: field -> staging

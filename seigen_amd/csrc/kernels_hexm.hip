@@ -649,45 +649,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HXW<P>::WPE
   }
 }
 
-template <int P>
-static int launch_hexm_p(int kind, const StageArgs& a, long nitems, hipStream_t s) {
-  // persistent grid: HXW<P>::WPE blocks of four waves per CU, a multiple of 8 (one item range per XCD label)
-  long blocks = (nitems + 3) / 4;
-  const long cap = a.grid_blocks > 0 ? a.grid_blocks : 256L * HXW<P>::WPE;
-  if (blocks > cap) blocks = cap;
-  blocks = (blocks + 7) / 8 * 8;
-  const dim3 grid((unsigned)blocks), block(256);
-#define SG_HEXM_LAUNCH(K, M)                                               \
-  do {                                                                     \
-    if (a.sym)                                                             \
-      SG_LAUNCH((hexm_stage<P, K, M, 1>), grid, block, s, a, a);           \
-    else                                                                   \
-      SG_LAUNCH((hexm_stage<P, K, M, 0>), grid, block, s, a, a);           \
-  } while (0)
-  if (kind == 0) {
-    if (a.mode == 0)
-      SG_HEXM_LAUNCH(0, 0);
-    else if (a.mode == 2)
-      SG_HEXM_LAUNCH(0, 2);
-    else
-      SG_HEXM_LAUNCH(0, 1);
-  } else {
-    if (a.mode == 0)
-      SG_HEXM_LAUNCH(1, 0);
-    else
-      SG_HEXM_LAUNCH(1, 1);
-  }
-#undef SG_HEXM_LAUNCH
-  return (int)hipGetLastError();
-}
-
 int hexm_blocks_per_cu(int P) { return P <= 3 ? 2 : 1; }
 
-int launch_stage_hexm(int kind, int P, const StageArgs& a, long nitems, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (P == 3) return launch_hexm_p<3>(kind, a, nitems, s);
-  if (P == 4) return launch_hexm_p<4>(kind, a, nitems, s);
-  return -1;
+// F stages: MODE = a.mode (0 / 1 / 2); G stages: MODE = (a.mode != 0)
+const void* stage_kernel_hexm(int kind, int P, const StageArgs& a) {
+  return sg_pick<3, 4>(P, [&](auto p) {
+    constexpr int PP = decltype(p)::value;
+    return sg_pick<0, 1>(a.sym != 0, [&](auto sym) {
+      constexpr int SYM = decltype(sym)::value;
+      if (kind == 0)
+        return sg_pick<0, 1, 2>(a.mode == 0 || a.mode == 2 ? a.mode : 1, [&](auto mode) {
+          return (const void*)&hexm_stage<PP, 0, decltype(mode)::value, SYM>;
+        });
+      return sg_pick<0, 1>(a.mode != 0, [&](auto mode) { return (const void*)&hexm_stage<PP, 1, decltype(mode)::value, SYM>; });
+    });
+  });
+}
+
+int launch_stage_hexm(const void* kernel, int P, const StageArgs& a, long nitems, void* stream) {
+  // persistent grid: HXW<P>::WPE blocks of four waves per CU, a multiple of 8 (one item range per XCD label)
+  long blocks = (nitems + 3) / 4;
+  const long cap = a.grid_blocks > 0 ? a.grid_blocks : 256L * (P == 3 ? HXW<3>::WPE : HXW<4>::WPE);
+  if (blocks > cap) blocks = cap;
+  blocks = (blocks + 7) / 8 * 8;
+  void* args[] = {const_cast<StageArgs*>(&a)};
+  (void)hipLaunchKernel(kernel, dim3((unsigned)blocks), dim3(256), args, 0, (hipStream_t)stream);
+  return (int)hipGetLastError();
 }
 
 }  // namespace sg

@@ -734,85 +734,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SG_HEX_WPE(
 #ifndef SG_HEX_BLOCKS
 #define SG_HEX_BLOCKS 2048
 #endif
-template <int P>
-static int launch_hex_p(int kind, const StageArgs& a, long nitems, hipStream_t s) {
-  long blocks = (nitems + 3) / 4;
-  if (blocks > SG_HEX_BLOCKS) blocks = SG_HEX_BLOCKS;
-  blocks = (blocks + 7) / 8 * 8;
-  const dim3 grid((unsigned)blocks), block(256);
-#define SG_HEX_LAUNCH(K, M)                                                        \
-  do {                                                                             \
-    if (a.sym)                                                                     \
-      SG_LAUNCH((hex_stage<P, K, M, 1>), grid, block, s, a, a);           \
-    else                                                                           \
-      SG_LAUNCH((hex_stage<P, K, M, 0>), grid, block, s, a, a);           \
-  } while (0)
-  if (kind == 0) {
-    if (a.mode == 0)
-      SG_HEX_LAUNCH(0, 0);
-    else
-      SG_HEX_LAUNCH(0, 1);
-  } else {
-    if (a.mode == 0)
-      SG_HEX_LAUNCH(1, 0);
-    else
-      SG_HEX_LAUNCH(1, 1);
-  }
-#undef SG_HEX_LAUNCH
-  return (int)hipGetLastError();
+// MODE = (a.mode != 0) for F and G stages alike: an F stage of mode 2 runs on MODE 1 with c_self = 0.
+// Simplices: every degree in 1-D and 2-D, degrees 1 and 2 in 3-D; a.tensor: hexahedra DQ_1 / DQ_2 (hex_stage)
+const void* stage_kernel_lane(int kind, int dim, int P, const StageArgs& a) {
+  return sg_pick<0, 1>(kind != 0, [&](auto k) {
+    constexpr int K = decltype(k)::value;
+    return sg_pick<0, 1>(a.mode != 0, [&](auto mode) {
+      constexpr int M = decltype(mode)::value;
+      return sg_pick<0, 1>(a.sym != 0, [&](auto sym) {
+        constexpr int SYM = decltype(sym)::value;
+        if (a.tensor) return dim != 3 ? nullptr : sg_pick<1, 2>(P, [&](auto p) { return (const void*)&hex_stage<decltype(p)::value, K, M, SYM>; });
+        if (dim == 3) return sg_pick<1, 2>(P, [&](auto p) { return (const void*)&lane_stage<3, decltype(p)::value, K, M, SYM>; });
+        return sg_pick<1, 2>(dim, [&](auto d) {
+          return sg_pick<1, 2, 3, 4>(P, [&](auto p) { return (const void*)&lane_stage<decltype(d)::value, decltype(p)::value, K, M, SYM>; });
+        });
+      });
+    });
+  });
 }
 
-template <int DIM, int P>
-static int launch_lane_dp(int kind, const StageArgs& a, long nitems, hipStream_t s) {
+int launch_stage_lane(const void* kernel, const StageArgs& a, long nitems, void* stream) {
   long blocks = (nitems + 3) / 4;
-  if (blocks > 2048) blocks = 2048;
+  const long cap = a.tensor ? SG_HEX_BLOCKS : 2048;
+  if (blocks > cap) blocks = cap;
   blocks = (blocks + 7) / 8 * 8;  // every XCD label needs a block
-  const dim3 grid((unsigned)blocks), block(256);
-#define SG_LANE_LAUNCH(K, M)                                                            \
-  do {                                                                                  \
-    if (a.sym)                                                                          \
-      SG_LAUNCH((lane_stage<DIM, P, K, M, 1>), grid, block, s, a, a);          \
-    else                                                                                \
-      SG_LAUNCH((lane_stage<DIM, P, K, M, 0>), grid, block, s, a, a);          \
-  } while (0)
-  if (kind == 0) {
-    if (a.mode == 0)
-      SG_LANE_LAUNCH(0, 0);
-    else
-      SG_LANE_LAUNCH(0, 1);
-  } else {
-    if (a.mode == 0)
-      SG_LANE_LAUNCH(1, 0);
-    else
-      SG_LANE_LAUNCH(1, 1);
-  }
-#undef SG_LANE_LAUNCH
+  void* args[] = {const_cast<StageArgs*>(&a)};
+  (void)hipLaunchKernel(kernel, dim3((unsigned)blocks), dim3(256), args, 0, (hipStream_t)stream);
   return (int)hipGetLastError();
-}
-
-template <int DIM>
-static int launch_lane_d(int kind, int P, const StageArgs& a, long nitems, hipStream_t s) {
-  switch (P) {
-    case 1: return launch_lane_dp<DIM, 1>(kind, a, nitems, s);
-    case 2: return launch_lane_dp<DIM, 2>(kind, a, nitems, s);
-    case 3: return launch_lane_dp<DIM, 3>(kind, a, nitems, s);
-    case 4: return launch_lane_dp<DIM, 4>(kind, a, nitems, s);
-  }
-  return -1;
-}
-
-int launch_stage_lane(int kind, int dim, int P, const StageArgs& a, long nitems, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (a.tensor) {
-    if (dim == 3 && P == 1) return launch_hex_p<1>(kind, a, nitems, s);
-    if (dim == 3 && P == 2) return launch_hex_p<2>(kind, a, nitems, s);
-    return -1;
-  }
-  if (dim == 1) return launch_lane_d<1>(kind, P, a, nitems, s);
-  if (dim == 2) return launch_lane_d<2>(kind, P, a, nitems, s);
-  if (dim == 3 && P == 1) return launch_lane_dp<3, 1>(kind, a, nitems, s);
-  if (dim == 3 && P == 2) return launch_lane_dp<3, 2>(kind, a, nitems, s);
-  return -1;
 }
 
 }  // namespace sg

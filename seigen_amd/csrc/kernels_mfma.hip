@@ -1216,60 +1216,6 @@ __global__ __launch_bounds__(256, (mfma_resident_blocks<R, P>())) void mfma_stag
   STAMP_FLUSH;
 }
 
-template <typename R, int P, int SYM>
-static int launch_ps(int kind, const StageArgs& a, hipStream_t s) {
-  // persistent grid, at most 2 blocks per CU; a multiple of 8 (one item range per XCD label)
-  // ... and no more blocks than there are items for their four waves (small blocks - the reference's own 3-D sweeps run
-  // N <= 8 - are launch-bound: every block copies the operator tiles into LDS before its first item)
-  unsigned nblk = (unsigned)(a.grid_blocks > 0 ? a.grid_blocks : 512);
-  if (a.nitems > 0 && !a.spread) {
-    const unsigned need = (((unsigned)a.nitems + 3u) / 4u + 7u) / 8u * 8u;
-    nblk = need < nblk ? need : nblk;
-  }
-  const dim3 grid(nblk), block(256);
-  if (kind == 0) {
-    // blocks without neighbour blocks never meet a packed remote trace: GHOST = 0 instantiation
-    bool ghosts = false;
-    for (int sd = 0; sd < 6; ++sd) ghosts = ghosts || (a.ghost[sd] != nullptr);
-    if (a.mode == 0) {
-      if (ghosts)
-        SG_LAUNCH((mfma_stage_F<R, P, 0, SYM, 1>), grid, block, s, a, a);
-      else
-        SG_LAUNCH((mfma_stage_F<R, P, 0, SYM, 0>), grid, block, s, a, a);
-    } else if (a.mode == 2) {
-      if (ghosts)
-        SG_LAUNCH((mfma_stage_F<R, P, 2, SYM, 1>), grid, block, s, a, a);
-      else
-        SG_LAUNCH((mfma_stage_F<R, P, 2, SYM, 0>), grid, block, s, a, a);
-    } else {
-      if (ghosts)
-        SG_LAUNCH((mfma_stage_F<R, P, 1, SYM, 1>), grid, block, s, a, a);
-      else
-        SG_LAUNCH((mfma_stage_F<R, P, 1, SYM, 0>), grid, block, s, a, a);
-    }
-  } else {
-    if constexpr (sizeof(R) == 8 && P >= 3) {
-      if (a.fragQ != nullptr) {      // factorised volume term (StageArgs::fragQ; a.fragV then holds the P_r tiles)
-        if (a.mode == 0)
-          SG_LAUNCH((mfma_stage_G<R, P, 0, SYM, 1>), grid, block, s, a, a);
-        else
-          SG_LAUNCH((mfma_stage_G<R, P, 1, SYM, 1>), grid, block, s, a, a);
-        return (int)hipGetLastError();
-      }
-    }
-    if (a.mode == 0)
-      SG_LAUNCH((mfma_stage_G<R, P, 0, SYM, 0>), grid, block, s, a, a);
-    else
-      SG_LAUNCH((mfma_stage_G<R, P, 1, SYM, 0>), grid, block, s, a, a);
-  }
-  return (int)hipGetLastError();
-}
-
-template <typename R, int P>
-static int launch_p(int kind, const StageArgs& a, hipStream_t s) {
-  return a.sym ? launch_ps<R, P, 1>(kind, a, s) : launch_ps<R, P, 0>(kind, a, s);
-}
-
 // --------------------------------------------------------------------------------------------
 //  Sponge of the cells whose sigma is affine in the reference coordinates (kernels.hpp launch_sponge_pre_affine has the
 //  family-independent form): sp[slot][a][i] = s_0 u_i[a] + sum_k s_k (X_k u_i)[a] with the element-constant X_k as row
@@ -1387,24 +1333,43 @@ int mfma_blocks_per_cu(int P, int f32) {
   return P == 1 ? mfma_resident_blocks<double, 1>() : (P == 2 ? mfma_resident_blocks<double, 2>() : mfma_resident_blocks<double, 4>());
 }
 
-int launch_stage_mfma(int kind, int P, const StageArgs& a, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (a.f32) {
-    switch (P) {
-      case 1: return launch_p<float, 1>(kind, a, s);
-      case 2: return launch_p<float, 2>(kind, a, s);
-      case 3: return launch_p<float, 3>(kind, a, s);
-      case 4: return launch_p<float, 4>(kind, a, s);
-    }
-    return -1;
+// F stages: MODE = a.mode (0 / 1 / 2) and GHOST; G stages: MODE = (a.mode != 0) and FACT, the factorised volume term
+// (StageArgs::fragQ; a.fragV then holds the P_r tiles), which exists in double from degree 3 on
+const void* stage_kernel_mfma(int kind, int P, const StageArgs& a) {
+  return sg_pick<0, 1>(a.f32 != 0, [&](auto f32) {
+    using R = std::conditional_t<decltype(f32)::value, float, double>;
+    return sg_pick<1, 2, 3, 4>(P, [&](auto p) {
+      constexpr int PP = decltype(p)::value, HAS_FACT = sizeof(R) == 8 && PP >= 3;
+      return sg_pick<0, 1>(a.sym != 0, [&](auto sym) {
+        constexpr int SYM = decltype(sym)::value;
+        if (kind == 0)
+          return sg_pick<0, 1, 2>(a.mode == 0 || a.mode == 2 ? a.mode : 1, [&](auto mode) {
+            return sg_pick<0, 1>(any_ghost(a, 6), [&](auto ghost) {
+              return (const void*)&mfma_stage_F<R, PP, decltype(mode)::value, SYM, decltype(ghost)::value>;
+            });
+          });
+        return sg_pick<0, 1>(a.mode != 0, [&](auto mode) {
+          return sg_pick<0, HAS_FACT>(HAS_FACT && a.fragQ != nullptr, [&](auto fact) {
+            return (const void*)&mfma_stage_G<R, PP, decltype(mode)::value, SYM, decltype(fact)::value>;
+          });
+        });
+      });
+    });
+  });
+}
+
+int launch_stage_mfma(const void* kernel, const StageArgs& a, void* stream) {
+  // persistent grid, at most 2 blocks per CU; a multiple of 8 (one item range per XCD label)
+  // ... and no more blocks than there are items for their four waves (small blocks - the reference's own 3-D sweeps run
+  // N <= 8 - are launch-bound: every block copies the operator tiles into LDS before its first item)
+  unsigned nblk = (unsigned)(a.grid_blocks > 0 ? a.grid_blocks : 512);
+  if (a.nitems > 0 && !a.spread) {
+    const unsigned need = (((unsigned)a.nitems + 3u) / 4u + 7u) / 8u * 8u;
+    nblk = need < nblk ? need : nblk;
   }
-  switch (P) {
-    case 1: return launch_p<double, 1>(kind, a, s);
-    case 2: return launch_p<double, 2>(kind, a, s);
-    case 3: return launch_p<double, 3>(kind, a, s);
-    case 4: return launch_p<double, 4>(kind, a, s);
-  }
-  return -1;
+  void* args[] = {const_cast<StageArgs*>(&a)};
+  (void)hipLaunchKernel(kernel, dim3(nblk), dim3(256), args, 0, (hipStream_t)stream);
+  return (int)hipGetLastError();
 }
 
 }  // namespace sg

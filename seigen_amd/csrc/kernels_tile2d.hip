@@ -511,80 +511,45 @@ __global__ __launch_bounds__(256) void tile2d_stage(const StageArgs A, const T2C
   }
 }
 
-// Blocks of four waves the device holds of one kernel instantiation (asked once per instantiation): the size of the
-// persistent grid when the caller names none (StageArgs::grid_blocks = 0, stages.cpp).  Exactly resident is a sharp optimum
+// F stages: MODE = a.mode (0 / 1 / 2); G stages: MODE = (a.mode != 0)
+const void* stage_kernel_tile2d(int kind, int P, const StageArgs& a) {
+  return sg_pick<0, 1>(a.f32 != 0, [&](auto f32) {
+    using R = std::conditional_t<decltype(f32)::value, float, double>;
+    return sg_pick<0, 1>(a.tensor != 0, [&](auto tp) {
+      constexpr int TP = decltype(tp)::value;
+      return sg_pick<1, 2, 3, 4>(P, [&](auto p) {
+        constexpr int PP = decltype(p)::value;
+        return sg_pick<0, 1>(a.sym != 0, [&](auto sym) {
+          constexpr int SYM = decltype(sym)::value;
+          return sg_pick<0, 1>(any_ghost(a, 4), [&](auto ghost) {
+            constexpr int GHOST = decltype(ghost)::value;
+            if (kind == 0)
+              return sg_pick<0, 1, 2>(a.mode == 0 || a.mode == 2 ? a.mode : 1, [&](auto mode) {
+                return (const void*)&tile2d_stage<PP, 0, decltype(mode)::value, SYM, GHOST, TP, R>;
+              });
+            return sg_pick<0, 1>(a.mode != 0, [&](auto mode) {
+              return (const void*)&tile2d_stage<PP, 1, decltype(mode)::value, SYM, GHOST, TP, R>;
+            });
+          });
+        });
+      });
+    });
+  });
+}
+
+// The persistent grid when the caller names none (StageArgs::grid_blocks = 0, stages.cpp) is `resident`, the blocks of four
+// waves the device holds of this instantiation.  Exactly resident is a sharp optimum
 // on the meshes of the benchmark protocol - a few blocks more start a second, nearly empty round, a few less leave slots
 // unused with the same number of items per wave (profiles/r05/tile_grid_sweep.txt) - and the instantiations differ: the
 // fused F stages hold two waves per SIMD at degree 4, the other stages three.
-template <typename K>
-static int t2_resident_blocks(K kernel) {
-  int per_cu = 0, dev = 0, ncu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || per_cu <= 0) per_cu = 2;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0)
-    ncu = 256;
-  return per_cu * ncu;
-}
-
-template <int P, int SYM, int GHOST, int TP = 0, typename R = double>
-static int launch_t2(int kind, const StageArgs& a, const T2Const& c, long nitems, hipStream_t s) {
-  const dim3 block(256);
-#define SG_T2_LAUNCH(K, M)                                                                          \
-  do {                                                                                              \
-    static const int resident = t2_resident_blocks(tile2d_stage<P, K, M, SYM, GHOST, TP, R>);       \
-    long blocks = (nitems + 3) / 4;                                                                 \
-    const long cap = a.grid_blocks > 0 ? a.grid_blocks : resident;                                  \
-    if (blocks > cap) blocks = cap;                                                                 \
-    blocks = (blocks + 7) / 8 * 8; /* every XCD label needs a block */                              \
-    const dim3 grid((unsigned)blocks);                                                              \
-    SG_LAUNCH((tile2d_stage<P, K, M, SYM, GHOST, TP, R>), grid, block, s, a, a, c);                 \
-  } while (0)
-  if (kind == 0) {
-    if (a.mode == 0)
-      SG_T2_LAUNCH(0, 0);
-    else if (a.mode == 2)
-      SG_T2_LAUNCH(0, 2);
-    else
-      SG_T2_LAUNCH(0, 1);
-  } else {
-    if (a.mode == 0)
-      SG_T2_LAUNCH(1, 0);
-    else
-      SG_T2_LAUNCH(1, 1);
-  }
-#undef SG_T2_LAUNCH
+int launch_stage_tile2d(const void* kernel, int resident, const StageArgs& a, const T2Const& c, long nitems, void* stream) {
+  long blocks = (nitems + 3) / 4;
+  const long cap = a.grid_blocks > 0 ? a.grid_blocks : resident;
+  if (blocks > cap) blocks = cap;
+  blocks = (blocks + 7) / 8 * 8;  // every XCD label needs a block
+  void* args[] = {const_cast<StageArgs*>(&a), const_cast<T2Const*>(&c)};
+  (void)hipLaunchKernel(kernel, dim3((unsigned)blocks), dim3(256), args, 0, (hipStream_t)stream);
   return (int)hipGetLastError();
-}
-
-template <int P, int TP, typename R>
-static int launch_t2r(int kind, const StageArgs& a, const T2Const& c, long nitems, hipStream_t s) {
-  bool ghosts = false;
-  for (int sd = 0; sd < 4; ++sd) ghosts = ghosts || (a.ghost[sd] != nullptr);
-  if (a.sym) return ghosts ? launch_t2<P, 1, 1, TP, R>(kind, a, c, nitems, s) : launch_t2<P, 1, 0, TP, R>(kind, a, c, nitems, s);
-  return ghosts ? launch_t2<P, 0, 1, TP, R>(kind, a, c, nitems, s) : launch_t2<P, 0, 0, TP, R>(kind, a, c, nitems, s);
-}
-template <int P, int TP = 0>
-static int launch_t2p(int kind, const StageArgs& a, const T2Const& c, long nitems, hipStream_t s) {
-  return a.f32 ? launch_t2r<P, TP, float>(kind, a, c, nitems, s) : launch_t2r<P, TP, double>(kind, a, c, nitems, s);
-}
-
-int launch_stage_tile2d(int kind, int P, const StageArgs& a, const T2Const& c, long nitems, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (a.tensor) {
-    switch (P) {
-      case 1: return launch_t2p<1, 1>(kind, a, c, nitems, s);
-      case 2: return launch_t2p<2, 1>(kind, a, c, nitems, s);
-      case 3: return launch_t2p<3, 1>(kind, a, c, nitems, s);
-      case 4: return launch_t2p<4, 1>(kind, a, c, nitems, s);
-    }
-    return -1;
-  }
-  switch (P) {
-    case 1: return launch_t2p<1>(kind, a, c, nitems, s);
-    case 2: return launch_t2p<2>(kind, a, c, nitems, s);
-    case 3: return launch_t2p<3>(kind, a, c, nitems, s);
-    case 4: return launch_t2p<4>(kind, a, c, nitems, s);
-  }
-  return -1;
 }
 
 }  // namespace sg

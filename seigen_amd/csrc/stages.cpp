@@ -1,14 +1,13 @@
-// Stage launches of the C-ABI: regions of a split stage, the six fused launches of an LF4 step
+// Stage launches of the C-ABI: the choice of a stage's kernel, regions of a split stage, the six fused launches of an LF4 step
 // (seigen/elastic.py:283-313), hipGraph replay, un-fused operator applications, halo packs, timing.
 #include "handle.hpp"
 
 // ---- stage launches --------------------------------------------------------------------
 
 // What a launch is queued with, as a value that its caller builds and every function below is handed: nothing on the handle
-// says "a capture is under way" or "only name the kernels", so nothing has to be put back afterwards.
+// says "a capture is under way", so nothing has to be put back afterwards.
 struct LaunchCtx {
   hipStream_t stream;                 // the stream of this launch and of what belongs to it (pre-pass, source)
-  std::string* name_out = nullptr;    // a naming pass: every launcher names its kernel and launches nothing (kernels.hpp SG_LAUNCH)
   bool capture_src = false;           // a capture: slice and weight of the source come from the device-side counter src_ctr_d ...
   bool capture_rec = false;           // ... and the recorder's step from rec.ctr
 };
@@ -59,7 +58,6 @@ static int stage_args(sg_handle* h, const LaunchCtx& ctx, StageArgs& a, const St
   a.mk = h->mk_dev.get();
   a.ftab = h->ftab_dev.get();
   a.nbr_tab = h->nbr_tab.get();
-  a.name_out = ctx.name_out;
   a.all_active = region == SG_REGION_ALL ? 1 : 0;
   a.tensor = h->re.kind == KIND_TENSOR ? 1 : 0;
   a.fragV = (kind == 0) ? h->fragF.get() : h->fragG.get();
@@ -105,10 +103,10 @@ static int stage_args(sg_handle* h, const LaunchCtx& ctx, StageArgs& a, const St
 }
 
 // The sponge pre-pass of an F stage (SpongeTables::pre): B_e u_abs of the sponge cells, queued before anything of the stage
-// writes, when the buffer does not hold it yet (hostlogic.hpp PrePass).  A naming pass changes nothing.
+// writes, when the buffer does not hold it yet (hostlogic.hpp PrePass).
 static int sponge_pre_pass(sg_handle* h, const LaunchCtx& ctx, const StageOp& op, int region) {
   SpongeTables& sp = h->sponge;
-  if (!sp.pre.get() || ctx.name_out || !sp.pre_state.due(op, region, h->field.versions())) return SG_OK;
+  if (!sp.pre.get() || !sp.pre_state.due(op, region, h->field.versions())) return SG_OK;
   const void* uabs = h->field.read(op.uabs);
   // the cells with a sponge matrix
   if (launch_sponge_pre(uabs, sp.B.get(), sp.cells.get(), sp.mat.get(), sp.mat_slots.get(), sp.pre.get(), sp.nmat_slots, h->re.nd,
@@ -142,29 +140,62 @@ static int region_items(sg_handle* h, int region, const std::vector<Box>& boxes)
   return SG_OK;
 }
 
-// one launch of the family's stage kernel (a naming pass: its name, kernels.hpp SG_LAUNCH)
+// The kernel instantiation that a stage launch with these arguments runs (kernels.hpp stage_kernel_*): the one place that
+// picks - launches, captures and sg_stage_kernel_name all take it from here.
+static int pick_kernel(sg_handle* h, int kind, const StageArgs& a, const void*& kernel) {
+  const int P = h->cfg.degree;
+  switch (h->family) {
+    case Family::Generic: kernel = stage_kernel_generic(kind, h->cfg.dim, P, a); break;
+    case Family::Lane: kernel = stage_kernel_lane(kind, h->cfg.dim, P, a); break;
+    case Family::Mfma: kernel = stage_kernel_mfma(kind, P, a); break;
+    case Family::Tile2d: kernel = stage_kernel_tile2d(kind, P, a); break;
+    case Family::Hexm: kernel = stage_kernel_hexm(kind, P, a); break;
+  }
+  return kernel ? SG_OK : fail(h, SG_ERR_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString((hipError_t)-1));
+}
+
+// Blocks of four waves the handle's device holds of a 2-D tile instantiation (launch_stage_tile2d's `resident`): asked of the
+// runtime the first time the handle meets the kernel and kept with the handle.  A capture must not ask: capture_steps asks first.
+static int tile_resident(sg_handle* h, const void* kernel) {
+  for (const auto& kr : h->tile_resident)
+    if (kr.first == kernel) return kr.second;
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, 0) != hipSuccess || per_cu <= 0) per_cu = 2;
+  h->tile_resident.emplace_back(kernel, per_cu * h->ncu);
+  return h->tile_resident.back().second;
+}
+
+// one launch of the family's stage kernel
 static int launch_family(sg_handle* h, const LaunchCtx& ctx, int kind, const StageArgs& a) {
+  const void* kernel = nullptr;
+  if (int rc = pick_kernel(h, kind, a, kernel)) return rc;
   const int P = h->cfg.degree;
   const long ngroups = (long)(h->md.ncube_pad / h->md.gw);
   int rc = 0;
   switch (h->family) {
-    case Family::Generic: rc = launch_stage(kind, h->cfg.dim, P, a, ctx.stream); break;
-    case Family::Lane: rc = launch_stage_lane(kind, h->cfg.dim, P, a, ngroups * h->ncls, ctx.stream); break;
-    case Family::Mfma: rc = launch_stage_mfma(kind, P, a, ctx.stream); break;
-    case Family::Tile2d: rc = launch_stage_tile2d(kind, P, a, h->t2c, ngroups * h->ncls, ctx.stream); break;
-    case Family::Hexm: rc = launch_stage_hexm(kind, P, a, ngroups, ctx.stream); break;
+    case Family::Generic: rc = launch_stage(kernel, h->cfg.dim, P, a, ctx.stream); break;
+    case Family::Lane: rc = launch_stage_lane(kernel, a, ngroups * h->ncls, ctx.stream); break;
+    case Family::Mfma: rc = launch_stage_mfma(kernel, a, ctx.stream); break;
+    case Family::Tile2d: rc = launch_stage_tile2d(kernel, tile_resident(h, kernel), a, h->t2c, ngroups * h->ncls, ctx.stream); break;
+    case Family::Hexm: rc = launch_stage_hexm(kernel, P, a, ngroups, ctx.stream); break;
   }
   return rc != 0 ? fail(h, SG_ERR_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString((hipError_t)rc)) : SG_OK;
+}
+
+// the boxes of a region that hold cubes
+static std::vector<Box> region_cubes(const sg_handle* h, int region) {
+  std::vector<Box> boxes;
+  region_boxes(h, region, boxes);
+  boxes.erase(std::remove_if(boxes.begin(), boxes.end(), [](const Box& b) { return b.n[0] <= 0 || b.n[1] <= 0 || b.n[2] <= 0; }), boxes.end());
+  return boxes;
 }
 
 // the launches of a region: one per box for the generic kernels; the other families scan all cell groups and mask lanes
 // by box in one launch
 static int launch_region(sg_handle* h, const LaunchCtx& ctx, int kind, int region, StageArgs& a) {
-  std::vector<Box> boxes;
-  region_boxes(h, region, boxes);
+  const std::vector<Box> boxes = region_cubes(h, region);
   if (!family_interleaved(h->family)) {
     for (const Box& b : boxes) {
-      if (b.n[0] <= 0 || b.n[1] <= 0 || b.n[2] <= 0) continue;
       std::memcpy(a.box_o, b.o, sizeof(a.box_o));
       std::memcpy(a.box_n, b.n, sizeof(a.box_n));
       if (int rc = launch_family(h, ctx, kind, a)) return rc;
@@ -173,7 +204,6 @@ static int launch_region(sg_handle* h, const LaunchCtx& ctx, int kind, int regio
   }
   a.nbox = 0;
   for (const Box& b : boxes) {
-    if (b.n[0] <= 0 || b.n[1] <= 0 || b.n[2] <= 0) continue;
     if (a.nbox >= SG_MAX_BOXES) return fail(h, SG_ERR_STATE, "region has more boxes than a launch can carry");
     for (int k = 0; k < 3; ++k) {
       a.boxes_o[a.nbox][k] = b.o[k];
@@ -204,7 +234,7 @@ static int launch_region(sg_handle* h, const LaunchCtx& ctx, int kind, int regio
 // the source lives on single nodes: added to each part of a split stage right after the launch
 // that wrote it (INTERIOR + BOUNDARY: all of it after the second launch)
 static int add_source(sg_handle* h, const LaunchCtx& ctx, int field, double coef, int region) {
-  if (h->src.fused || ctx.name_out) return SG_OK;  // added by the stage kernel (stage_args) / a naming pass launches nothing
+  if (h->src.fused) return SG_OK;  // added by the stage kernel (stage_args)
   const SourceNow sn = source_now(h, ctx);
   if (!sn.at.due || region == SG_REGION_INTERIOR) return SG_OK;
   const int d = h->cfg.dim;
@@ -226,15 +256,25 @@ static int run_op(sg_handle* h, const LaunchCtx& ctx, const StageOp& op, int reg
   StageArgs a;
   if (int rc = stage_args(h, ctx, a, op, region)) return rc;
   if (int rc = sponge_pre_pass(h, ctx, op, region)) return rc;
-  // the output counts as written from here on, i.e. after the pre-pass was decided (hostlogic.hpp PrePass::due); a naming
-  // pass writes nothing
-  a.out = ctx.name_out ? nullptr : h->field.write(op.out);
+  // the output counts as written from here on, i.e. after the pre-pass was decided (hostlogic.hpp PrePass::due)
+  a.out = h->field.write(op.out);
   if (int rc = launch_region(h, ctx, op.kind, region, a)) return rc;
   return op.with_source ? add_source(h, ctx, op.out, op.src_coef, region) : SG_OK;
 }
 
-static int run_stage_impl(sg_handle* h, const LaunchCtx& ctx, int stage, int region) {
-  return run_op(h, ctx, lf4_stage(stage, h->dt, h->rho, h->rho_physical != 0, h->rho2_d.get() != nullptr), region);
+static StageOp stage_op(const sg_handle* h, int stage) {
+  return lf4_stage(stage, h->dt, h->rho, h->rho_physical != 0, h->rho2_d.get() != nullptr);
+}
+static int run_stage_impl(sg_handle* h, const LaunchCtx& ctx, int stage, int region) { return run_op(h, ctx, stage_op(h, stage), region); }
+
+// The kernel of an LF4 stage as a launch of `region` would choose it, without launching, allocating or counting anything;
+// null (and SG_OK) for a region that has no box with cubes: it launches nothing.
+static int stage_kernel(sg_handle* h, int stage, int region, const void*& kernel) {
+  const StageOp op = stage_op(h, stage);
+  StageArgs a;
+  kernel = nullptr;
+  if (int rc = stage_args(h, LaunchCtx{h->stream}, a, op, region)) return rc;
+  return region_cubes(h, region).empty() ? SG_OK : pick_kernel(h, op.kind, a, kernel);
 }
 
 int resolve_timing(sg_handle* h) {
@@ -344,7 +384,7 @@ int sg_run_stage(sg_handle* h, int stage, int region) {
 // SG_ERR_STATE, nothing queued and nothing counted: the step is due a sample the trace has no room for.
 static int record_step(sg_handle* h, const LaunchCtx& ctx) {
   ReceiverTables& rt = h->rec;
-  if (rt.nrec == 0 || ctx.name_out) return SG_OK;
+  if (rt.nrec == 0) return SG_OK;
   const int64_t step = rt.clock.steps + 1;
   if (!ctx.capture_rec && rt.clock.no_room_at(step))
     return fail(h, SG_ERR_STATE, "receiver trace full: read it out (sg_get_receivers) and re-arm before stepping on");
@@ -420,13 +460,15 @@ static int enqueue_step(sg_handle* h, const LaunchCtx& ctx, bool counted) {
 static hipGraphExec_t capture_steps(sg_handle* h, int steps, bool with_src) {
   hipGraph_t g = nullptr;
   hipGraphExec_t ge = nullptr;
-  // a dry pass through the launch code (nothing is queued): what a launcher asks the runtime once per kernel
-  // instantiation - the resident blocks of the 2-D tile kernels - is asked here, outside the capture
-  std::string name;
-  (void)run_stages(h, LaunchCtx{h->stream, &name}, false);
+  // what a launch asks the runtime once per kernel instantiation - the resident blocks of the 2-D tile kernels - is
+  // asked here, outside the capture, of the six stages' kernels (a failure shows again, and is reported, in the capture)
+  for (int st = 0; st < 6 && h->family == Family::Tile2d; ++st) {
+    const void* kernel = nullptr;
+    if (stage_kernel(h, st, SG_REGION_ALL, kernel) == SG_OK && kernel) (void)tile_resident(h, kernel);
+  }
   if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return nullptr;
   int rc = SG_OK;
-  const LaunchCtx ctx{h->stream, nullptr, with_src, h->rec.nrec > 0};
+  const LaunchCtx ctx{h->stream, with_src, h->rec.nrec > 0};
   h->sponge.pre_state.forget();      // a replay starts from whatever the buffer holds: the captured step computes its own
   for (int k = 0; k < steps && rc == SG_OK; ++k) rc = enqueue_step(h, ctx, false);
   h->sponge.pre_state.forget();      // nothing was launched: the buffer does not hold what the capture asked for
@@ -616,11 +658,10 @@ int sg_stage_kernel_name(sg_handle* h, int stage, int region, char* buf, size_t 
   if (region < 0 || region > 4) return fail(h, SG_ERR_ARG, "unknown region");
   if (stage < 0 || stage > 5) return fail(h, SG_ERR_ARG, "unknown stage");
   HIPCHECK(h, hipSetDevice(h->cfg.device));
-  // the stage's own launch code with StageArgs::name_out set: the dispatch that picks the instantiation is the one
-  // that would launch it (kernels.hpp SG_LAUNCH); nothing is queued on the stream
-  std::string name;
-  if (int rc = run_stage_impl(h, LaunchCtx{h->stream, &name}, stage, region)) return rc;
-  std::snprintf(buf, n, "%s", name.c_str());
+  // the choice that a launch makes (pick_kernel), named from the handle that a launch would pass to the runtime
+  const void* kernel = nullptr;
+  if (int rc = stage_kernel(h, stage, region, kernel)) return rc;
+  std::snprintf(buf, n, "%s", kernel ? kernel_name_of(kernel).c_str() : "");
   return SG_OK;
 }
 
