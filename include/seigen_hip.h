@@ -254,6 +254,43 @@ int sg_set_receivers(sg_handle* h, int64_t nrec, const double* pts, int what, in
  * probe of every 5th VTU file (uy.py:36-43, vtktools.vtu.ProbeData). */
 int sg_get_receivers(sg_handle* h, double* out, size_t nbytes, int64_t* nsamples);
 
+/* ---- monitor: L2 norms and elastic energy of the block, taken on the device (the global observer beside the point-wise
+ * one; what a harness gets from norm(u) of the downloaded fields, or the oracle's energy test from 1/2 (rho |u|^2 +
+ * s : C^-1 : s) of its state) --------------------------------------------------------------------------------------------
+ * With Mhat the reference mass matrix of the element and |det J| the cell's Jacobian determinant, every cell c has
+ *   Qu_c = sum_i u_i^T Mhat u_i,   Qs_c = sum_ij s_ij^T Mhat s_ij,   Qt_c = t^T Mhat t with t = sum_i s_ii node by node
+ * of u = SG_FIELD_U and s = SG_FIELD_S.  A SAMPLE is five doubles { U2, S2, T2, EK, ES }:
+ *   U2 = sum_c |det J| Qu_c  (= ||u||^2 in L2; S2, T2 likewise from Qs_c, Qt_c),
+ *   EK = sum_c |det J| wk_c Qu_c,   ES = sum_c |det J| (ws_c Qs_c + wt_c Qt_c).
+ * The weights w = (wk, ws, wt) are the caller's: one triple for the block (per_cell = 0: w[3]) or one per cell (per_cell
+ * = 1: w[ncells][3], host cell order cube * ncls + cls); the library does not derive them from its material state.  The
+ * physical choice in dimension d is wk = rho / 2, ws = 1 / (4 mu), wt = -lambda / (4 mu (d lambda + 2 mu)): EK + ES is
+ * then the kinetic plus the compliance energy 1/2 s : C^-1 : s, strain = (s - lambda / (d lambda + 2 mu) tr(s) I) / (2 mu).
+ * w = NULL: EK = ES = 0.
+ * Arithmetic: a form v^T Mhat v is sum_a v_a (Mhat_aa v_a + 2 sum_{b<a} Mhat_ab v_b), b ascending inside a ascending, with
+ * fma, in double (FP32 blocks convert every nodal value first).  In symmetric-stress storage only the i <= j lines are
+ * read and an off-diagonal form counts twice.  Cells of the layout's padding contribute nothing; ghost traces are no
+ * part of a block (a split block measures its own cells).  The lanes of an item are summed by a fixed tree, then
+ * SG_MONITOR_CHUNK_ITEMS consecutive items (by item index) in ascending order into one partial, then the partials by one
+ * workgroup in a fixed order; no floating-point atomics.  The bits of a sample therefore depend only on the block (shape,
+ * kernel family, dtype, storage mode) and the field contents: the same under graph replay and eager launches, for one
+ * sg_step(n) and n calls of sg_step(1), for host-driven stages with sg_end_step, with timing on or off.  They are NOT
+ * promised equal across partitions: the sum over the blocks of a split equals the single block's to round-off.
+ * Arm: a sample after every `every`-th completed step counted from the arming call - through sg_step (graph replay or
+ * eager, with or without a communicator) or through sg_end_step after host-driven stages; sample j (0-based) is taken
+ * after step (j+1)*every from u1 (time t) and s1 (time t + dt/2); `capacity` >= 1 samples the device buffer holds.  every
+ * = 0 disarms; re-arming discards the old samples; a failed call leaves the previous monitor recording, samples intact.
+ * sg_step(n) whose samples would exceed the capacity returns SG_ERR_STATE before it queues anything (fields, counters
+ * and trace untouched); sg_end_step of a step due a sample the trace has no room for returns SG_ERR_STATE and does not
+ * count the step.  No monitor armed: no extra launch, the same captured graphs. */
+#define SG_MONITOR_CHUNK_ITEMS 4
+/* one sample of the fields as they stand now, after everything the handle has queued */
+int sg_measure(sg_handle* h, const double* w, int per_cell, double out[5]);
+int sg_set_monitor(sg_handle* h, int64_t every, int64_t capacity, const double* w, int per_cell);
+/* samples taken so far -> out[nsamples][5]; nbytes must be that of `capacity` samples (0 with no monitor armed);
+ * *nsamples = samples taken */
+int sg_get_monitor(sg_handle* h, double* out, size_t nbytes, int64_t* nsamples);
+
 /* un-fused operators for stage-level parity tests:
  *   out = Minv f(w; s_in, u_abs)   (elastic.py:204-209 + :358-367)
  *   out = Minv g(v; u_in)          (elastic.py:211-219 + :358-367)

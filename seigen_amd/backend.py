@@ -234,6 +234,38 @@ class HipBlock(object):
         check(self.lib.sg_get_receivers(self.h, out.ctypes.data, out.nbytes, C.byref(n)), self.h)
         return out[:n.value]
 
+    # ---- monitor (sg_measure / sg_set_monitor / sg_get_monitor) ------------------------------------
+    def _weights(self, w):
+        """(pointer, per_cell, array kept alive) of the weights (wk, ws, wt): None, one triple, or [ncells, 3]"""
+        if w is None:
+            return None, 0, None
+        w = _f64(w)
+        if w.shape == (3,):
+            return w.ctypes.data, 0, w
+        if w.shape != (self.ncells, 3):
+            raise ValueError("weights are one (wk, ws, wt) or one per cell of the block [%d, 3], not %r" % (self.ncells, w.shape))
+        return w.ctypes.data, 1, w
+
+    def measure(self, w=None):
+        """One sample { U2, S2, T2, EK, ES } of u and s as they stand now, taken on the device (sg_measure)."""
+        ptr, per_cell, keep = self._weights(w)
+        out = np.zeros(5)
+        check(self.lib.sg_measure(self.h, ptr, per_cell, out.ctypes.data), self.h)
+        return out
+
+    def set_monitor(self, every, capacity, w=None):
+        """Arm the monitor: a sample after every `every`-th step, room for `capacity` samples; every = 0 disarms."""
+        ptr, per_cell, keep = self._weights(w)
+        check(self.lib.sg_set_monitor(self.h, int(every), int(capacity), ptr, per_cell), self.h)
+        self._mon_capacity = int(capacity) if int(every) > 0 else 0
+
+    def get_monitor(self):
+        """The samples taken so far, [n, 5]."""
+        out = np.zeros((getattr(self, "_mon_capacity", 0), 5))
+        n = C.c_int64()
+        check(self.lib.sg_get_monitor(self.h, out.ctypes.data, out.nbytes, C.byref(n)), self.h)
+        return out[:n.value]
+
     def apply_F(self, s_in, u_abs, u_out):
         check(self.lib.sg_apply_F(self.h, s_in, u_abs, u_out), self.h)
 

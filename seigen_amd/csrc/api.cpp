@@ -692,6 +692,49 @@ int sg_get_receivers(sg_handle* h, double* out, size_t nbytes, int64_t* nsamples
   return SG_OK;
 }
 
+// The monitor (kernels_measure.hip): tables and trace are built in locals and moved into the handle once nothing can fail
+// any more, as the receivers' are.
+int sg_set_monitor(sg_handle* h, int64_t every, int64_t capacity, const double* w, int per_cell) {
+  if (!h) return SG_ERR_ARG;
+  if (every < 0) return fail(h, SG_ERR_ARG, "sg_set_monitor: every must be >= 0 (0 disarms)");
+  if (every > 0 && capacity < 1) return fail(h, SG_ERR_ARG, "sg_set_monitor: capacity must be >= 1");
+  if (every > 0 && per_cell && !w) return fail(h, SG_ERR_ARG, "sg_set_monitor: per-cell weights without weights");
+  if (every > 0 && capacity > ((int64_t)1 << 32)) return fail(h, SG_ERR_ARG, "sg_set_monitor: more than 2^32 samples");
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  MonitorTables mt;
+  if (every > 0) {
+    if (int rc = measure_prepare(h)) return rc;
+    mt.armed = true;
+    mt.clock.every = every;
+    mt.clock.capacity = capacity;
+    if (w && per_cell) HIPCHECK(h, mt.w.upload(w, (size_t)h->ncells * 3));
+    if (w && !per_cell) std::memcpy(mt.w0, w, sizeof(mt.w0));
+    const int64_t zero = 0;
+    if (mt.trace.alloc((size_t)capacity * 5) != hipSuccess) return fail(h, SG_ERR_NOMEM, "sg_set_monitor: hipMalloc of the trace failed");
+    HIPCHECK(h, hipMemset(mt.trace.get(), 0, (size_t)capacity * 5 * sizeof(double)));
+    HIPCHECK(h, mt.ctr.upload(&zero, 1));
+  }
+  HIPCHECK(h, sync_all(h));
+  h->mon = std::move(mt);
+  h->epoch += 1;
+  return SG_OK;
+}
+
+int sg_get_monitor(sg_handle* h, double* out, size_t nbytes, int64_t* nsamples) {
+  if (!h || !nsamples) return SG_ERR_ARG;
+  const MonitorTables& mt = h->mon;
+  const size_t want = mt.armed ? (size_t)mt.clock.capacity * 5 * sizeof(double) : 0;
+  if (nbytes != want || (want > 0 && !out))
+    return fail(h, SG_ERR_ARG, "sg_get_monitor: the buffer must hold capacity x 5 doubles (" + std::to_string(want) + " bytes)");
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  HIPCHECK(h, sync_all(h));
+  const int64_t n = mt.armed ? mt.clock.samples() : 0;
+  if (want > 0) std::memset(out, 0, want);
+  if (n > 0) HIPCHECK(h, hipMemcpy(out, mt.trace.get(), (size_t)n * 5 * sizeof(double), hipMemcpyDeviceToHost));
+  *nsamples = n;
+  return SG_OK;
+}
+
 int sg_get_sym(const sg_handle* h, int* sym) {
   if (!h || !sym) return SG_ERR_ARG;
   *sym = h->sym ? 1 : 0;
@@ -711,3 +754,21 @@ int sg_halo_attach(sg_handle* h, int field, int side, const void* dev_in) {
 }
 
 }  // extern "C"
+
+// what every sample of the handle needs (handle.hpp MeasureScratch): built once, outside any capture
+int measure_prepare(sg_handle* h) {
+  if (h->msr.ready) return SG_OK;
+  MeasureScratch ms;
+  const int gw = (int)h->md.gw, nd = h->re.nd;
+  ms.nitems = (h->md.ncube_pad / gw) * h->ncls;
+  ms.nchunks = (ms.nitems + SG_MONITOR_CHUNK_ITEMS - 1) / SG_MONITOR_CHUNK_ITEMS;
+  ms.ips = measure_items_per_sweep(nd, gw);
+  if (ms.ips <= 0 || prepare_measure(nd, gw, ms.ips, h->f32) != 0) return fail(h, SG_ERR_DEVICE, "monitor: no kernel for this element");
+  const std::vector<double> tri = mass_lower_rows(h->re.Mhat, nd);
+  HIPCHECK(h, ms.Mtri.upload(tri.data(), tri.size()));
+  if (ms.partial.alloc((size_t)ms.nchunks * 5) != hipSuccess || ms.out.alloc(5) != hipSuccess)
+    return fail(h, SG_ERR_NOMEM, "monitor: hipMalloc of the partial sums failed");
+  ms.ready = true;
+  h->msr = std::move(ms);
+  return SG_OK;
+}

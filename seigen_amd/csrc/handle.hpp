@@ -1,5 +1,5 @@
 // The handle behind the C-ABI (include/seigen_hip.h) and what its translation units share:
-//   api.cpp      create / destroy, parameters, sponge, source, receivers: device checks, uploads, the move into the handle
+//   api.cpp      create / destroy, parameters, sponge, source, receivers, monitor: device checks, uploads, the move into the handle
 //   transfer.cpp host <-> device field transfers (layout conversion, pinned pipeline)
 //   stages.cpp   regions, stage launches, the LF4 step, graphs, halo packs, timing
 // and, without a device or a HIP header (the CPU sanitizer build, `make host-asan`):
@@ -122,6 +122,25 @@ struct ReceiverTables {
   DevBuf<int64_t> ctr;
 };
 
+// The monitor of sg_set_monitor and the scratch of sg_measure (kernels_measure.hip), on the device
+struct MonitorTables {
+  bool armed = false;
+  MonitorClock clock;         // every, capacity, steps completed since arming (hostlogic.hpp)
+  DevBuf<double> w;           // [ncells][3] per-cell weights, or empty: w0
+  double w0[3] = {0.0, 0.0, 0.0};
+  DevBuf<double> trace;       // [capacity][5]
+  DevBuf<int64_t> ctr;        // graph replay: the step index of the launches of a capture (the role of ReceiverTables::ctr)
+};
+// what every sample needs, built by the first sg_measure / sg_set_monitor of the handle and kept
+struct MeasureScratch {
+  DevBuf<double> Mtri;        // hostlogic.hpp mass_lower_rows
+  DevBuf<double> partial;     // [nchunks][5]
+  DevBuf<double> out;         // [5]: the sample of sg_measure
+  int64_t nitems = 0, nchunks = 0;
+  int ips = 0;                // measure::Args::ips
+  bool ready = false;
+};
+
 // The four fields of a block.  Whoever writes one asks for it with write(), which counts the write: what remembers a field
 // state (the sponge pre-pass, hostlogic.hpp PrePass) can then tell that the field has moved on - from a stage, a source
 // launch, an upload or the mirror launch alike.  Readers take the const pointer.
@@ -189,6 +208,9 @@ struct sg_handle {
   bool graph_src = false;     // the captured graphs contain the source launches
   ReceiverTables rec;
   bool graph_rec = false;     // the captured graphs contain the recorder launches
+  MonitorTables mon;
+  MeasureScratch msr;
+  bool graph_mon = false;     // the captured graphs contain the monitor's launches
   // halo
   const double* ghost[4][6] = {};
   // execution
@@ -280,6 +302,7 @@ inline void region_boxes(const sg_handle* h, int region, std::vector<Box>& out) 
 }
 int resolve_timing(sg_handle* h);
 int finish_step_call(sg_handle* h);   // stages.cpp: the end of sg_step and comm_step (ev1, synchronise, last_ms)
+int measure_prepare(sg_handle* h);    // api.cpp: the scratch of the monitor's samples (MeasureScratch), built once
 // comm.cpp
 int comm_step(sg_handle* h, int64_t nsteps);
 void comm_release(sg_handle* h);

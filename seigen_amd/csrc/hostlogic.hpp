@@ -173,6 +173,31 @@ struct ReceiverClock {
   bool no_room_at(int64_t s) const { return s % every == 0 && s / every > capacity; }       // step s is due a sample and has none
 };
 
+// The monitor (seigen_hip.h sg_set_monitor) keeps the receivers' clock: sample j after step (j + 1) * every, `capacity`
+// samples, the same two refusals.  What its kernels read, in the order they read it (kernels_measure.hip): the dim
+// components of the velocity, then the stress's - all dim^2 of full storage, the i <= j ones of symmetric storage, where an
+// off-diagonal form counts twice; the diagonal ones also make up the trace t.
+using MonitorClock = ReceiverClock;
+struct MonitorComp {
+  int comp = 0;        // index of the component in its field (velocity: i, stress: i * dim + j)
+  bool stress = false, diag = false;
+  double mult = 1.0;
+};
+inline std::vector<MonitorComp> monitor_components(int dim, bool sym) {
+  std::vector<MonitorComp> r;
+  for (int i = 0; i < dim; ++i) r.push_back({i, false, false, 1.0});
+  for (int i = 0; i < dim; ++i)
+    for (int j = sym ? i : 0; j < dim; ++j) r.push_back({i * dim + j, true, i == j, (sym && i != j) ? 2.0 : 1.0});
+  return r;
+}
+// ... and the reference mass matrix as the rows b = 0 .. a of its lower triangle, nd (nd + 1) / 2 values
+inline std::vector<double> mass_lower_rows(const std::vector<double>& Mhat, int nd) {
+  std::vector<double> r;
+  for (int a = 0; a < nd; ++a)
+    for (int b = 0; b <= a; ++b) r.push_back(Mhat[(size_t)a * nd + b]);
+  return r;
+}
+
 struct Box {
   int o[3], n[3];
 };

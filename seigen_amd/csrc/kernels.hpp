@@ -5,6 +5,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "../../include/seigen_hip.h"
 #include "mesh_tables.hpp"
 
 namespace sg {
@@ -285,5 +286,39 @@ struct RecvArgs {
   int32_t dim, nd, gw, sym;
 };
 int launch_receivers(const void* u, const void* s, const RecvArgs& a, int f32, void* stream);
+
+// The monitor's sample (kernels_measure.hip; seigen_hip.h sg_measure / sg_set_monitor): { U2, S2, T2, EK, ES } of the block
+// from u and s, in two passes - one partial per chunk of SG_MONITOR_CHUNK_ITEMS consecutive items, then one workgroup.
+// After step s with s % every == 0 (s from *ctr + 1 under graph replay) the sample goes to out[s / every - 1]; a one-shot
+// names step = every = capacity = 1.
+namespace measure {
+constexpr int MAX_COMP = 12;   // dim velocity components + dim^2 stress components
+struct Args {
+  const int64_t* ctr;      // graph replay: *ctr + 1 is the step that just ended; null: `step`
+  int64_t step;
+  int64_t every, capacity; // (a sample index beyond the capacity is not written)
+  const double* Mtri;      // the reference mass matrix, row a: b = 0 .. a; nd (nd + 1) / 2 values
+  const double* w;         // [cell][3] = (wk, ws, wt) in host cell order cube * ncls + cls, or null: w0 for every cell
+  double w0[3];
+  double detj;             // |det J| of every cell of the block
+  double* partial;         // [nchunks][5]
+  double* out;             // [capacity][5]
+  int64_t nitems, ncube, nchunks;
+  int32_t nd, dim, gw, ncls;
+  int32_t ips;             // pass1_lds: items of a chunk worked on at a time (measure_items_per_sweep)
+  int32_t ncomp;           // the components read, in this order: the velocity's, then the stress's (i <= j only in symmetric storage)
+  int32_t comp[MAX_COMP];  // ... the component's index in its field
+  int32_t diag[MAX_COMP];  // ... a diagonal stress component: joins the trace t
+  double mult[MAX_COMP];   // ... and how often its form counts (2: an off-diagonal one in symmetric storage)
+};
+}  // namespace measure
+// items of a chunk that the LDS-staged pass 1 holds at a time - 4, 2 or 1 (gw = 64: 1) - or 0: none fits.  The staging is
+// sized for 64 KB per workgroup, 2 * nd * ips * gw doubles: every layout the library has fits (gw = 64 up to nd = 64,
+// gw = 16 up to nd = 256); a layout beyond that is refused by sg_measure / sg_set_monitor ("no kernel for this element")
+int measure_items_per_sweep(int nd, int gw);
+// once per handle, outside any stream capture: allow pass 1 its dynamic LDS; 0 on success
+int prepare_measure(int nd, int gw, int ips, int f32);
+// both passes on `stream`; a.nchunks = 0 launches nothing
+int launch_measure(const void* u, const void* s, const measure::Args& a, int f32, void* stream);
 
 }  // namespace sg

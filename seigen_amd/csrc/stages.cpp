@@ -10,6 +10,7 @@ struct LaunchCtx {
   hipStream_t stream;                 // the stream of this launch and of what belongs to it (pre-pass, source)
   bool capture_src = false;           // a capture: slice and weight of the source come from the device-side counter src_ctr_d ...
   bool capture_rec = false;           // ... and the recorder's step from rec.ctr
+  bool capture_mon = false;           // ... and the monitor's from mon.ctr
 };
 
 // the source at the handle's step (hostlogic.hpp source_slice), with the device pointers of a capture's SrcStep
@@ -416,6 +417,73 @@ static int record_step(sg_handle* h, const LaunchCtx& ctx) {
   return SG_OK;
 }
 
+// The two passes of a monitor sample (kernels_measure.hip) on `stream`: of the fields as they stand there, with these weights,
+// into out[step / every - 1] when the step (by value, or *ctr + 1) is a sample step.
+static int queue_measure(sg_handle* h, hipStream_t stream, const double* w_cells, const double w0[3], const int64_t* ctr, int64_t step,
+                         int64_t every, int64_t capacity, double* out) {
+  const MeasureScratch& ms = h->msr;
+  measure::Args a;
+  std::memset(&a, 0, sizeof(a));
+  a.ctr = ctr;
+  a.step = step;
+  a.every = every;
+  a.capacity = capacity;
+  a.Mtri = ms.Mtri.get();
+  a.w = w_cells;
+  for (int k = 0; k < 3; ++k) a.w0[k] = w0[k];
+  a.detj = 1.0;
+  for (int k = 0; k < h->cfg.dim; ++k) a.detj *= h->cfg.h[k];
+  a.partial = ms.partial.get();
+  a.out = out;
+  a.nitems = ms.nitems;
+  a.ncube = h->md.ncube;
+  a.nchunks = ms.nchunks;
+  a.nd = h->re.nd;
+  a.dim = h->cfg.dim;
+  a.gw = (int32_t)h->md.gw;
+  a.ncls = h->ncls;
+  a.ips = ms.ips;
+  const std::vector<MonitorComp> comps = monitor_components(h->cfg.dim, h->sym);
+  a.ncomp = (int32_t)comps.size();
+  for (size_t k = 0; k < comps.size(); ++k) {
+    a.comp[k] = comps[k].comp;
+    a.diag[k] = comps[k].diag ? 1 : 0;
+    a.mult[k] = comps[k].mult;
+  }
+  if (launch_measure(h->field.read(SG_FIELD_U), h->field.read(SG_FIELD_S), a, h->f32, stream) != 0)
+    return fail(h, SG_ERR_DEVICE, "monitor launch failed");
+  return SG_OK;
+}
+
+// The end of a step for the monitor (sg_set_monitor), by the receivers' rules (record_step): the sample of u1 and s1 on the
+// main stream behind stage S1's SECOND launch; eager launches name the step by value and count it here, the launches of a
+// capture read it from mon.ctr and bump that.  No room for the sample: end_of_step refuses before anything is queued.
+static bool monitor_no_room(const sg_handle* h, const LaunchCtx& ctx) {
+  return h->mon.armed && !ctx.capture_mon && h->mon.clock.no_room_at(h->mon.clock.steps + 1);
+}
+static int monitor_step(sg_handle* h, const LaunchCtx& ctx) {
+  MonitorTables& mt = h->mon;
+  if (!mt.armed) return SG_OK;
+  const int64_t step = mt.clock.steps + 1;
+  if (int rc = join_second(h)) return rc;
+  if (int rc = queue_measure(h, ctx.stream, mt.w.get(), mt.w0, ctx.capture_mon ? mt.ctr.get() : nullptr, step, mt.clock.every,
+                             mt.clock.capacity, mt.trace.get()))
+    return rc;
+  if (ctx.capture_mon && launch_step_counter(mt.ctr.get(), 1, 1, ctx.stream) != 0)
+    return fail(h, SG_ERR_DEVICE, "step counter launch failed");
+  if (!ctx.capture_mon) mt.clock.steps = step;
+  return SG_OK;
+}
+
+// what ends a step on the stream: the receivers' recorder, then the monitor.  Either's refusal (no room for the sample) is
+// found before anything is queued or counted; a launch error of the second leaves the first one's step counted
+static int end_of_step(sg_handle* h, const LaunchCtx& ctx) {
+  if (monitor_no_room(h, ctx))
+    return fail(h, SG_ERR_STATE, "monitor trace full: read it out (sg_get_monitor) and re-arm before stepping on");
+  if (int rc = record_step(h, ctx)) return rc;
+  return monitor_step(h, ctx);
+}
+
 // The bookkeeping of n finished steps.  Eager stage launches and record_step have counted themselves; replayed steps
 // count here, and what a replay wrote is new to everything that remembers a field state.
 static void steps_done(sg_handle* h, int64_t n, bool replayed) {
@@ -424,6 +492,7 @@ static void steps_done(sg_handle* h, int64_t n, bool replayed) {
   if (!replayed) return;
   for (int st = 0; st < 6; ++st) h->counters.launches[st] += n;
   if (h->rec.nrec > 0) h->rec.clock.steps += n;
+  if (h->mon.armed) h->mon.clock.steps += n;
   h->field.replayed();
   h->sponge.pre_state.forget();
 }
@@ -431,7 +500,7 @@ static void steps_done(sg_handle* h, int64_t n, bool replayed) {
 int sg_end_step(sg_handle* h) {
   if (!h) return SG_ERR_ARG;
   HIPCHECK(h, hipSetDevice(h->cfg.device));
-  if (int rc = record_step(h, LaunchCtx{h->stream})) return rc;
+  if (int rc = end_of_step(h, LaunchCtx{h->stream})) return rc;
   steps_done(h, 1, false);
   return SG_OK;
 }
@@ -453,7 +522,7 @@ static int enqueue_step(sg_handle* h, const LaunchCtx& ctx, bool counted) {
   // the next step's slice (tile path: stage UH1 bumps the counter itself, stage_args)
   if (ctx.capture_src && !h->src.fused && launch_step_counter(h->src_ctr_d.get(), 1, 1, ctx.stream) != 0)
     return fail(h, SG_ERR_DEVICE, "step counter launch failed");
-  return record_step(h, ctx);
+  return end_of_step(h, ctx);
 }
 
 // capture `steps` steps into an executable graph; on any failure graphs are switched off for the handle
@@ -468,7 +537,7 @@ static hipGraphExec_t capture_steps(sg_handle* h, int steps, bool with_src) {
   }
   if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return nullptr;
   int rc = SG_OK;
-  const LaunchCtx ctx{h->stream, with_src, h->rec.nrec > 0};
+  const LaunchCtx ctx{h->stream, with_src, h->rec.nrec > 0, h->mon.armed};
   h->sponge.pre_state.forget();      // a replay starts from whatever the buffer holds: the captured step computes its own
   for (int k = 0; k < steps && rc == SG_OK; ++k) rc = enqueue_step(h, ctx, false);
   h->sponge.pre_state.forget();      // nothing was launched: the buffer does not hold what the capture asked for
@@ -488,14 +557,22 @@ static int check_receiver_room(sg_handle* h, int64_t nsteps) {
   return fail(h, SG_ERR_STATE, "sg_step: the receiver trace has room for " + std::to_string(c.capacity - c.samples()) +
                                    " more samples, these steps take " + std::to_string(c.samples_after(nsteps) - c.samples()));
 }
+// ... and the monitor's
+static int check_monitor_room(sg_handle* h, int64_t nsteps) {
+  const MonitorClock& c = h->mon.clock;
+  if (!h->mon.armed || c.fits(nsteps)) return SG_OK;
+  return fail(h, SG_ERR_STATE, "sg_step: the monitor trace has room for " + std::to_string(c.capacity - c.samples()) +
+                                   " more samples, these steps take " + std::to_string(c.samples_after(nsteps) - c.samples()));
+}
 
 // The graphs of one and of eight steps, captured again when a setter changed kernel arguments (epoch) or the source or the
 // receivers came or went.  A source that is still active is part of them: its launches take the step's slice and weight from
 // a device-side counter (kernels.hpp SrcStep); one that has run out, or none: no source launches.  Armed receivers likewise.
 static int ensure_graphs(sg_handle* h) {
-  const bool with_src = source_at(h, false).active, with_rec = h->rec.nrec > 0;
+  const bool with_src = source_at(h, false).active, with_rec = h->rec.nrec > 0, with_mon = h->mon.armed;
   if (with_src && !h->src_ctr_d.get()) return fail(h, SG_ERR_STATE, "source without a device-side step counter");
-  if (h->graph_epoch == h->epoch && h->graph_src == with_src && h->graph_rec == with_rec) return SG_OK;
+  if (h->graph_epoch == h->epoch && h->graph_src == with_src && h->graph_rec == with_rec && h->graph_mon == with_mon)
+    return SG_OK;
   if (h->graph1) (void)hipGraphExecDestroy(h->graph1);
   if (h->graph8) (void)hipGraphExecDestroy(h->graph8);
   h->graph1 = capture_steps(h, 1, with_src);
@@ -503,6 +580,7 @@ static int ensure_graphs(sg_handle* h) {
   h->graph_epoch = h->epoch;
   h->graph_src = with_src;
   h->graph_rec = with_rec;
+  h->graph_mon = with_mon;
   if (!h->graph1 || !h->graph8) h->graph_ok = false;  // same kernels, launched one by one (eager_steps)
   return SG_OK;
 }
@@ -513,6 +591,8 @@ static int replay_steps(sg_handle* h, int64_t nsteps) {
   if (h->graph_src && launch_step_counter(h->src_ctr_d.get(), h->src_step - (h->src.fused ? 1 : 0), 0, h->stream) != 0)
     return fail(h, SG_ERR_DEVICE, "step counter launch failed");
   if (h->rec.nown > 0 && launch_step_counter(h->rec.ctr.get(), h->rec.clock.steps, 0, h->stream) != 0)
+    return fail(h, SG_ERR_DEVICE, "step counter launch failed");
+  if (h->mon.armed && launch_step_counter(h->mon.ctr.get(), h->mon.clock.steps, 0, h->stream) != 0)
     return fail(h, SG_ERR_DEVICE, "step counter launch failed");
   int64_t k = 0;
   for (; k + 8 <= nsteps; k += 8) HIPCHECK(h, hipGraphLaunch(h->graph8, h->stream));
@@ -533,6 +613,7 @@ int sg_step(sg_handle* h, int64_t nsteps) {
   if (!h || nsteps < 0) return SG_ERR_ARG;
   if (!h->params_set) return fail(h, SG_ERR_STATE, "sg_set_params must be called before stepping");
   if (int rc = check_receiver_room(h, nsteps)) return rc;
+  if (int rc = check_monitor_room(h, nsteps)) return rc;
   HIPCHECK(h, hipSetDevice(h->cfg.device));
   for (int s = 0; s < 6; ++s)
     if (h->md.has_nbr[s]) {
@@ -547,6 +628,23 @@ int sg_step(sg_handle* h, int64_t nsteps) {
   HIPCHECK(h, hipEventRecord(h->ev0, h->stream));
   if (int rc = (graphs && h->graph_ok) ? replay_steps(h, nsteps) : eager_steps(h, nsteps)) return rc;
   return finish_step_call(h);
+}
+
+// One sample of the fields as they stand behind everything the handle has queued, with the caller's weights.
+int sg_measure(sg_handle* h, const double* w, int per_cell, double out[5]) {
+  if (!h || !out) return SG_ERR_ARG;
+  if (per_cell && !w) return fail(h, SG_ERR_ARG, "sg_measure: per-cell weights without weights");
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  if (int rc = measure_prepare(h)) return rc;
+  DevBuf<double> w_cells;
+  double w0[3] = {0.0, 0.0, 0.0};
+  if (w && per_cell) HIPCHECK(h, w_cells.upload(w, (size_t)h->ncells * 3));
+  if (w && !per_cell) std::memcpy(w0, w, sizeof(w0));
+  if (int rc = join_second(h)) return rc;
+  if (int rc = queue_measure(h, h->stream, w && per_cell ? w_cells.get() : nullptr, w0, nullptr, 1, 1, 1, h->msr.out.get())) return rc;
+  HIPCHECK(h, hipStreamSynchronize(h->stream));
+  HIPCHECK(h, hipMemcpy(out, h->msr.out.get(), 5 * sizeof(double), hipMemcpyDeviceToHost));
+  return SG_OK;
 }
 
 int sg_last_step_ms(sg_handle* h, double* ms) {

@@ -43,6 +43,18 @@ from .profiling import timed_region
 _SOLVER_MODES = ("implicit", "explicit", "parloop", "fusion", "tiling", "hip")
 
 
+def monitor_weights(dim, density, mu, l, ncells):
+    """The weights (wk, ws, wt) that make the monitor's EK + ES the kinetic plus the compliance energy 1/2 s : C^-1 : s
+    (include/seigen_hip.h): wk = rho / 2, ws = 1 / (4 mu), wt = -lambda / (4 mu (d lambda + 2 mu)).  Floats: one triple
+    [3]; any of the three one value per cell: [ncells, 3]."""
+    rho, mu, lam = (np.atleast_1d(np.asarray(a, dtype=np.float64)).ravel() for a in (density, mu, l))
+    per_cell = max(rho.size, mu.size, lam.size) > 1
+    if per_cell:
+        rho, mu, lam = (np.broadcast_to(a, (int(ncells),)) for a in (rho, mu, lam))
+    w = np.stack([rho / 2.0, 1.0 / (4.0 * mu), -lam / (4.0 * mu * (dim * lam + 2.0 * mu))], axis=-1)
+    return np.ascontiguousarray(w if per_cell else w[0])
+
+
 def _device_for_rank():
     if "SEIGEN_HIP_DEVICE" in os.environ:
         return int(os.environ["SEIGEN_HIP_DEVICE"])
@@ -137,6 +149,8 @@ class ElasticLF4(object):
             self._step_index = 0
             self._receivers = None          # (points, every, what) of set_receivers
             self._receiver_times = []
+            self._monitor = None            # `every` of set_monitor
+            self._monitor_times = []
 
         if self.output:
             with timed_region('i/o'):
@@ -487,6 +501,46 @@ class ElasticLF4(object):
         self._block.set_receivers(pts, what, every, len(times) // every)
         self._receiver_times = list(times[every - 1::every])
 
+    # ---- monitor: L2 norms and elastic energy inside the time loop (sg_set_monitor) -----------------
+    def energy_weights(self):
+        """The weights of the monitor's energies from `density`, `mu`, `l` (monitor_weights)."""
+        for name in ("density", "mu", "l"):
+            if getattr(self, name) is None:
+                raise ValueError("ElasticLF4.%s must be set before the energy can be weighted" % name)
+        return monitor_weights(self.dimension, self.density, self.mu, self.l, self._block.ncells)
+
+    def set_monitor(self, every=1):
+        """Record the L2 norms of (u1, s1) and the kinetic and strain energy after every `every`-th step of the next runs,
+        on the device inside the time loop; every = 0: no monitor."""
+        if int(every) < 0:
+            raise ValueError("set_monitor needs every >= 0")
+        self._monitor = int(every) or None
+
+    def monitor_trace(self):
+        """(times [n], {"u_l2", "s_l2", "kinetic", "strain", "energy"}: [n] each) of the last run: sample j after step
+        (j + 1) * every at t = times[j] (u1 at t, s1 at t + dt/2).  Collective with more than one rank: the blocks' sums
+        are added."""
+        if self._monitor is None:
+            raise RuntimeError("no monitor: call set_monitor before run")
+        tr = allreduce_sum_array(self._block.get_monitor())
+        return np.array(self._monitor_times[:tr.shape[0]]), self._monitor_quantities(tr)
+
+    @staticmethod
+    def _monitor_quantities(tr):
+        return {"u_l2": np.sqrt(tr[..., 0]), "s_l2": np.sqrt(tr[..., 1]), "kinetic": tr[..., 3].copy(), "strain": tr[..., 4].copy(),
+                "energy": tr[..., 3] + tr[..., 4]}
+
+    def energy(self):
+        """The quantities of monitor_trace of the fields as they stand now (one sg_measure); collective."""
+        return {k: float(v) for k, v in self._monitor_quantities(allreduce_sum_array(self._block.measure(self.energy_weights()))).items()}
+
+    def _arm_monitor(self, times):
+        if self._monitor is None:
+            return
+        every = self._monitor
+        self._block.set_monitor(every, max(1, len(times) // every), self.energy_weights())
+        self._monitor_times = list(times[every - 1::every])
+
     # ---- time loop (elastic.py:267-315) ----------------------------------------------------------
     def step_times(self, T):
         """The values of `t` visited by the reference loop ``t = dt; while t <= T + 1e-12``."""
@@ -529,6 +583,7 @@ class ElasticLF4(object):
                 self.upload_source(times)
             self._agree_on_stress_storage()
             self._arm_receivers(times)
+            self._arm_monitor(times)
             with self.loop_context():
                 if self.output:
                     for t in times:

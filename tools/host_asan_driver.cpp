@@ -847,7 +847,7 @@ static void stage_table() {
   for (int k = 0; k < 6; ++k) std::printf("stage %d: %d %d\n", k, lf4_stage_input(k), lf4_stage_output(k));
 }
 
-// What stepping remembers between calls (hostlogic.hpp FieldVersions, PrePass, source_slice, ReceiverClock), against models
+// What stepping remembers between calls (hostlogic.hpp FieldVersions, PrePass, source_slice, ReceiverClock, MonitorClock), against models
 // written out here that share nothing with them.
 //
 // The pre-pass: the model gives every field a content id, raised whenever a launch or an upload writes the field, and tags the
@@ -1083,6 +1083,70 @@ static void stepping_state() {
         }
         EXPECT(c.samples() == capacity);
       }
+
+  // The monitor (seigen_hip.h sg_set_monitor) keeps that clock, armed with capacity >= 1: calls of sg_step while they fit,
+  // then sg_end_step up to the refusal - every sample index it hands out lies inside the trace, none is handed out twice.
+  for (int64_t every : {1, 3, 4})
+    for (int64_t capacity : {1, 2, 5})
+      for (int64_t call : {1, 2, 11}) {
+        MonitorClock c;
+        c.every = every;
+        c.capacity = capacity;
+        std::vector<int> taken((size_t)capacity, 0);
+        auto step_done = [&](int64_t s) {     // what the kernels do with step s (kernels_measure.hip sample_index)
+          if (s % every != 0) return;
+          const int64_t j = s / every - 1;
+          EXPECT(j >= 0 && j < capacity);
+          if (j >= 0 && j < capacity) taken[(size_t)j] += 1;
+        };
+        while (c.fits(call)) {
+          for (int64_t k = 1; k <= call; ++k) step_done(c.steps + k);
+          c.steps += call;
+          if (c.steps > 64 * every * capacity) break;
+        }
+        EXPECT(c.steps <= (capacity + 1) * every);
+        for (int guard = 0; guard < 64 && !c.no_room_at(c.steps + 1); ++guard) {
+          step_done(c.steps + 1);
+          c.steps += 1;
+        }
+        EXPECT(c.no_room_at(c.steps + 1) && !c.fits(1) && c.samples() == capacity);
+        for (int n : taken) EXPECT(n == 1);
+      }
+  // ... and what its kernels read, in order: the velocity's components, then the stress's - every entry of the tensor counted
+  // once, whichever storage
+  for (int dim = 1; dim <= 3; ++dim)
+    for (bool sym : {false, true}) {
+      const std::vector<MonitorComp> cs = monitor_components(dim, sym);
+      EXPECT((int)cs.size() == dim + (sym ? dim * (dim + 1) / 2 : dim * dim) && (int)cs.size() <= sg::measure::MAX_COMP);
+      std::vector<double> counted((size_t)dim * dim, 0.0);
+      int ndiag = 0;
+      for (size_t k = 0; k < cs.size(); ++k) {
+        EXPECT(cs[k].stress == ((int)k >= dim));
+        if (!cs[k].stress) {
+          EXPECT(cs[k].comp == (int)k && cs[k].mult == 1.0 && !cs[k].diag);
+          continue;
+        }
+        const int i = cs[k].comp / dim, j = cs[k].comp % dim;
+        EXPECT(i < dim && (!sym || i <= j) && cs[k].diag == (i == j));
+        counted[(size_t)i * dim + j] += cs[k].mult / (cs[k].mult == 2.0 ? 2.0 : 1.0);
+        if (cs[k].mult == 2.0) counted[(size_t)j * dim + i] += 1.0;
+        ndiag += cs[k].diag ? 1 : 0;
+        if (k > (size_t)dim) EXPECT(cs[k].comp > cs[k - 1].comp);
+      }
+      EXPECT(ndiag == dim);
+      for (double x : counted) EXPECT(x == 1.0);
+    }
+  {
+    const int nd = 4;
+    std::vector<double> M((size_t)nd * nd);
+    for (int a = 0; a < nd; ++a)
+      for (int b = 0; b < nd; ++b) M[(size_t)a * nd + b] = 10.0 * a + b;
+    const std::vector<double> tri = mass_lower_rows(M, nd);
+    EXPECT(tri.size() == (size_t)nd * (nd + 1) / 2);
+    size_t m = 0;
+    for (int a = 0; a < nd; ++a)
+      for (int b = 0; b <= a; ++b) EXPECT(tri[m++] == 10.0 * a + b);
+  }
 }
 
 int main() {
