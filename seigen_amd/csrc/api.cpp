@@ -172,6 +172,9 @@ static int family_tables(sg_handle* h, Frags& fr) {
           return fail(h, SG_ERR_ARG, e.what());
         }
       }
+      // degree 4: the lifts take their own traces from a wave-private LDS stash (kernels_mfma.hip g_stash); 0 = from memory
+      const char* gs = std::getenv("SEIGEN_HIP_GSTASH");
+      h->gstash = !(gs && std::atoi(gs) == 0);
       break;
     }
     case Family::Tile2d: {
@@ -254,6 +257,7 @@ static int init_launch(sg_handle* h) {
   // Infinity Cache: F stages -3 %, profiles/r03/order_chunk_sweep.txt; the G stages do not gain and keep one
   // contiguous range per XCD).  SEIGEN_HIP_ORDER_CHUNK overrides (0 = off).
   h->order_chunk = 0;
+  if (h->family == Family::Mfma && prepare_stage_mfma() != 0) return fail(h, SG_ERR_DEVICE, "the G stage kernels' dynamic LDS was refused");
   if (h->family == Family::Mfma) {
     const int64_t per_layer = ((int64_t)cfg->n[0] * cfg->n[1] + 15) / 16 * 6;
     if (cfg->n[2] >= 16) h->order_chunk = (int)std::max<int64_t>(6, (per_layer + 7) / 8);

@@ -181,6 +181,7 @@ struct sg_handle {
   // G stages with the factorised volume term (kernels_mfma.hip mfma_stage_G<.., FACT = 1>; double, degrees 3 and 4;
   // SEIGEN_HIP_GQ): the Q tiles and the P_r tiles, or empty
   DevBuf<double> fragQ, fragP;
+  bool gstash = true;      // ... at degree 4 launched in the form with the own traces out of the LDS stash (eight-wave blocks); SEIGEN_HIP_GSTASH=0: the form before it
   DevBuf<double> staging;  // host-layout staging buffer for layout conversion
   // large transfers: two pinned host slots + two device slots, so that the DMA of one chunk, the
   // layout kernel of the next and the host-side copy of the previous one overlap

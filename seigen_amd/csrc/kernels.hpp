@@ -143,7 +143,10 @@ struct StageArgs {
   // layer together, so the z-neighbour traces and the own rows of the next layer meet in the Infinity Cache.
   int32_t order_chunk;
   int32_t nitems;               // MFMA path: items of this launch (the item list's length, or cell groups x classes)
-  void* reserved_;              // unused: keeps every later member, and the tile kernels' T2Const behind StageArgs, at its kernarg offset
+  // MFMA path, G stages with the factorised volume term at degree 4 (one kernel object, two forms): 1 = eight-wave blocks whose
+  // lifts read the own traces out of a wave-private LDS stash, 0 = the form before it (four-wave blocks; SEIGEN_HIP_GSTASH=0)
+  int32_t gstash;
+  int32_t reserved_;            // unused: keeps every later member, and the tile kernels' T2Const behind StageArgs, at its kernarg offset
   // 2-D tile path, G stages: the sparse nodal source (elastic.py:217-218) added inside the stage kernel instead of
   // by a launch of its own.  src_slot[item] = slot of an item (16 cells of one class) that holds source nodes, or -1;
   // src_idx[slot][node][cell] = row of that node in this step's value table src_vals[row][dim*dim], or -1.
@@ -185,6 +188,7 @@ int launch_stage(const void* kernel, int dim, int P, const StageArgs& a, void* s
 
 // MFMA path (3-D, degree >= 3; fields in the gw = 16 interleaved layout)
 int mfma_blocks_per_cu(int P, int f32);
+int prepare_stage_mfma();   // once per handle, outside any stream capture: the dynamic LDS of the degree-4 G kernels' stash form; 0 on success
 const void* stage_kernel_mfma(int kind, int P, const StageArgs& a);
 int launch_stage_mfma(const void* kernel, const StageArgs& a, void* stream);
 

@@ -83,6 +83,45 @@ struct MG {
   static constexpr int NFRAG_P = 3 * MTT * KR;
 };
 
+// G stages at degree 4 in double, factorised volume term (FACT = 1): ONE block of eight waves per CU instead of two of four,
+// so that the waves share one copy of the operator tiles and the LDS that frees holds a wave-private copy ("stash") of
+// the own cell's rows, from which the lifts take their own traces (stage_G_body).  The form before it - four-wave blocks,
+// own traces from memory - stays in the same kernel objects for comparisons (mfma_stage_G, SEIGEN_HIP_GSTASH=0); degree 3
+// has only that form.
+template <typename R, int P, int FACT>
+constexpr bool g_stash() {
+  return sizeof(R) == 8 && P == 4 && FACT == 1;
+}
+// Operator tiles of a stash kernel in LDS: the 16-row tiles as they come (64 doubles in lane order), then the 4-row
+// tiles COMPACT: the A operand of the 4x4x4 shape is one 4x4 tile replicated over the four blocks of cells (lane l holds
+// A[l & 3][l >> 4], mfma_tables.hpp), so 16 doubles hold it - entry (l & 3) + 4 (l >> 4), read by every lane with one
+// broadcast ds_read_b64.  Tables of NOUT operators x (LT large + ST small row tiles) x NKS k-steps, fragment order
+// ((o * (LT + ST) + t) * NKS + ks) in memory.
+template <int NOUT, int LT, int ST, int NKS>
+struct CompactTiles {
+  static constexpr int NL = NOUT * LT * NKS * 64, NS = NOUT * ST * NKS * 16, N = NL + NS;
+  static constexpr int at(int o, int t, int ks) {
+    return t < LT ? ((o * LT + t) * NKS + ks) * 64 : NL + ((o * ST + (t - LT)) * NKS + ks) * 16;
+  }
+};
+constexpr int G_STASH_SLOTS = 36;    // node rows a wave stashes per component: 35 nodes + the clamped row of the last k-step
+constexpr int G_STASH_WAVES = 8;
+// Dynamic LDS of a g_stash kernel, in bytes from its start: the MeshDev copy, (STASH) the facet-node offsets, the P_r, Q and
+// lift tiles, (STASH) the eight stashes.  At degree 4:
+//   STASH = 1   4 320 + 256 + 41 472 (71 tiles x 512 + 40 x 128) + 8 x 13 824 = 156 640 of the CU's 163 840: one block
+//   STASH = 0   4 320 + 56 832 (111 tiles x 512)                              =  61 152: two blocks
+template <typename R, int P, int STASH>
+struct GLds {
+  using M = MG<P, R>;
+  static constexpr int STW = 3 * G_STASH_SLOTS * 16;
+  static constexpr int OFF_FO = ((int)sizeof(MeshDev) + 15) / 16 * 16;
+  static constexpr int OFF_AV = OFF_FO + (STASH ? 64 * (int)sizeof(int) : 0);
+  static constexpr int OFF_Q = OFF_AV + (int)sizeof(R) * (STASH ? CompactTiles<3, M::MTF, M::NSM, M::KR>::N : M::NFRAG_P * 64);
+  static constexpr int OFF_AL = OFF_Q + (int)sizeof(R) * (STASH ? CompactTiles<1, M::QLT, M::QST, M::KS>::N : M::NFRAG_Q * 64);
+  static constexpr int OFF_ST = OFF_AL + (int)sizeof(R) * (STASH ? CompactTiles<4, M::MTF, M::NSM, M::KSF>::N : M::NFRAG_L * 64);
+  static constexpr int BYTES = OFF_ST + (STASH ? G_STASH_WAVES * STW * (int)sizeof(R) : 0);
+};
+
 // Streaming accesses: old values of the fused combine and all results are touched once per launch; the
 // non-temporal hint keeps them from displacing the cell data that the neighbours' lift phases are about to ask
 // the L2 for: fabric reads -4 % (F) to -23 % (G<4,0>), step time -2 %.  (The same hint on the trace loads
@@ -356,6 +395,31 @@ __device__ __forceinline__ void copy_to_lds(R* dst, const R* __restrict__ src) {
   }
 }
 
+// A fragment table into its CompactTiles form (all loads first, as above)
+template <typename CT, int NOUT, int LT, int ST, int NKS, typename R, int NT>
+__device__ __forceinline__ void copy_compact(R* dst, const R* __restrict__ src) {
+  constexpr int PER = (CT::N + NT - 1) / NT;
+  R v[PER];
+#pragma unroll
+  for (int j = 0; j < PER; ++j) {
+    const int i = threadIdx.x + j * NT;
+    int s = 0;
+    if (i < CT::NL) {
+      const int fr = i >> 6, o = fr / (LT * NKS), rem = fr - o * (LT * NKS);   // rem = t * NKS + ks, t < LT
+      s = (o * (LT + ST) * NKS + rem) * 64 + (i & 63);
+    } else {
+      const int i2 = i - CT::NL, fr = i2 >> 4, c = i2 & 15, o = fr / (ST * NKS), rem = fr - o * (ST * NKS);
+      s = (o * (LT + ST) * NKS + LT * NKS + rem) * 64 + (c & 3) + 16 * (c >> 2);     // lane (c & 3) + 16 (c >> 2) holds A[c & 3][c >> 2]
+    }
+    v[j] = (i < CT::N) ? src[s] : R(0);
+  }
+#pragma unroll
+  for (int j = 0; j < PER; ++j) {
+    const int i = threadIdx.x + j * NT;
+    if (i < CT::N) dst[i] = v[j];
+  }
+}
+
 template <int NV, int NL, typename R, int NT = 256>
 __device__ __forceinline__ void load_tables(R* sAV, R* sAL, const StageArgs& A) {
   copy_to_lds<NV * 64, R, NT>(sAV, reinterpret_cast<const R*>(A.fragV));
@@ -409,9 +473,13 @@ __device__ __forceinline__ float ndot<float>(float c0, float c1, float c2, float
 //  tile, m = 4*MTF + s for small tile s), so the three D_r u_i of one node meet in the same lane;
 //  only W_ii and W_ij + W_ji are accumulated (6 * S4 values).
 // --------------------------------------------------------------------------------------------
-template <typename R, int P, int MODE, int SYM, int FACT>
-__global__ __launch_bounds__(256, (mfma_resident_blocks<R, P>())) void mfma_stage_G(StageArgs A) {
+// (FACT: the factorised volume term.  STASH: the lifts' own traces out of the wave's LDS stash, eight waves to a block.
+//  DYN: the LDS is the launch's dynamic allocation, laid out by GLds - the two forms of a g_stash kernel need 61 KB and
+//  153 KB and must not both be charged to every block; every other instantiation keeps its static arrays.)
+template <typename R, int P, int MODE, int SYM, bool FACT, bool STASH, bool DYN>
+__device__ __forceinline__ void stage_G_body(const StageArgs& A) {
   using M = MG<P, R>;
+  constexpr int NT = STASH ? 512 : 256;
   typedef typename RT<R>::v4 d4;
   constexpr int PRIO3 = MODE ? SG_PRIO_G1 : SG_PRIO_G0;
   constexpr int ND = M::ND, NF = M::NF, KS = M::KS, KSF = M::KSF, MTF = M::MTF, NSM = M::NSM, MTT = M::MTT, S4 = M::S4;
@@ -422,12 +490,48 @@ __global__ __launch_bounds__(256, (mfma_resident_blocks<R, P>())) void mfma_stag
   constexpr int QLT = M::QLT, QST = M::QST, KR = M::KR;
   // operator tiles in LDS: the row tiles of the three D_r (E_r: with the own-trace half of the flux folded in), or
   // (FACT) those of the P_r in their place (A.fragV) and the Q tiles beside them
-  __shared__ R sAV[(FACT ? M::NFRAG_P : M::NFRAG_G) * 64];
-  __shared__ R sQ[FACT ? M::NFRAG_Q * 64 : 1];
-  __shared__ R sAL[M::NFRAG_L * 64];
-  __shared__ MeshDev sMd;
-  if constexpr (FACT) copy_to_lds<M::NFRAG_Q * 64>(sQ, reinterpret_cast<const R*>(A.fragQ));
-  load_tables<(FACT ? M::NFRAG_P : M::NFRAG_G), M::NFRAG_L>(sAV, sAL, &sMd, A);
+  // STASH: one copy for eight waves, the 4-row tiles compact (CompactTiles); beside them every wave's stash of its cell
+  // group's own rows, [component][node slot][16 cells], and the stash offsets of the facet nodes per (facet, lane group) x
+  // four k-steps (GLds has the byte counts).
+  using CP = CompactTiles<3, MTF, NSM, KR>;
+  using CQ = CompactTiles<1, QLT, QST, KS>;
+  using CL = CompactTiles<4, MTF, NSM, KSF>;
+  using LY = GLds<R, P, STASH>;
+  constexpr int STW = LY::STW;          // doubles of one wave's stash
+  R *sAV = nullptr, *sQ = nullptr, *sAL = nullptr, *sSt = nullptr;
+  MeshDev* sMdp = nullptr;
+  int* sFo = nullptr;
+  if constexpr (DYN) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sg_dyn_lds[];
+    sMdp = reinterpret_cast<MeshDev*>(sg_dyn_lds);
+    sFo = reinterpret_cast<int*>(sg_dyn_lds + LY::OFF_FO);
+    sAV = reinterpret_cast<R*>(sg_dyn_lds + LY::OFF_AV);
+    sQ = reinterpret_cast<R*>(sg_dyn_lds + LY::OFF_Q);
+    sAL = reinterpret_cast<R*>(sg_dyn_lds + LY::OFF_AL);
+    sSt = reinterpret_cast<R*>(sg_dyn_lds + LY::OFF_ST);
+  } else {
+    __shared__ R sAV_[(FACT ? M::NFRAG_P : M::NFRAG_G) * 64];
+    __shared__ R sQ_[FACT ? M::NFRAG_Q * 64 : 1];
+    __shared__ R sAL_[M::NFRAG_L * 64];
+    __shared__ MeshDev sMd_;
+    sAV = sAV_, sQ = sQ_, sAL = sAL_, sMdp = &sMd_;
+  }
+  MeshDev& sMd = *sMdp;
+  if constexpr (STASH) {
+    static_assert(ND <= G_STASH_SLOTS && 4 * KS <= G_STASH_SLOTS, "a stash slot per B row of the Q pass");
+    copy_to_lds<(int)(sizeof(MeshDev) / sizeof(int)), int, NT>(reinterpret_cast<int*>(&sMd), reinterpret_cast<const int*>(A.md));
+    copy_compact<CQ, 1, QLT, QST, KS, R, NT>(sQ, reinterpret_cast<const R*>(A.fragQ));
+    copy_compact<CP, 3, MTF, NSM, KR, R, NT>(sAV, reinterpret_cast<const R*>(A.fragV));
+    copy_compact<CL, 4, MTF, NSM, KSF, R, NT>(sAL, reinterpret_cast<const R*>(A.fragL));
+    if (threadIdx.x < 64) {   // entry (f * 4 + q) * 4 + ks: byte offset of my element node of facet node 4 ks + q (padded rows: node of facet node 0, as in request)
+      const int f = threadIdx.x >> 4, bq4 = 4 * (threadIdx.x & 3) + ((threadIdx.x >> 2) & 3);
+      sFo[threadIdx.x] = (int)A.md->fnode[f][bq4 < NF ? bq4 : 0] * 16 * (int)sizeof(R);
+    }
+    __syncthreads();
+  } else {
+    if constexpr (FACT) copy_to_lds<M::NFRAG_Q * 64>(sQ, reinterpret_cast<const R*>(A.fragQ));
+    load_tables<(FACT ? M::NFRAG_P : M::NFRAG_G), M::NFRAG_L>(sAV, sAL, &sMd, A);
+  }
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -467,6 +571,14 @@ __global__ __launch_bounds__(256, (mfma_resident_blocks<R, P>())) void mfma_stag
     // all of them into registers (and, unlike a laundered pointer, keeps the reads ds_read_b64)
     int lo = lane;
     asm volatile("" : "+v"(lo));
+    // STASH: a lane's entry of a compact 4-row tile; where it writes its B rows of the Q pass (k-step ks, lane group q = node
+    // slot 4 ks + q: the four lane groups write four consecutive 128-byte rows) and reads the own trace of a facet node.
+    // The stash belongs to the wave: writer and reader are the same wave, whose LDS operations stay in order, so no barrier
+    // stands between the Q pass and the lifts or between two items - the lgkmcnt wait in front of a read's use is all.
+    const int lo4 = (lo & 3) + ((lo >> 4) << 2);
+    R* const stw = sSt + (STASH ? wave * STW : 0) + lo;
+    const char* const str = reinterpret_cast<const char*>(sSt + (STASH ? wave * STW : 0) + (lo & 15));
+    auto tile = [&](const R* tab, int full, int at, int t, int nlarge) { return STASH ? tab[at + (t < nlarge ? lo : lo4)] : tab[full * 64 + lo]; };
 
     R Jm[3][3], cnf[4][3];  // class constants (wave-uniform)
 #pragma unroll
@@ -485,8 +597,8 @@ __global__ __launch_bounds__(256, (mfma_resident_blocks<R, P>())) void mfma_stag
       for (int m = 0; m < S4; ++m) Sd[i][m] = So[i][m] = R(0);
 
     constexpr int NB = 2;   // trace buffers: facet f in nx[f % NB], the next NB - 1 facets on their way
-    constexpr int NBO = FACT ? NB : 1;
-    R nx[NB][KSF][3], nxo[NBO][KSF][3];   // nxo (FACT): the own traces of the same facet nodes
+    constexpr int NBO = (FACT && !STASH) ? NB : 1;
+    R nx[NB][KSF][3], nxo[NBO][KSF][3];   // nxo (FACT without a stash): the own traces of the same facet nodes
     auto request = [&](int f, R (&dst)[KSF][3], R (&dso)[KSF][3]) {
       const NbrRef<R> NR = nbr_from_entry<ND, NF, 3>(A, nbe[f], 2 * sMd.nb_axis[k][f] + (sMd.nb_dir[k][f] > 0 ? 1 : 0), own);
 #pragma unroll
@@ -498,8 +610,9 @@ __global__ __launch_bounds__(256, (mfma_resident_blocks<R, P>())) void mfma_stag
         for (int i = 0; i < 3; ++i) {
           dst[ks][i] = NR.p[(nn * 3 + i) * NR.cstride];
           // FACT: u^ = 1/2 (own + neighbour) (own + own on a boundary facet), the 1/2 being part of the lift tiles.
-          // Two loads per value: the own rows were read a phase ago and come out of the L2.
-          if constexpr (FACT) dso[ks][i] = own[(on * 3 + i) * 16];
+          // Two loads per value: the own rows were read a phase ago and come out of the L2 - or (STASH) no second load: the
+          // lifts read the own value out of the wave's stash when they need it.
+          if constexpr (FACT && !STASH) dso[ks][i] = own[(on * 3 + i) * 16];
         }
       }
     };
@@ -545,7 +658,7 @@ __global__ __launch_bounds__(256, (mfma_resident_blocks<R, P>())) void mfma_stag
     auto tiles_step = [&](int nks, int r, int ks, const R (&b)[3], d4 (&acc)[M::MTFA][3], R (&accs)[M::NSMA][3]) {
 #pragma unroll
       for (int t = 0; t < MTT; ++t) {
-        const R a = sAV[((r * MTT + t) * nks + ks) * 64 + lo];
+        const R a = tile(sAV, (r * MTT + t) * nks + ks, CP::at(r, t, ks), t, MTF);
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
           if (t < MTF)
@@ -625,9 +738,13 @@ __global__ __launch_bounds__(256, (mfma_resident_blocks<R, P>())) void mfma_stag
 #pragma unroll
           for (int i = 0; i < 3; ++i) bq[ks % PF][i] = brow(ks + PF)[i * 16];
         }
+        if constexpr (STASH) {   // the own rows pass through the registers once, here: keep them for the lifts
+#pragma unroll
+          for (int i = 0; i < 3; ++i) stw[(i * G_STASH_SLOTS + 4 * ks) * 16] = b[i];
+        }
 #pragma unroll
         for (int t = 0; t < QLT + QST; ++t) {
-          const R a = sQ[(t * KS + ks) * 64 + lo];
+          const R a = tile(sQ, t * KS + ks, CQ::at(0, t, ks), t, QLT);
 #pragma unroll
           for (int i = 0; i < 3; ++i) {
             if (t < QLT)
@@ -671,7 +788,15 @@ __global__ __launch_bounds__(256, (mfma_resident_blocks<R, P>())) void mfma_stag
 #pragma unroll
       for (int f = 0; f < 4; ++f) {
         R(&flf)[KSF][3] = nx[f % NB];
-        if constexpr (FACT) {
+        if constexpr (STASH) {
+          // the facet's four node offsets of this lane group: one ds_read_b128 (item-invariant, but sixteen registers if kept)
+          const nbr4 fo = *reinterpret_cast<const nbr4*>(&sFo[f * 16 + (lo >> 4) * 4]);
+#pragma unroll
+          for (int ks = 0; ks < KSF; ++ks)
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+              flf[ks][i] += *reinterpret_cast<const R*>(str + fo[ks] + i * G_STASH_SLOTS * 16 * (int)sizeof(R));
+        } else if constexpr (FACT) {
 #pragma unroll
           for (int ks = 0; ks < KSF; ++ks)
 #pragma unroll
@@ -712,7 +837,7 @@ __global__ __launch_bounds__(256, (mfma_resident_blocks<R, P>())) void mfma_stag
             for (int i = 0; i < 3; ++i) tmp[i] = d4{0, 0, 0, 0};
 #pragma unroll
             for (int ks = 0; ks < KSF; ++ks) {
-              const R a = sAL[((f * MTT + t) * KSF + ks) * 64 + lo];
+              const R a = tile(sAL, (f * MTT + t) * KSF + ks, CL::at(f, t, ks), t, MTF);
 #pragma unroll
               for (int i = 0; i < 3; ++i) tmp[i] = MFMA64(a, flf[ks][i], tmp[i]);
             }
@@ -728,7 +853,7 @@ __global__ __launch_bounds__(256, (mfma_resident_blocks<R, P>())) void mfma_stag
             R tmp[3] = {R(0), R(0), R(0)};
 #pragma unroll
             for (int ks = 0; ks < KSF; ++ks) {
-              const R a = sAL[((f * MTT + t) * KSF + ks) * 64 + lo];
+              const R a = tile(sAL, (f * MTT + t) * KSF + ks, CL::at(f, t, ks), t, MTF);
 #pragma unroll
               for (int i = 0; i < 3; ++i) tmp[i] = MFMA4(a, flf[ks][i], tmp[i]);
             }
@@ -841,6 +966,21 @@ __global__ __launch_bounds__(256, (mfma_resident_blocks<R, P>())) void mfma_stag
     STAMP_ACC;
   }
   STAMP_FLUSH;
+}
+
+// A g_stash instantiation holds BOTH forms and the launch picks one by its block: 512 threads and GLds<.., 1>::BYTES of dynamic
+// LDS run the stash form, 256 threads and GLds<.., 0>::BYTES the form before it (launch_stage_mfma, StageArgs::gstash) - one
+// kernel object and one name per (MODE, SYM), two bodies that share nothing but the arguments.  The branch is on a scalar.
+template <typename R, int P, int MODE, int SYM, int FACT>
+__global__ __launch_bounds__((g_stash<R, P, FACT>() ? 512 : 256), (g_stash<R, P, FACT>() ? 1 : mfma_resident_blocks<R, P>())) void mfma_stage_G(StageArgs A) {
+  if constexpr (g_stash<R, P, FACT>()) {
+    if (blockDim.x == 512)
+      stage_G_body<R, P, MODE, SYM, true, true, true>(A);
+    else
+      stage_G_body<R, P, MODE, SYM, true, false, true>(A);
+  } else {
+    stage_G_body<R, P, MODE, SYM, FACT != 0, false, false>(A);
+  }
 }
 
 // --------------------------------------------------------------------------------------------
@@ -1358,17 +1498,49 @@ const void* stage_kernel_mfma(int kind, int P, const StageArgs& a) {
   });
 }
 
+static_assert(GLds<double, 4, 1>::BYTES == 156640 && GLds<double, 4, 1>::BYTES <= 160 * 1024, "stash form: one block per CU");
+static_assert(GLds<double, 4, 0>::BYTES == 61152 && 2 * GLds<double, 4, 0>::BYTES <= 160 * 1024, "form without a stash: two blocks per CU");
+
+// the G kernels of degree 4 that hold two forms (g_stash): these take their LDS from the launch
+static bool two_form_kernel(const void* kernel) {
+  for (int v = 0; v < 4; ++v) {
+    const void* k = sg_pick<0, 1>(v & 1, [&](auto mode) {
+      return sg_pick<0, 1>(v >> 1, [&](auto sym) { return (const void*)&mfma_stage_G<double, 4, decltype(mode)::value, decltype(sym)::value, 1>; });
+    });
+    if (k == kernel) return true;
+  }
+  return false;
+}
+
+// once per handle of the MFMA family, outside any stream capture: allow the stash form its dynamic LDS (more than the 64 KB
+// a launch may ask for unprepared); 0 on success
+int prepare_stage_mfma() {
+  for (int v = 0; v < 4; ++v) {
+    const void* k = sg_pick<0, 1>(v & 1, [&](auto mode) {
+      return sg_pick<0, 1>(v >> 1, [&](auto sym) { return (const void*)&mfma_stage_G<double, 4, decltype(mode)::value, decltype(sym)::value, 1>; });
+    });
+    if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, GLds<double, 4, 1>::BYTES) != hipSuccess) return -1;
+  }
+  return 0;
+}
+
 int launch_stage_mfma(const void* kernel, const StageArgs& a, void* stream) {
-  // persistent grid, at most 2 blocks per CU; a multiple of 8 (one item range per XCD label)
-  // ... and no more blocks than there are items for their four waves (small blocks - the reference's own 3-D sweeps run
+  // persistent grid, at most 2 blocks of four waves per CU; a multiple of 8 (one item range per XCD label)
+  // ... and no more blocks than there are items for their waves (small blocks - the reference's own 3-D sweeps run
   // N <= 8 - are launch-bound: every block copies the operator tiles into LDS before its first item)
+  // a.grid_blocks counts slots of FOUR waves whatever the kernel: an eight-wave block of the stash form takes two (the same
+  // waves on the same CUs, blockIdx % 8 still the XCD), and there are at least eight blocks, so that every XCD label has one
+  const bool two = two_form_kernel(kernel), stash = two && a.gstash;
+  const unsigned wpb = stash ? 8u : 4u;
+  const unsigned lds = two ? (unsigned)(stash ? GLds<double, 4, 1>::BYTES : GLds<double, 4, 0>::BYTES) : 0u;
   unsigned nblk = (unsigned)(a.grid_blocks > 0 ? a.grid_blocks : 512);
+  if (stash) nblk = nblk / 16u * 8u > 8u ? nblk / 16u * 8u : 8u;
   if (a.nitems > 0 && !a.spread) {
-    const unsigned need = (((unsigned)a.nitems + 3u) / 4u + 7u) / 8u * 8u;
+    const unsigned need = (((unsigned)a.nitems + wpb - 1u) / wpb + 7u) / 8u * 8u;
     nblk = need < nblk ? need : nblk;
   }
   void* args[] = {const_cast<StageArgs*>(&a)};
-  (void)hipLaunchKernel(kernel, dim3(nblk), dim3(256), args, 0, (hipStream_t)stream);
+  (void)hipLaunchKernel(kernel, dim3(nblk), dim3(wpb * 64u), args, lds, (hipStream_t)stream);
   return (int)hipGetLastError();
 }
 

@@ -66,6 +66,7 @@ static int stage_args(sg_handle* h, const LaunchCtx& ctx, StageArgs& a, const St
   if (kind == 1 && h->fragQ.get()) {      // G stages with the factorised volume term
     a.fragV = h->fragP.get();
     a.fragQ = h->fragQ.get();
+    a.gstash = h->gstash ? 1 : 0;
   }
   a.sym = h->sym ? 1 : 0;
   a.f32 = h->f32;
