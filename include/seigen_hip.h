@@ -291,6 +291,42 @@ int sg_set_monitor(sg_handle* h, int64_t every, int64_t capacity, const double* 
  * *nsamples = samples taken */
 int sg_get_monitor(sg_handle* h, double* out, size_t nbytes, int64_t* nsamples);
 
+/* ---- correlation: the zero-lag cross-correlation of two handles' fields, cell by cell, accumulated on the device (the
+ * observer between the point-wise one and the block-wide one: what imaging and material-gradient loops form from a forward
+ * and an adjoint or back-propagated wavefield) ---------------------------------------------------------------------------
+ * For two handles a, b of the same shape, with Mhat and |det J| as above, every cell c of the block has
+ *   Buu_c = sum_i  a.u_i^T  Mhat b.u_i,
+ *   Bss_c = sum_ij a.s_ij^T Mhat b.s_ij,
+ *   Btt_c = t_a^T Mhat t_b,   t_x = sum_i x.s_ii node by node,
+ *   acc_a[c][k] += w[k] |det J| B_k,c        k = uu, ss, tt
+ * of u = SG_FIELD_U and s = SG_FIELD_S of each handle.  acc_a is a device buffer [ncells][3] of doubles owned by a, in host
+ * cell order cube * ncls + cls; the first successful sg_correlate allocates and zeroes it.  It is double for FP32 blocks
+ * too: every nodal value is converted first.
+ * Arithmetic: a form x^T Mhat y is sum_alpha x_alpha r_alpha with r = Mhat y, r_alpha summed over beta ascending and the
+ * products over alpha ascending, with fma, from zero for every component.  Components: the velocity's, then the stress's
+ * row-major; Buu adds the components' forms in that order, Bss takes fma(mult, form, Bss), then acc = fma(w[k] |det J|,
+ * B_k, acc) with the factor rounded once.  Each handle reads (i, j) from the line its own storage mode holds, the mirror
+ * (min, max) in symmetric storage; when both handles are symmetric only i <= j is read and an off-diagonal form counts
+ * twice (mult = 2), otherwise all d^2 pairs are formed.  The matrix-pipe form (3-D P3 / P4 blocks in the 16-cube layout)
+ * computes r with v_mfma_f64_16x16x4_f64 - four beta at a time, the sums inside the instruction in the hardware's own fixed
+ * order - and every lane of the four that share a cell sums alpha = 4 m + q over m ascending, q = its lane group; the groups
+ * are then added as (q0 + q2) + (q1 + q3).  There is no sum across cells and no atomic: the bits of a cell's result depend
+ * only on that cell's nodal values in both handles, the weights, the dtype and the kernel form - not on nbr_mask, the stage
+ * kernels of either handle or the order of launches.  Cells of the layout's padding contribute nothing; ghost traces are
+ * no part of a block.
+ * Handles: b may be a itself.  Otherwise both must be on the same device and agree in dim, degree, cell type and diagonal,
+ * dtype, n[], h[] and the layout of their fields (the kernel family's group width); anything else returns SG_ERR_ARG and
+ * sg_last_error(a) names the first difference.  nbr_mask, material, sponge, source and storage mode may differ.
+ * Ordering: the launch runs on a's stream after everything both handles have queued, and b's stream waits for it: a later
+ * sg_step(b) cannot overwrite what is being read.  There is no arming and no graph integration: the caller drives the
+ * call between its stepping calls.  By bilinearity B(a, (b^{n+1} - b^n) / dt) is two calls with weights -+ 1/dt.
+ * A failed call leaves the accumulator, the fields and both handles untouched. */
+int sg_correlate(sg_handle* a, sg_handle* b, const double w[3]);     /* w = NULL: (1, 1, 1) */
+/* acc_a -> out[ncells][3]; SG_ERR_STATE before the first successful sg_correlate, SG_ERR_ARG for another nbytes */
+int sg_get_correlation(sg_handle* a, double* out, size_t nbytes);
+/* zero the accumulator (behind what a has queued); release != 0: free it and the tables with it */
+int sg_reset_correlation(sg_handle* a, int release);
+
 /* un-fused operators for stage-level parity tests:
  *   out = Minv f(w; s_in, u_abs)   (elastic.py:204-209 + :358-367)
  *   out = Minv g(v; u_in)          (elastic.py:211-219 + :358-367)

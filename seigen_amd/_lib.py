@@ -73,6 +73,9 @@ SYMBOLS = {
     "sg_measure": (C.c_int, [_P, _P, C.c_int, _P]),
     "sg_set_monitor": (C.c_int, [_P, C.c_int64, C.c_int64, _P, C.c_int]),
     "sg_get_monitor": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_int64)]),
+    "sg_correlate": (C.c_int, [_P, _P, _P]),
+    "sg_get_correlation": (C.c_int, [_P, _P, C.c_size_t]),
+    "sg_reset_correlation": (C.c_int, [_P, C.c_int]),
     "sg_locate_points": (C.c_int, [C.POINTER(SgConfig), C.c_int64, _P, _P, _P]),
     "sg_apply_F": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     "sg_apply_G": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),

@@ -266,6 +266,26 @@ class HipBlock(object):
         check(self.lib.sg_get_monitor(self.h, out.ctypes.data, out.nbytes, C.byref(n)), self.h)
         return out[:n.value]
 
+    # ---- correlation (sg_correlate / sg_get_correlation / sg_reset_correlation) -----------------------
+    def correlate(self, other, w=None):
+        """acc[c] += w * |det J| * (Buu_c, Bss_c, Btt_c) of this block's (u, s) against `other`'s (another HipBlock of the
+        same shape on the same device, or this one), cell by cell on the device (sg_correlate); w: one triple, None = 1."""
+        if w is not None:
+            w = _f64(w)
+            if w.shape != (3,):
+                raise ValueError("weights are one (w_uu, w_ss, w_tt), not %r" % (w.shape,))
+        check(self.lib.sg_correlate(self.h, other.h, None if w is None else w.ctypes.data), self.h)
+
+    def get_correlation(self):
+        """The accumulator [ncells, 3] = (uu, ss, tt) in host cell order."""
+        out = np.empty((self.ncells, 3))
+        check(self.lib.sg_get_correlation(self.h, out.ctypes.data, out.nbytes), self.h)
+        return out
+
+    def reset_correlation(self, release=False):
+        """Zero the accumulator; release: free it (get_correlation then raises until the next correlate)."""
+        check(self.lib.sg_reset_correlation(self.h, int(bool(release))), self.h)
+
     def apply_F(self, s_in, u_abs, u_out):
         check(self.lib.sg_apply_F(self.h, s_in, u_abs, u_out), self.h)
 

@@ -739,6 +739,107 @@ int sg_get_monitor(sg_handle* h, double* out, size_t nbytes, int64_t* nsamples) 
   return SG_OK;
 }
 
+// The correlation (kernels_xcorr.hip).  The first successful call builds the handle's tables - the operator in the form the
+// kernel takes, the zeroed accumulator, the two events - in locals and moves them into the handle after the launch is queued;
+// every refusal comes before anything is queued.
+static int correlation_prepare(sg_handle* a, CorrelationTables& ct) {
+  const int gw = (int)a->md.gw, nd = a->re.nd;
+  const int tensor = a->cfg.diagonal == SG_DIAGONAL_QUAD ? 1 : 0;
+  const char* form = std::getenv("SEIGEN_HIP_XCORR");
+  ct.mfma = xcorr_has_mfma(a->cfg.dim, nd, gw, tensor) && !(form && std::strcmp(form, "lds") == 0);
+  ct.nitems = (a->md.ncube_pad / gw) * a->ncls;
+  ct.ipw = ct.mfma ? 0 : xcorr_items_per_group(nd, gw);
+  ct.grid = (ct.mfma || ct.ipw > 0) ? prepare_xcorr(nd, gw, ct.ipw, ct.mfma ? 1 : 0, a->f32, a->ncu) : -1;
+  if (ct.grid <= 0) return fail(a, SG_ERR_DEVICE, "sg_correlate: no kernel for this element");
+  const std::vector<double> op = ct.mfma ? xcorr_mass_tiles(a->re.Mhat, nd) : a->re.Mhat;
+  HIPCHECK(a, ct.M.upload(op.data(), op.size()));
+  if (ct.acc.alloc((size_t)a->ncells * 3) != hipSuccess) return fail(a, SG_ERR_NOMEM, "sg_correlate: hipMalloc of the accumulator failed");
+  HIPCHECK(a, hipMemset(ct.acc.get(), 0, (size_t)a->ncells * 3 * sizeof(double)));
+  HIPCHECK(a, ct.ev_in.create());
+  HIPCHECK(a, ct.ev_out.create());
+  ct.ready = true;
+  return SG_OK;
+}
+
+int sg_correlate(sg_handle* a, sg_handle* b, const double w[3]) {
+  if (!a) return SG_ERR_ARG;
+  if (!b) return fail(a, SG_ERR_ARG, "sg_correlate: no second handle");
+  if (b != a) {
+    const std::string diff = xcorr_first_difference(a->cfg, (int)a->md.gw, b->cfg, (int)b->md.gw);
+    if (!diff.empty()) return fail(a, SG_ERR_ARG, "sg_correlate: the handles differ in " + diff);
+  }
+  HIPCHECK(a, hipSetDevice(a->cfg.device));
+  CorrelationTables fresh;
+  if (!a->cor.ready)
+    if (int rc = correlation_prepare(a, fresh)) return rc;
+  const CorrelationTables& ct = a->cor.ready ? a->cor : fresh;
+  xcorr::Args x;
+  std::memset(&x, 0, sizeof(x));
+  x.ua = a->field.read(SG_FIELD_U);
+  x.sa = a->field.read(SG_FIELD_S);
+  x.ub = b->field.read(SG_FIELD_U);
+  x.sb = b->field.read(SG_FIELD_S);
+  x.M = ct.M.get();
+  x.acc = ct.acc.get();
+  double detj = 1.0;
+  for (int k = 0; k < a->cfg.dim; ++k) detj *= a->cfg.h[k];
+  for (int k = 0; k < 3; ++k) x.wd[k] = (w ? w[k] : 1.0) * detj;
+  x.nitems = ct.nitems;
+  x.ncube = a->md.ncube;
+  x.nd = a->re.nd;
+  x.dim = a->cfg.dim;
+  x.gw = (int32_t)a->md.gw;
+  x.ncls = a->ncls;
+  x.ipw = ct.ipw;
+  const std::vector<XcorrComp> comps = xcorr_components(a->cfg.dim, a->sym, b->sym);
+  x.ncomp = (int32_t)comps.size();
+  for (size_t k = 0; k < comps.size(); ++k) {
+    x.comp_a[k] = comps[k].comp_a;
+    x.comp_b[k] = comps[k].comp_b;
+    x.diag[k] = comps[k].diag ? 1 : 0;
+    x.mult[k] = comps[k].mult;
+  }
+  // behind everything both handles have queued; b's later work behind the launch
+  if (int rc = join_second(a)) return rc;
+  if (b != a) {
+    if (join_second(b) != SG_OK) return fail(a, SG_ERR_DEVICE, std::string("sg_correlate: second handle: ") + b->err);
+    HIPCHECK(a, hipEventRecord(ct.ev_in.get(), b->stream));
+    HIPCHECK(a, hipStreamWaitEvent(a->stream, ct.ev_in.get(), 0));
+  }
+  if (launch_xcorr(x, ct.mfma ? 1 : 0, a->f32, ct.grid, a->stream) != 0) return fail(a, SG_ERR_DEVICE, "correlation launch failed");
+  if (b != a) {
+    HIPCHECK(a, hipEventRecord(ct.ev_out.get(), a->stream));
+    HIPCHECK(a, hipStreamWaitEvent(b->stream, ct.ev_out.get(), 0));
+  }
+  if (!a->cor.ready) a->cor = std::move(fresh);
+  return SG_OK;
+}
+
+int sg_get_correlation(sg_handle* a, double* out, size_t nbytes) {
+  if (!a) return SG_ERR_ARG;
+  if (!a->cor.ready) return fail(a, SG_ERR_STATE, "sg_get_correlation: no correlation yet (sg_correlate)");
+  const size_t want = (size_t)a->ncells * 3 * sizeof(double);
+  if (nbytes != want || !out)
+    return fail(a, SG_ERR_ARG, "sg_get_correlation: the buffer must hold ncells x 3 doubles (" + std::to_string(want) + " bytes)");
+  HIPCHECK(a, hipSetDevice(a->cfg.device));
+  HIPCHECK(a, sync_all(a));
+  HIPCHECK(a, hipMemcpy(out, a->cor.acc.get(), want, hipMemcpyDeviceToHost));
+  return SG_OK;
+}
+
+int sg_reset_correlation(sg_handle* a, int release) {
+  if (!a) return SG_ERR_ARG;
+  if (!a->cor.ready) return SG_OK;
+  HIPCHECK(a, hipSetDevice(a->cfg.device));
+  if (release) {
+    HIPCHECK(a, sync_all(a));
+    a->cor = CorrelationTables();
+    return SG_OK;
+  }
+  HIPCHECK(a, hipMemsetAsync(a->cor.acc.get(), 0, (size_t)a->ncells * 3 * sizeof(double), a->stream));
+  return SG_OK;
+}
+
 int sg_get_sym(const sg_handle* h, int* sym) {
   if (!h || !sym) return SG_ERR_ARG;
   *sym = h->sym ? 1 : 0;

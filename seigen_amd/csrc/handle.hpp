@@ -1,5 +1,5 @@
 // The handle behind the C-ABI (include/seigen_hip.h) and what its translation units share:
-//   api.cpp      create / destroy, parameters, sponge, source, receivers, monitor: device checks, uploads, the move into the handle
+//   api.cpp      create / destroy, parameters, sponge, source, receivers, monitor, correlation: device checks, uploads, the move into the handle
 //   transfer.cpp host <-> device field transfers (layout conversion, pinned pipeline)
 //   stages.cpp   regions, stage launches, the LF4 step, graphs, halo packs, timing
 // and, without a device or a HIP header (the CPU sanitizer build, `make host-asan`):
@@ -141,6 +141,45 @@ struct MeasureScratch {
   bool ready = false;
 };
 
+// An event of the runtime with one owner, as DevBuf is for arrays
+struct DevEvent {
+  DevEvent() = default;
+  DevEvent(DevEvent&& o) noexcept : e_(o.e_) { o.e_ = nullptr; }
+  DevEvent& operator=(DevEvent&& o) noexcept {
+    if (this != &o) {
+      reset();
+      std::swap(e_, o.e_);
+    }
+    return *this;
+  }
+  ~DevEvent() { reset(); }
+  hipEvent_t get() const { return e_; }
+  void reset() {
+    if (e_) (void)hipEventDestroy(e_);
+    e_ = nullptr;
+  }
+  hipError_t create() {
+    reset();
+    return hipEventCreateWithFlags(&e_, hipEventDisableTiming);
+  }
+
+ private:
+  hipEvent_t e_ = nullptr;
+};
+
+// The correlation of sg_correlate (kernels_xcorr.hip): built by the handle's first successful call and kept until
+// sg_reset_correlation releases it
+struct CorrelationTables {
+  DevBuf<double> acc;         // [ncells][3] = (uu, ss, tt) in host cell order
+  DevBuf<double> M;           // the operator in the form the kernel takes: hostlogic.hpp xcorr_mass_tiles, or Mhat [nd][nd]
+  bool mfma = false;          // the matrix-pipe form (SEIGEN_HIP_XCORR=lds: the LDS-staged one on its layouts too)
+  int ipw = 0;                // xcorr::Args::ipw
+  int grid = 0;               // persistent grid of the matrix-pipe form
+  int64_t nitems = 0;
+  DevEvent ev_in, ev_out;     // the other handle's stream -> the launch -> the other handle's stream
+  bool ready = false;
+};
+
 // The four fields of a block.  Whoever writes one asks for it with write(), which counts the write: what remembers a field
 // state (the sponge pre-pass, hostlogic.hpp PrePass) can then tell that the field has moved on - from a stage, a source
 // launch, an upload or the mirror launch alike.  Readers take the const pointer.
@@ -212,6 +251,7 @@ struct sg_handle {
   MonitorTables mon;
   MeasureScratch msr;
   bool graph_mon = false;     // the captured graphs contain the monitor's launches
+  CorrelationTables cor;
   // halo
   const double* ghost[4][6] = {};
   // execution

@@ -198,6 +198,58 @@ inline std::vector<double> mass_lower_rows(const std::vector<double>& Mhat, int 
   return r;
 }
 
+// The correlation of two handles' fields (seigen_hip.h sg_correlate; kernels_xcorr.hip).  What its kernels read, in the order
+// they read it: the dim components of the velocity, then the stress's row-major.  Each handle reads entry (i, j) from the
+// line its own storage holds - the mirror (min, max) in symmetric storage.  Both symmetric: only i <= j, an off-diagonal
+// form counts twice; otherwise all dim^2 pairs.  The diagonal ones also make up the traces t_a, t_b.
+struct XcorrComp {
+  int comp_a = 0, comp_b = 0;   // index of the component in a's / b's field (velocity: i, stress: i * dim + j)
+  bool stress = false, diag = false;
+  double mult = 1.0;
+};
+inline std::vector<XcorrComp> xcorr_components(int dim, bool sym_a, bool sym_b) {
+  std::vector<XcorrComp> r;
+  for (int i = 0; i < dim; ++i) r.push_back({i, i, false, false, 1.0});
+  const bool both = sym_a && sym_b;
+  auto line = [dim](bool sym, int i, int j) { return sym && i > j ? j * dim + i : i * dim + j; };
+  for (int i = 0; i < dim; ++i)
+    for (int j = both ? i : 0; j < dim; ++j)
+      r.push_back({line(sym_a, i, j), line(sym_b, i, j), true, i == j, (both && i != j) ? 2.0 : 1.0});
+  return r;
+}
+// The reference mass matrix as the A operands of v_mfma_f64_16x16x4_f64, padded with zeros to whole 16 x 4 tiles: tile
+// (rt, ks) holds rows 16 rt .. + 15, columns 4 ks .. + 3, and lane l of a wave holds its entry (row l & 15, column l >> 4):
+// tiles[(rt * nks + ks) * 64 + l], nrt = ceil(nd / 16) row tiles of nks = ceil(nd / 4) k-steps.
+inline int xcorr_row_tiles(int nd) { return (nd + 15) / 16; }
+inline int xcorr_k_steps(int nd) { return (nd + 3) / 4; }
+inline std::vector<double> xcorr_mass_tiles(const std::vector<double>& Mhat, int nd) {
+  const int nrt = xcorr_row_tiles(nd), nks = xcorr_k_steps(nd);
+  std::vector<double> r((size_t)nrt * nks * 64, 0.0);
+  for (int rt = 0; rt < nrt; ++rt)
+    for (int ks = 0; ks < nks; ++ks)
+      for (int l = 0; l < 64; ++l) {
+        const int row = 16 * rt + (l & 15), col = 4 * ks + (l >> 4);
+        if (row < nd && col < nd) r[((size_t)rt * nks + ks) * 64 + l] = Mhat[(size_t)row * nd + col];
+      }
+  return r;
+}
+// Two handles correlate when they are on one device and agree in dim, degree, cell type and diagonal, dtype, n[], h[] and
+// the layout of their fields (gw); nbr_mask, origin and everything set later may differ.  Returns the name of the first
+// difference in that order, or an empty string.
+inline std::string xcorr_first_difference(const sg_config& a, int gw_a, const sg_config& b, int gw_b) {
+  if (a.device != b.device) return "device";
+  if (a.dim != b.dim) return "dim";
+  if (a.degree != b.degree) return "degree";
+  if (a.diagonal != b.diagonal) return "diagonal";
+  if (a.dtype != b.dtype) return "dtype";
+  for (int k = 0; k < a.dim; ++k)
+    if (a.n[k] != b.n[k]) return "n[" + std::to_string(k) + "]";
+  for (int k = 0; k < a.dim; ++k)
+    if (a.h[k] != b.h[k]) return "h[" + std::to_string(k) + "]";
+  if (gw_a != gw_b) return "field layout (gw " + std::to_string(gw_a) + " against " + std::to_string(gw_b) + ")";
+  return std::string();
+}
+
 struct Box {
   int o[3], n[3];
 };

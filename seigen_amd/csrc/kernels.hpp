@@ -325,4 +325,36 @@ int prepare_measure(int nd, int gw, int ips, int f32);
 // both passes on `stream`; a.nchunks = 0 launches nothing
 int launch_measure(const void* u, const void* s, const measure::Args& a, int f32, void* stream);
 
+// The per-cell correlation of two handles' fields (kernels_xcorr.hip; seigen_hip.h sg_correlate): acc[cell][k] +=
+// wd[k] * B_k of the cell, k = uu, ss, tt; one launch, no sum across cells.
+namespace xcorr {
+constexpr int MAX_COMP = 12;   // dim velocity components + dim^2 stress components
+struct Args {
+  const void* ua;          // handle a: velocity and stress
+  const void* sa;
+  const void* ub;          // handle b
+  const void* sb;
+  const double* M;         // xcorr_lds: the reference mass matrix [nd][nd]; xcorr_mfma: its A tiles (hostlogic.hpp xcorr_mass_tiles)
+  double* acc;             // [ncells][3] in host cell order cube * ncls + cls
+  double wd[3];            // w[k] * |det J|
+  int64_t nitems, ncube;
+  int32_t nd, dim, gw, ncls;
+  int32_t ipw;             // xcorr_lds: items a workgroup of 64 lanes works on (xcorr_items_per_group)
+  int32_t ncomp;           // hostlogic.hpp xcorr_components, in that order
+  int32_t comp_a[MAX_COMP], comp_b[MAX_COMP];
+  int32_t diag[MAX_COMP];
+  double mult[MAX_COMP];
+};
+}  // namespace xcorr
+// the matrix-pipe form takes this layout (the 3-D simplices at P3 / P4 in the gw = 16 layout)
+inline bool xcorr_has_mfma(int dim, int nd, int gw, int tensor) { return gw == 16 && dim == 3 && !tensor && (nd == 20 || nd == 35); }
+// items a workgroup of the LDS-staged form holds at a time, 4 nd ipw gw doubles in at most 64 KB and ipw gw <= 64 lanes; 0: none fits
+int xcorr_items_per_group(int nd, int gw);
+size_t xcorr_lds_bytes(int nd, int gw, int ipw);
+// once per handle: allow the LDS-staged form its dynamic LDS (returns 1), or ask how many blocks of the matrix-pipe form a
+// device of ncu CUs holds - its persistent grid, the `grid` of launch_xcorr; <= 0 on failure
+int prepare_xcorr(int nd, int gw, int ipw, int mfma, int f32, int ncu);
+// one launch on `stream`: the matrix-pipe form (mfma != 0; a.M = the A tiles) or the LDS-staged one (a.M = [nd][nd])
+int launch_xcorr(const xcorr::Args& a, int mfma, int f32, int grid, void* stream);
+
 }  // namespace sg

@@ -55,6 +55,23 @@ def monitor_weights(dim, density, mu, l, ncells):
     return np.ascontiguousarray(w if per_cell else w[0])
 
 
+def sensitivity(dim, density, lam, mu, corr):
+    """The derivatives of rho * uu + alpha * ss + beta * tt with respect to rho, lambda and mu at fixed correlations
+    corr = {"uu", "ss", "tt"} (ElasticLF4.correlation), where alpha = 1 / (2 mu) and beta = -lambda / (2 mu (d lambda +
+    2 mu)) make alpha s:s' + beta tr s tr s' the compliance form s : C^-1 : s' (twice the monitor's ws, wt):
+      K_rho = uu,   K_lambda = -tt / (d lambda + 2 mu)^2,
+      K_mu = -ss / (2 mu^2) + lambda (d lambda + 4 mu) / (2 mu^2 (d lambda + 2 mu)^2) tt.
+    Floats or one value per cell; returns {"rho", "lambda", "mu"}, each of the correlations' shape.  The sign and the time
+    derivative are the caller's convention: by bilinearity the correlation with (b^{n+1} - b^n) / dt is two calls of
+    `correlate` with weights -1/dt and +1/dt."""
+    lam, mu = np.asarray(lam, dtype=np.float64), np.asarray(mu, dtype=np.float64)
+    uu, ss, tt = (np.asarray(corr[k], dtype=np.float64) for k in ("uu", "ss", "tt"))
+    k = dim * lam + 2.0 * mu
+    return {"rho": uu + 0.0 * np.asarray(density, dtype=np.float64),
+            "lambda": -tt / k ** 2,
+            "mu": -ss / (2.0 * mu ** 2) + lam * (dim * lam + 4.0 * mu) / (2.0 * mu ** 2 * k ** 2) * tt}
+
+
 def _device_for_rank():
     if "SEIGEN_HIP_DEVICE" in os.environ:
         return int(os.environ["SEIGEN_HIP_DEVICE"])
@@ -540,6 +557,21 @@ class ElasticLF4(object):
         every = self._monitor
         self._block.set_monitor(every, max(1, len(times) // every), self.energy_weights())
         self._monitor_times = list(times[every - 1::every])
+
+    # ---- correlation with another solver's fields, cell by cell (sg_correlate) ------------------------
+    def correlate(self, other, weights=(1.0, 1.0, 1.0)):
+        """Add weights * (uu, ss, tt) of this solver's (u1, s1) against `other`'s - an ElasticLF4 on the same mesh and
+        device, e.g. the forward field being re-wound beside the adjoint - to this block's per-cell accumulator.  The
+        caller drives the call between steps; the correlation with a time derivative is two calls with weights -+ 1/dt."""
+        self._block.correlate(other._block, weights)
+
+    def correlation(self):
+        """{"uu", "ss", "tt"}: [ncells] each, of this rank's block (nothing to reduce across ranks)."""
+        acc = self._block.get_correlation()
+        return {"uu": acc[:, 0].copy(), "ss": acc[:, 1].copy(), "tt": acc[:, 2].copy()}
+
+    def reset_correlation(self):
+        self._block.reset_correlation()
 
     # ---- time loop (elastic.py:267-315) ----------------------------------------------------------
     def step_times(self, T):

@@ -1,6 +1,6 @@
 // CPU sanitizer driver (SURVEY 5 "sanitizers"; `make -C seigen_amd/csrc host-asan`): everything of libseigen_hip that
 // needs no device - reference elements, mesh tables, MFMA fragment tables, the sponge, source and receiver plans, the items
-// of split-stage regions, the stage table, what stepping remembers between calls, the device-free C-ABI entry points - built with
+// of split-stage regions, the stage table, what stepping remembers between calls, the correlation's plan, the device-free C-ABI entry points - built with
 // -fsanitize=address,undefined and walked over every (dim, degree, cell type, diagonal) the library accepts, plus the
 // argument errors the entry points must refuse.  Exit code 0 and no sanitizer report = clean.
 #include <algorithm>
@@ -1149,7 +1149,116 @@ static void stepping_state() {
   }
 }
 
+// The correlation's plan (hostlogic.hpp xcorr_components, xcorr_mass_tiles, xcorr_first_difference) against a restatement
+// that shares no code with it: two tensors stored the way each handle's storage mode stores them, read through the component
+// table, must give sum_ij A_ij B_ij and the two traces; the A tiles, walked by (row, column), must be the mass matrix of
+// sg_reference_operator_cell and zero beyond it.
+static void correlation_plan(int cell_type, int dim, int degree) {
+  const int64_t nn = sg_reference_operator_cell(cell_type, dim, degree, 2, 0, nullptr, 0);
+  EXPECT(nn > 0);
+  if (nn <= 0) return;
+  std::vector<double> M((size_t)nn);
+  EXPECT(sg_reference_operator_cell(cell_type, dim, degree, 2, 0, M.data(), M.size() * sizeof(double)) == nn);
+  const int nd = num_nodes(dim, degree, cell_type);
+  EXPECT((int64_t)nd * nd == nn);
+  const std::vector<double> tiles = xcorr_mass_tiles(M, nd);
+  int rows = 0, cols = 0;
+  while (rows < nd) rows += 16;
+  while (cols < nd) cols += 4;
+  EXPECT(xcorr_row_tiles(nd) * 16 == rows && xcorr_k_steps(nd) * 4 == cols);
+  EXPECT(tiles.size() == (size_t)rows * cols);
+  if (tiles.size() == (size_t)rows * cols)
+    for (int r = 0; r < rows; ++r)
+      for (int c = 0; c < cols; ++c) {
+        // lane (r mod 16) + 16 (c mod 4) of tile (r / 16, c / 4): the A operand map of the 16 x 16 x 4 f64 instruction
+        const double v = tiles[((size_t)(r / 16) * (cols / 4) + c / 4) * 64 + (size_t)(c % 4) * 16 + r % 16];
+        EXPECT(v == ((r < nd && c < nd) ? M[(size_t)r * nd + c] : 0.0));
+      }
+  for (bool sym_a : {false, true})
+    for (bool sym_b : {false, true}) {
+      const std::vector<XcorrComp> cs = xcorr_components(dim, sym_a, sym_b);
+      EXPECT((int)cs.size() <= sg::xcorr::MAX_COMP);
+      // small integers: every sum below is exact
+      std::vector<double> A((size_t)dim * dim), B((size_t)dim * dim);
+      for (int i = 0; i < dim; ++i)
+        for (int j = 0; j < dim; ++j) {
+          A[(size_t)i * dim + j] = sym_a ? 1 + 3 * std::min(i, j) + 35 * std::max(i, j) : 1 + 3 * i + 7 * j;
+          B[(size_t)i * dim + j] = 2 + 11 * i * (sym_b ? j : 1) + (sym_b ? 13 * (i + j) : 5 * j);
+        }
+      // a line of the lower triangle holds nothing usable in symmetric storage
+      std::vector<double> SA = A, SB = B;
+      for (int i = 0; i < dim; ++i)
+        for (int j = 0; j < i; ++j) {
+          if (sym_a) SA[(size_t)i * dim + j] = 1e300;
+          if (sym_b) SB[(size_t)i * dim + j] = 1e300;
+        }
+      double want = 0, tra = 0, trb = 0;
+      for (int i = 0; i < dim; ++i) {
+        tra += A[(size_t)i * dim + i];
+        trb += B[(size_t)i * dim + i];
+        for (int j = 0; j < dim; ++j) want += A[(size_t)i * dim + j] * B[(size_t)i * dim + j];
+      }
+      double got = 0, gta = 0, gtb = 0, mults = 0;
+      int nvel = 0;
+      for (size_t k = 0; k < cs.size(); ++k) {
+        EXPECT(cs[k].stress == ((int)k >= dim));
+        if (!cs[k].stress) {
+          EXPECT(cs[k].comp_a == (int)k && cs[k].comp_b == (int)k && cs[k].mult == 1.0 && !cs[k].diag);
+          nvel += 1;
+          continue;
+        }
+        EXPECT(cs[k].comp_a >= 0 && cs[k].comp_a < dim * dim && cs[k].comp_b >= 0 && cs[k].comp_b < dim * dim);
+        got += cs[k].mult * SA[(size_t)cs[k].comp_a] * SB[(size_t)cs[k].comp_b];
+        mults += cs[k].mult;
+        if (cs[k].diag) {
+          gta += SA[(size_t)cs[k].comp_a];
+          gtb += SB[(size_t)cs[k].comp_b];
+        }
+      }
+      EXPECT(nvel == dim && mults == (double)(dim * dim));
+      EXPECT(got == want && gta == tra && gtb == trb);
+      EXPECT((int)cs.size() == dim + ((sym_a && sym_b) ? dim * (dim + 1) / 2 : dim * dim));
+    }
+}
+
+static void correlation_compatibility() {
+  sg_config a;
+  std::memset(&a, 0, sizeof(a));
+  a.dim = 3;
+  a.degree = 4;
+  for (int k = 0; k < 3; ++k) {
+    a.n[k] = 4 + k;
+    a.h[k] = 0.25;
+  }
+  EXPECT(xcorr_first_difference(a, 16, a, 16).empty());
+  sg_config b = a;
+  b.nbr_mask = 5;
+  b.origin[1] = 2.0;
+  b.cube0[2] = 7;
+  EXPECT(xcorr_first_difference(a, 16, b, 16).empty());
+  auto named = [&](const sg_config& x, int gw, const char* word) {
+    const std::string d = xcorr_first_difference(a, 16, x, gw);
+    EXPECT(d.find(word) != std::string::npos);
+    EXPECT(!xcorr_first_difference(x, gw, a, 16).empty());
+  };
+  b = a; b.device = 1; named(b, 16, "device");
+  b = a; b.dim = 2; named(b, 16, "dim");
+  b = a; b.degree = 3; named(b, 16, "degree");
+  b = a; b.diagonal = 1; named(b, 16, "diagonal");
+  b = a; b.dtype = 1; named(b, 16, "dtype");
+  b = a; b.n[1] = 9; named(b, 16, "n[1]");
+  b = a; b.h[2] = 0.5; named(b, 16, "h[2]");
+  named(a, 1, "layout");
+  // the first difference in the documented order
+  b = a; b.degree = 3; b.dtype = 1; named(b, 64, "degree");
+}
+
 int main() {
+  for (int cell_type : {0, 1})
+    for (int dim = 1; dim <= 3; ++dim)
+      for (int degree = 1; degree <= 4; ++degree)
+        if (!(cell_type == 1 && dim == 1)) correlation_plan(cell_type, dim, degree);
+  correlation_compatibility();
   for (int cell_type : {0, 1})
     for (int dim = 1; dim <= 3; ++dim)
       for (int degree = 1; degree <= 4; ++degree) {
