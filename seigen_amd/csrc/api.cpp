@@ -250,7 +250,7 @@ static int init_launch(sg_handle* h) {
   const int slots = blocks_per_cu(h) * prop.multiProcessorCount;
   h->grid_full = slots / 8 * 8;
   h->grid_blocks = (cfg->nbr_mask != 0 ? slots - slots / 16 : slots) / 8 * 8;
-  if (const char* gb = std::getenv("SEIGEN_HIP_GRID_BLOCKS")) h->grid_blocks = std::max(8, std::atoi(gb) / 8 * 8);
+  if (const char* gb = std::getenv("SEIGEN_HIP_GRID_BLOCKS")) h->grid_blocks = grid_blocks_override(std::atoi(gb));
   if (cfg->nbr_mask == 0) h->grid_full = h->grid_blocks;
   // F stages of a whole 3-D block: items dealt to the XCDs in chunks of 1/8 of a z-layer of cubes, so that all XCDs
   // sweep the block layer by layer together (the z-neighbour traces then meet the own rows of the next layer in the
@@ -507,6 +507,8 @@ int sg_set_absorption(sg_handle* h, const double* sigma_nodes, int sigma_degree)
       HIPCHECK(h, hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->cfg.device));
       sp.aff_grid = aff_mfma ? prepare_sponge_affine_mfma(h->cfg.degree, ncu) : prepare_sponge_pre_affine(d, h->f32, lds, ncu);
       if (sp.aff_grid <= 0) return fail(h, SG_ERR_DEVICE, "sg_set_absorption: the affine-sigma pre-pass cannot be set up on this device");
+      // SEIGEN_HIP_GRID_BLOCKS also caps this grid (hostlogic.hpp affine_grid_cap): tests make the pre-pass loop on small meshes
+      if (const char* gb = std::getenv("SEIGEN_HIP_GRID_BLOCKS")) sp.aff_grid = affine_grid_cap(sp.aff_grid, std::atoi(gb));
     }
     hipError_t e = hipSuccess;
     auto up = [&e](auto& buf, const auto& v) {

@@ -85,7 +85,7 @@ struct SpongeTables {
   DevBuf<double> aff_X;       // [dim][nd][W]
   DevBuf<int32_t> aff_col;    // [nd][W], empty where the rows are dense
   DevBuf<double> aff_frag;    // 3-D MFMA family in double: the X_k as row tiles (mfma_frags_dense)
-  int aff_grid = 0;           // persistent grid of the affine pre-pass (sponge_affine_mfma where aff_frag is set), on the handle's device
+  int aff_grid = 0;           // persistent grid of the affine pre-pass (sponge_affine_mfma where aff_frag is set), on the handle's device; capped by SEIGEN_HIP_GRID_BLOCKS
   PrePass pre_state;          // what `pre` holds and when it is due again (hostlogic.hpp); new tables start with none
 };
 

@@ -66,6 +66,14 @@ inline bool family_fused_source(Family f) { return f == Family::Tile2d; }
 // a region of whole cell groups runs as a whole-block launch: no cube coordinates, no box tests (StageArgs::all_active)
 inline bool family_whole_groups(Family f) { return f == Family::Mfma || f == Family::Hexm; }
 
+// SEIGEN_HIP_GRID_BLOCKS as a persistent grid: whole multiples of eight blocks (an item range belongs to an XCD label,
+// blockIdx % 8), never fewer than eight ...
+inline int grid_blocks_override(int value) { return value / 8 * 8 > 8 ? value / 8 * 8 : 8; }
+// ... and what it leaves of the grid prepared for the affine-sigma pre-pass of sg_set_absorption (SpongeTables::aff_grid,
+// either form): the switch only ever shrinks that grid, so that a block or wave of the pre-pass can be made to run item
+// after item on a small mesh.  The item split changes speed, never a result.
+inline int affine_grid_cap(int prepared, int value) { return prepared < grid_blocks_override(value) ? prepared : grid_blocks_override(value); }
+
 // One launch of a stage kernel as a value (stages.cpp run_op): F or G of a field and the fused epilogue around it
 // (kernels.hpp StageArgs::mode / c_self / c_aux / c_new).  The defaults are the un-fused application out = F(in; u) / G(in).
 struct StageOp {

@@ -96,14 +96,27 @@ def _row_id(r):
                                "" if len(r) < 5 or r[4] is None else "-gq" + r[4])
 
 
-def _environment(monkeypatch, path, gq):
-    """a row's switches, and nothing else that picks an instantiation or the sponge's form"""
+# the switches that pick the persistent grid, the item order and the launch form of the G stages at degree 4: unset in
+# every row here; tests/test_item_loop_gpu.py sets them
+LAUNCH_SWITCHES = ("SEIGEN_HIP_GRID_BLOCKS", "SEIGEN_HIP_ORDER_CHUNK", "SEIGEN_HIP_GSTASH")
+
+
+def _environment(monkeypatch, path, gq, launch=None):
+    """a row's switches, and nothing else that picks an instantiation or the sponge's form; launch: values for
+    LAUNCH_SWITCHES (None or missing: unset)"""
     for var in ("SEIGEN_HIP_SPONGE_AFFINE", "SEIGEN_HIP_SYM", "SEIGEN_HIP_GQ", "SEIGEN_HIP_PATH"):
         monkeypatch.delenv(var, raising=False)
     if path:
         monkeypatch.setenv("SEIGEN_HIP_PATH", path)
     if gq is not None:
         monkeypatch.setenv("SEIGEN_HIP_GQ", gq)
+    if launch is not None:
+        assert set(launch) <= set(LAUNCH_SWITCHES), launch
+        for var in LAUNCH_SWITCHES:
+            if launch.get(var) is None:
+                monkeypatch.delenv(var, raising=False)
+            else:
+                monkeypatch.setenv(var, launch[var])
 
 
 def _block(dtype, P, n, L):
@@ -119,7 +132,8 @@ def _stress(shape, rng, sym):
 def _sponge(m, rng):
     """DG4 nodal sigma: cells of all four kinds - none, one value (sigma u at the node), general nodal (a matrix of its
     own), affine in x with a gradient of its own (four coefficients: sponge_affine_mfma in double, sponge_pre_affine_kernel
-    in float) - in turn, so every 16-cube item holds all four"""
+    in float) - by cell % 4.  A cell is 6 cube + class, so the items (16 cubes of one class) of an odd class hold the
+    constant and the affine cells, those of an even class the cells with none and the cells with a matrix"""
     Xq = m.node_coords(4)
     kind = np.arange(m.ncells) % 4
     sigma = np.zeros(Xq.shape[:2])
@@ -151,16 +165,46 @@ def _tolerances(dtype, P):
     return (tol_of(P, "left"), 10 * tol_of(P, "left")) if dtype == "f64" else (2e-5, 5e-5)
 
 
-def _check_row(dtype, P, sym, n, gq, density):
+def _figure(what, e):
+    """the figure, printed before anything is asserted on it"""
+    print("ERR mfma %s %.3e" % (what, e))
+    return e
+
+
+class SharedOracle(object):
+    """The oracle of block n at degree P, built once and lent to several rows (_check_row's `oracle`): its operators, and
+    the sponge matrix of one _sponge sigma - at degree 4 the two take seconds, the steps of a row a second."""
+
+    def __init__(self, n, P, seed):
+        self.n, self.P = tuple(n), P
+        self.m = oracle_mesh(3, n, tuple(0.4 * k for k in n))
+        self.orc = OracleLF4(self.m, P)
+        self.sigma = _sponge(self.m, np.random.default_rng(seed))
+        self.sigma.setflags(write=False)
+        self.orc.E.set_absorption(self.sigma, 4)
+        self.absorb, self.orc.E.absorb = self.orc.E.absorb, None
+
+    def lend(self):
+        """as a fresh OracleLF4 has it: no sponge, no source, the explicit reference's density convention"""
+        orc = self.orc
+        orc.E.absorb, orc.source, orc.density, orc.density_physical = None, None, 1.0, False
+        return self.m, orc
+
+
+def _check_row(dtype, P, sym, n, gq, density, oracle=None):
     """one application of F and G, then three steps with every extra, against the oracle; returns the names the stages
-    reported"""
+    reported.  oracle: a SharedOracle of (n, P) to use instead of building one (its sigma is then the row's sponge)"""
     from seigen_amd import _lib
     L = tuple(0.4 * k for k in n)
     h = [L[a] / n[a] for a in range(3)]
     tol1, tol3 = _tolerances(dtype, P)
     rng = np.random.default_rng(1000 * P + 10 * n[0] + n[2] + (0 if dtype == "f64" else 7))
-    m = oracle_mesh(3, n, L)
-    orc = OracleLF4(m, P)
+    if oracle is None:
+        m = oracle_mesh(3, n, L)
+        orc = OracleLF4(m, P)
+    else:
+        assert (oracle.n, oracle.P) == (tuple(n), P)
+        m, orc = oracle.lend()
     nc = m.ncells
     lam, mu = rng.uniform(0.4, 0.8, nc), rng.uniform(0.2, 0.4, nc)
 
@@ -178,9 +222,9 @@ def _check_row(dtype, P, sym, n, gq, density):
 
     # one application of each operator (the MODE 0 kernels)
     blk.apply_F(_lib.FIELD_S, _lib.FIELD_U, _lib.FIELD_UH)
-    assert rel_err(blk.get_field(_lib.FIELD_UH), orc.E.apply_F(T, u)) < tol1
+    assert _figure("F", rel_err(blk.get_field(_lib.FIELD_UH), orc.E.apply_F(T, u))) < tol1
     blk.apply_G(_lib.FIELD_U, _lib.FIELD_SH)
-    assert rel_err(blk.get_field(_lib.FIELD_SH), orc.E.apply_G(u, lam, mu)) < tol1
+    assert _figure("G", rel_err(blk.get_field(_lib.FIELD_SH), orc.E.apply_G(u, lam, mu))) < tol1
     blk.close()
 
     # three whole steps
@@ -197,8 +241,11 @@ def _check_row(dtype, P, sym, n, gq, density):
         orc.density_physical = density == "physical"
         blk.set_params(1.0, orc.dt, lam, mu)
         blk.set_density(orc.density, physical=orc.density_physical)
-    sigma = _sponge(m, rng)
-    orc.E.set_absorption(sigma, 4)
+    if oracle is None:
+        sigma = _sponge(m, rng)
+        orc.E.set_absorption(sigma, 4)
+    else:
+        sigma, orc.E.absorb = oracle.sigma, oracle.absorb
     blk.set_absorption(sigma, 4)
     nodes = _source_nodes(n, nd, rng)
     vals = _stress((3, len(nodes), 3, 3), rng, sym)
@@ -211,11 +258,11 @@ def _check_row(dtype, P, sym, n, gq, density):
     for k in range(3):
         orc.source = lambda t, k=k: _oracle_source(nc, nd, nodes, vals[k])
         orc.step((k + 1) * orc.dt)
-    assert rel_err(blk.get_field(_lib.FIELD_U), orc.u1) < tol3
-    assert rel_err(blk.get_field(_lib.FIELD_S), orc.s1) < tol3
+    assert _figure("steps u", rel_err(blk.get_field(_lib.FIELD_U), orc.u1)) < tol3
+    assert _figure("steps s", rel_err(blk.get_field(_lib.FIELD_S), orc.s1)) < tol3
     # what the last step left behind: w = dt u1 + dt^3/24 utemp (UTEMP, MODE 2) and sh1 = G(u1) + S (SH1)
-    assert rel_err(blk.get_field(_lib.FIELD_UH), orc.dt * orc.u1 + orc.dt ** 3 / 24.0 * orc.last["utemp"]) < tol3
-    assert rel_err(blk.get_field(_lib.FIELD_SH), orc.last["sh1"]) < tol3
+    assert _figure("steps uh", rel_err(blk.get_field(_lib.FIELD_UH), orc.dt * orc.u1 + orc.dt ** 3 / 24.0 * orc.last["utemp"])) < tol3
+    assert _figure("steps sh", rel_err(blk.get_field(_lib.FIELD_SH), orc.last["sh1"])) < tol3
     assert rel_err(orc.u1, u_start) > 1e-4
     blk.close()
     return names

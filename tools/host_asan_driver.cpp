@@ -813,6 +813,22 @@ static void region_item_lists() {
   EXPECT(region_items({}, n1, Layout{16, 2, 1}, 4, 16).items.empty() && region_items({}, n1, Layout{16, 2, 1}, 4, 16).whole);
 }
 
+// SEIGEN_HIP_GRID_BLOCKS as a grid (hostlogic.hpp grid_blocks_override) and as the cap of the affine pre-pass's grid
+// (affine_grid_cap): min(prepared, max(8, value / 8 * 8)) - it shrinks, never enlarges
+static void grid_overrides() {
+  const int in[] = {-5, 0, 1, 7, 8, 9, 15, 16, 17, 255, 256, 480, 511, 512, 100000};
+  const int out[] = {8, 8, 8, 8, 8, 8, 8, 16, 16, 248, 256, 480, 504, 512, 100000};
+  for (size_t k = 0; k < sizeof(in) / sizeof(in[0]); ++k) {
+    EXPECT(grid_blocks_override(in[k]) == out[k]);
+    for (int prepared : {1, 7, 8, 9, 256, 512, 1024}) {
+      const int got = affine_grid_cap(prepared, in[k]);
+      EXPECT(got == std::min(prepared, std::max(8, in[k] / 8 * 8)));
+      EXPECT(got <= prepared && got >= std::min(prepared, 8));
+    }
+  }
+  EXPECT(affine_grid_cap(1024, 8) == 8 && affine_grid_cap(512, 8) == 8 && affine_grid_cap(4, 8) == 4 && affine_grid_cap(1024, 4096) == 1024);
+}
+
 // The six launches of an LF4 step (hostlogic.hpp lf4_stage) against the rows written out here, for two (dt, rho) and the
 // three density conventions of stage U1; every stage reads what the stage before it wrote, cyclically over the step.
 // The printed lines are what tests/test_host_logic.py compares with seigen_amd/parallel.py STAGE_INPUT / STAGE_OUTPUT.
@@ -1282,6 +1298,7 @@ int main() {
   regions_and_coords();
   point_location();
   kernel_family_table();
+  grid_overrides();
   stage_table();
   stepping_state();
   for (int dim = 1; dim <= 3; ++dim)
