@@ -6,7 +6,10 @@
   (seigen/elastic.py:291-304, :340-352) is reversible; undoing a step is the stress update run
   with -dt followed by the velocity update with -dt, so K steps forward and K steps backward must
   return the initial state to round-off.  Every launch of the step (plain and fused kernels,
-  interior and domain-boundary facets) takes part at the full size,
+  interior and domain-boundary facets) takes part at the full size.  Reversal holds for any deterministic F', G' with
+  G'(-w) = -G'(w): it sees non-determinism and stray writes, not a wrong linear operator - a stage that reads the wrong
+  neighbour, or the row 2^32 bytes below the right one, reverses exactly (tests/test_large_offsets_gpu.py compares the
+  kernels with the oracle at those offsets),
 * polynomial reproduction: g of a linear velocity field is the constant Hooke stress everywhere,
   domain boundary included (own-trace boundary flux, elastic.py:216).
 """
