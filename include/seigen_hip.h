@@ -227,7 +227,7 @@ int sg_set_source_box_ricker(sg_handle* h, const double* lo, const double* hi, d
 int sg_step(sg_handle* h, int64_t nsteps);
 /* one fused stage over a region (multi-block overlap and stage-level tests). */
 int sg_run_stage(sg_handle* h, int stage, int region);
-/* advance the source-amplitude index after a manually staged step */
+/* end a manually staged step: advance the source-amplitude index; receivers, monitor and injectors take their turn */
 int sg_end_step(sg_handle* h);
 
 /* ---- receivers (tests/explosive_source/uy.py:31-43: VelocityNew written to a VTU file at every step, three points
@@ -253,6 +253,45 @@ int sg_set_receivers(sg_handle* h, int64_t nrec, const double* pts, int what, in
  * does not own are 0.0; nbytes must be that of `capacity` samples; *nsamples = samples taken.  Replaces the host-side
  * probe of every 5th VTU file (uy.py:36-43, vtktools.vtu.ProbeData). */
 int sg_get_receivers(sg_handle* h, double* out, size_t nbytes, int64_t* nsamples);
+
+/* ---- injectors: force and stress series added at physical points inside the time loop - the driving side beside the
+ * receivers, what puts a point force into the velocity equation or a data residual into an adjoint field ----------------
+ * An injector is the transpose of a receiver.  Where the recorder forms sum_a phi_a(xi) field[cell][a][c], an injector adds
+ *   field[cell][a][c] += amp[c] * psi_a,   psi = Mhat^-1 phi(xi) / |det J|,
+ * the L2 projection of amp * delta(x - x_r) onto the element: sum_a psi_a (|det J| Mhat v)_a = v(x_r) for every v of the
+ * element's space.  Mhat is the cell type's own (simplex or tensor-product), |det J| the product of the cell sizes.
+ * what: bit 0 adds to the velocity SG_FIELD_U (dim values), bit 1 to the stress SG_FIELD_S (dim x dim, row-major); per point
+ * amp holds the velocity's values and then the stress's, ncomp = dim * bit0 + dim^2 * bit1 as for the receivers.
+ * The cell and xi of a point: sg_locate_points.  A block owns an injector when the chosen cube (in the mesh's indices) lies
+ * in it: under any partition every point inside the mesh has exactly one owner, a point outside none.  On a grid line the
+ * lower cell gets the whole delta - the transpose of the receiver reading the lower side.  Every block is handed all of the
+ * mesh's points [npts][dim] and keeps the ones it owns; owned[npts] out (0/1, may be NULL).
+ * Arithmetic: the host groups the owned points by cell; one thread per (cell with points, node a, component q) forms
+ * v = sum_r fma(amp[r][q], psi_r[a], v) from zero over that cell's points in the order listed, then field = field + v in
+ * double (FP32 blocks convert, add and round once).  No atomics: the bits depend only on the field contents, the amplitudes
+ * and the points - the same under graph replay and eager launches, for one sg_step(n) and n calls of sg_step(1), for
+ * host-driven stages with sg_end_step, with timing on or off, and on a split block.
+ * Symmetric-stress storage: a stress table that is symmetric to the bit (the owned points', every entry) writes the i <= j
+ * lines only; one that is not makes THIS block leave symmetric storage at the call, as a non-symmetric source does
+ * (sg_get_sym / sg_leave_sym: the blocks of a mesh must agree).
+ * The library adds exactly amp * psi: 1/rho, dt, or the 1/wk of an adjoint source in the energy inner product are the
+ * caller's, folded into amp.
+ * Series: entry k (k = 0 .. nsteps-1) is added at the END of step k+1 counted from the arming call - through sg_step (graph
+ * replay or eager, with or without a communicator) or through sg_end_step after host-driven stages - after the recorder and
+ * the monitor have sampled that step: a sample of step k+1 never contains entry k, which belongs to the step that follows.
+ * sg_inject supplies the entry "before step 1": a force f(t) is sg_inject(q_0), then the series q_1, q_2, ...  After nsteps
+ * entries nothing is added (no refusal, as with a source that has run out).  npts = 0 or nsteps = 0 disarms; re-arming
+ * replaces the series and restarts the count; a failed call leaves the previous injectors armed, their count intact.
+ * With a communicator a step that added a stress entry sends the traces of s1 again before the next step reads them; a host
+ * that drives stages and halo itself does the same after its sg_end_step.  Nothing armed: no extra launch, the same
+ * captured graphs. */
+/* device-free, like sg_locate_points: cell[k] (or -1) and psi[k][nd] = Mhat^-1 phi(xi_k) / |det J| (0 where -1); degree <= 4 */
+int sg_injector_weights(const sg_config* cfg, int64_t npts, const double* pts, int64_t* cell, double* psi);
+/* one shot, behind everything the handle has queued: field += amp[npts][ncomp] at the points */
+int sg_inject(sg_handle* h, int64_t npts, const double* pts, int what, const double* amp);
+/* a series: amp[nsteps][npts][ncomp] */
+int sg_set_injectors(sg_handle* h, int64_t npts, const double* pts, int what, int64_t nsteps, const double* amp,
+                     int32_t* owned);
 
 /* ---- monitor: L2 norms and elastic energy of the block, taken on the device (the global observer beside the point-wise
  * one; what a harness gets from norm(u) of the downloaded fields, or the oracle's energy test from 1/2 (rho |u|^2 +

@@ -37,6 +37,17 @@ def locate_points(cfg, points):
     return cell, xi
 
 
+def injector_weights(cfg, points, nd):
+    """(cell [npts], psi [npts, nd]) of the points [npts, dim] in the block `cfg` (an SgConfig) describes: the owning cell
+    as locate_points gives it and psi = Mhat^-1 phi(xi) / |det J|, what an injector of unit amplitude adds to that cell's
+    nodes (sg_injector_weights; device-free); nd: scalar nodes per cell."""
+    pts = _f64(points).reshape(-1, cfg.dim)
+    cell = np.empty(len(pts), dtype=np.int64)
+    psi = np.zeros((len(pts), int(nd)))
+    check(_lib.load().sg_injector_weights(C.byref(cfg), len(pts), pts.ctypes.data, cell.ctypes.data, psi.ctypes.data))
+    return cell, psi
+
+
 class HipBlock(object):
     def __init__(self, dim, degree, n, h, origin, diagonal="left", nbr_mask=0, device=0, stream=None, dtype="f64",
                  cube0=None):
@@ -72,6 +83,7 @@ class HipBlock(object):
         self.u_dofs, self.s_dofs = int(info.u_dofs), int(info.s_dofs)
         self.halo_faces = [int(x) for x in info.halo_faces]
         self.nbr_mask = int(nbr_mask)
+        self._inj = None                # (what, entries, the library's step count at the arming call) of set_injectors
 
     def stream_ptr(self):
         """hipStream_t (as an integer) the block launches on."""
@@ -211,7 +223,49 @@ class HipBlock(object):
         check(self.lib.sg_run_stage(self.h, int(stage), int(region)), self.h)
 
     def end_step(self):
+        """End a host-driven step.  Returns whether an armed stress series added an entry to s1: a host that exchanges the
+        halo itself sends the traces of s1 again before the next step (include/seigen_hip.h)."""
+        due = self._inj is not None and (self._inj[0] & 2) and self.injector_entries_left() > 0
         check(self.lib.sg_end_step(self.h), self.h)
+        return bool(due)
+
+    def injector_entries_left(self):
+        """Entries of the armed series not added yet: entry k goes in at the end of step k + 1 counted from the arming
+        call, and the steps are the library's own count (sg_get_counters: sg_step and sg_end_step alike)."""
+        if self._inj is None:
+            return 0
+        what, entries, at = self._inj
+        return max(0, entries - (self.counters()["steps"] - at))
+
+    # ---- injectors (sg_inject / sg_set_injectors) -------------------------------------------------
+    def _ncomp(self, what):
+        if int(what) not in (1, 2, 3):
+            raise ValueError("what is 1 (velocity), 2 (stress) or 3 (both)")
+        return (self.dim if what & 1 else 0) + (self.dim * self.dim if what & 2 else 0)
+
+    def inject(self, points, amp, what=1):
+        """field += amp at the physical `points` [npts, dim], once, behind everything queued: amp [npts, ncomp] holds per
+        point the velocity's dim values (what bit 0) and then the stress's dim * dim (bit 1).  Every block of a mesh is
+        handed all points and adds the ones it owns."""
+        pts = _f64(points).reshape(-1, self.dim)
+        amp = _f64(amp).reshape(len(pts), self._ncomp(what))
+        check(self.lib.sg_inject(self.h, len(pts), pts.ctypes.data, int(what), amp.ctypes.data), self.h)
+
+    def set_injectors(self, points, series, what=1):
+        """Arm a series at `points` [npts, dim]: series[k] [npts, ncomp] is added at the end of step k + 1 counted from
+        this call.  No points or no entries: disarm.  Returns owned [npts] (bool)."""
+        pts = _f64(points).reshape(-1, self.dim)
+        nsteps = 0 if series is None else len(series)
+        if len(pts) == 0 or nsteps == 0:
+            check(self.lib.sg_set_injectors(self.h, 0, None, 0, 0, None, None), self.h)
+            self._inj = None
+            return np.zeros(len(pts), dtype=bool)
+        amp = _f64(series).reshape(nsteps, len(pts), self._ncomp(what))
+        owned = np.zeros(len(pts), dtype=np.int32)
+        check(self.lib.sg_set_injectors(self.h, len(pts), pts.ctypes.data, int(what), nsteps, amp.ctypes.data,
+                                        owned.ctypes.data), self.h)
+        self._inj = (int(what), nsteps, self.counters()["steps"])
+        return owned.astype(bool)
 
     # ---- receivers (sg_set_receivers / sg_get_receivers) ----------------------------------------
     def set_receivers(self, points, what=1, every=1, capacity=0):

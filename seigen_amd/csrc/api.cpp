@@ -2,6 +2,7 @@
 // family choice), parameters, sponge, source and the table exports.  Field transfers: transfer.cpp; stage launches,
 // the fused six-launch LF4 step (seigen/elastic.py:283-313) and halo packs: stages.cpp.
 #include <limits>
+#include <stdexcept>
 #include <string>
 
 #include "handle.hpp"
@@ -695,6 +696,74 @@ int sg_get_receivers(sg_handle* h, double* out, size_t nbytes, int64_t* nsamples
       std::memcpy(out + (j * rt.nrec + rt.row[(size_t)r]) * rt.ncomp, t.data() + (j * rt.nown + r) * rt.ncomp,
                   (size_t)rt.ncomp * sizeof(double));
   *nsamples = n;
+  return SG_OK;
+}
+
+// The injectors: located, weighted and grouped by cell on the host (hostlogic.hpp injector_plan: locate_point, the rule of
+// sg_locate_points; psi from the element's Mhat^-1), uploaded into a local InjectTables.  Nothing of the handle changes here
+// but - last, once nothing else can fail - the storage mode, which a stress table that is not symmetric makes the block leave.
+static int build_injectors(sg_handle* h, const char* who, int64_t npts, const double* pts, int what, int64_t nsteps, const double* amp,
+                           InjectTables& it, std::vector<int32_t>& own) {
+  if (npts < 0 || nsteps < 0) return fail(h, SG_ERR_ARG, std::string(who) + ": npts and nsteps must be >= 0");
+  if (what < 1 || what > 3) return fail(h, SG_ERR_ARG, std::string(who) + ": what must be 1 (velocity), 2 (stress) or 3");
+  if (!pts || !amp) return fail(h, SG_ERR_ARG, std::string(who) + ": no points or no amplitudes");
+  NodeGeom G;
+  if (!G.init(&h->cfg, h->cfg.degree)) return fail(h, SG_ERR_ARG, std::string(who) + ": cell type");
+  InjectorPlan pl;
+  std::vector<double> table;
+  try {
+    pl = injector_plan(G, layout(h), h->re, npts, pts, what);
+    table = injector_gather(pl, npts, nsteps, amp);
+  } catch (const std::exception& e) {
+    return fail(h, SG_ERR_ARG, std::string(who) + ": " + e.what());
+  }
+  it.npts = npts;
+  it.nown = (int64_t)pl.row.size();
+  it.ngroups = (int64_t)pl.cell.size();
+  it.what = what;
+  it.ncomp = pl.ncomp;
+  it.clock.nsteps = nsteps;
+  const int64_t zero = 0;
+  HIPCHECK(h, it.item.upload(pl.item.data(), pl.item.size()));
+  HIPCHECK(h, it.lane.upload(pl.lane.data(), pl.lane.size()));
+  HIPCHECK(h, it.start.upload(pl.start.data(), pl.start.size()));
+  HIPCHECK(h, it.psi.upload(pl.psi.data(), pl.psi.size()));
+  HIPCHECK(h, it.amp.upload(table.data(), table.size()));
+  HIPCHECK(h, it.ctr.upload(&zero, 1));
+  own = std::move(pl.own);
+  if (h->sym && !injector_symmetric(pl, h->cfg.dim, what, nsteps, table))
+    if (int rc = leave_sym_mode(h)) return rc;
+  return SG_OK;
+}
+
+int sg_set_injectors(sg_handle* h, int64_t npts, const double* pts, int what, int64_t nsteps, const double* amp, int32_t* owned) {
+  if (!h) return SG_ERR_ARG;
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  InjectTables it;
+  std::vector<int32_t> own;
+  if (npts != 0 && nsteps != 0) {
+    if (int rc = build_injectors(h, "sg_set_injectors", npts, pts, what, nsteps, amp, it, own)) return rc;
+  } else if (npts < 0 || nsteps < 0) {
+    return fail(h, SG_ERR_ARG, "sg_set_injectors: npts and nsteps must be >= 0");
+  }
+  HIPCHECK(h, sync_all(h));
+  h->inj = std::move(it);
+  h->epoch += 1;
+  if (owned && !own.empty()) std::memcpy(owned, own.data(), own.size() * sizeof(int32_t));
+  return SG_OK;
+}
+
+int sg_inject(sg_handle* h, int64_t npts, const double* pts, int what, const double* amp) {
+  if (!h) return SG_ERR_ARG;
+  if (npts == 0) return SG_OK;
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  InjectTables it;
+  std::vector<int32_t> own;
+  if (int rc = build_injectors(h, "sg_inject", npts, pts, what, 1, amp, it, own)) return rc;
+  if (it.nown == 0) return SG_OK;
+  if (int rc = join_second(h)) return rc;
+  if (int rc = queue_inject(h, h->stream, it, nullptr, 1)) return rc;
+  HIPCHECK(h, hipStreamSynchronize(h->stream));   // the tables are this call's: they go when it returns
   return SG_OK;
 }
 

@@ -224,7 +224,14 @@ int comm_step(sg_handle* h, int64_t nsteps) {
           if (int rc = resolve_waits(h)) return rc;
       }
     }
+    // A stress entry of the injectors (sg_set_injectors), added at the end of the step, is younger than the traces of s1 that
+    // stage S1 sent: they travel again before the next step's first stage reads them.  Every block is handed the same points
+    // and series, so every rank decides alike, whoever owns the points.
+    const InjectTables& it = h->inj;
+    const bool stress_entry = it.npts > 0 && (it.what & 2) && it.clock.due_at(it.clock.steps + 1);
     if (int rc = sg_end_step(h)) return rc;
+    if (stress_entry && k + 1 < nsteps)
+      if (int rc = exchange(h, lf4_stage_input(0), nullptr)) return rc;
   }
   if (int rc = join_second(h)) return rc;
   return finish_step_call(h);

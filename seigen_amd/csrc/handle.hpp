@@ -1,11 +1,11 @@
 // The handle behind the C-ABI (include/seigen_hip.h) and what its translation units share:
-//   api.cpp      create / destroy, parameters, sponge, source, receivers, monitor, correlation: device checks, uploads, the move into the handle
+//   api.cpp      create / destroy, parameters, sponge, source, receivers, injectors, monitor, correlation: device checks, uploads, the move into the handle
 //   transfer.cpp host <-> device field transfers (layout conversion, pinned pipeline)
 //   stages.cpp   regions, stage launches, the LF4 step, graphs, halo packs, timing
 // and, without a device or a HIP header (the CPU sanitizer build, `make host-asan`):
-//   hostapi.cpp (hostlogic.hpp)  family choice, field layout, stage table, region boxes / items, point location, receiver plan;
+//   hostapi.cpp (hostlogic.hpp)  family choice, field layout, stage table, region boxes / items, point location, receiver and injector plans;
 //                                what stepping remembers between calls: field write counts, the sponge pre-pass's state,
-//                                the source's slice at a step, the receivers' clock
+//                                the source's slice at a step, the receivers' and the injectors' clocks
 //   sponge_tables.cpp            what sg_set_absorption derives from the nodal sigma
 //   source_tables.cpp            what the source setters derive from the caller's nodes and values
 #pragma once
@@ -120,6 +120,23 @@ struct ReceiverTables {
   // graph replay: the step index of the launches of a capture (RecvArgs::ctr), set by sg_step before it replays and
   // bumped by a one-thread launch after the recorder (the role of sg_handle::src_ctr_d for the receivers)
   DevBuf<int64_t> ctr;
+};
+
+// The injectors of sg_set_injectors (and, for the one launch, of sg_inject), on the device: the owned points grouped by cell
+// (hostlogic.hpp InjectorPlan), their psi, and the series that the kernel (kernels_inject.hip) adds at the end of the steps
+struct InjectTables {
+  int64_t npts = 0;           // points armed (0: none; every block of a mesh is handed all of them)
+  int64_t nown = 0;           // ... of which this block owns these
+  int64_t ngroups = 0;        // cells with points
+  DevBuf<int64_t> item;       // [ngroups] item and
+  DevBuf<int32_t> lane;       // [ngroups] lane of the cell in the layout of the fields (hostlogic.hpp Layout)
+  DevBuf<int64_t> start;      // [ngroups + 1] the group's rows
+  DevBuf<double> psi;         // [nown][nd]
+  DevBuf<double> amp;         // [nsteps][nown][ncomp]
+  int what = 0;               // bit 0: velocity (dim values), bit 1: stress (dim x dim, row-major)
+  int ncomp = 0;
+  InjectorClock clock;        // entries, steps completed since arming (hostlogic.hpp)
+  DevBuf<int64_t> ctr;        // graph replay: the step index of the launches of a capture (the role of ReceiverTables::ctr)
 };
 
 // The monitor of sg_set_monitor and the scratch of sg_measure (kernels_measure.hip), on the device
@@ -251,6 +268,8 @@ struct sg_handle {
   MonitorTables mon;
   MeasureScratch msr;
   bool graph_mon = false;     // the captured graphs contain the monitor's launches
+  InjectTables inj;
+  bool graph_inj = false;     // the captured graphs contain the injector launches
   CorrelationTables cor;
   // halo
   const double* ghost[4][6] = {};
@@ -343,6 +362,7 @@ inline void region_boxes(const sg_handle* h, int region, std::vector<Box>& out) 
 }
 int resolve_timing(sg_handle* h);
 int finish_step_call(sg_handle* h);   // stages.cpp: the end of sg_step and comm_step (ev1, synchronise, last_ms)
+int queue_inject(sg_handle* h, hipStream_t stream, const InjectTables& it, const int64_t* ctr, int64_t step);   // stages.cpp: one launch of the injector kernel
 int measure_prepare(sg_handle* h);    // api.cpp: the scratch of the monitor's samples (MeasureScratch), built once
 // comm.cpp
 int comm_step(sg_handle* h, int64_t nsteps);

@@ -1,6 +1,6 @@
 // The device-free part of the C-ABI (include/seigen_hip.h "device-free setup queries") and the host logic behind
 // sg_create that involves no device: kernel-family choice, regions of a split stage and their items, node coordinates,
-// point location and the receiver plan, the exports of the reference-element operators and mesh tables.  No HIP header,
+// point location, the receiver and the injector plan, the exports of the reference-element operators and mesh tables.  No HIP header,
 // no HIP call: this file, refelem.cpp, mesh_tables.cpp, mfma_tables.cpp, sponge_tables.cpp and source_tables.cpp are what
 // `make host-asan` builds with -fsanitize=address,undefined and runs on the CPU.
 #include <algorithm>
@@ -279,9 +279,98 @@ ReceiverPlan plan_receivers(const NodeGeom& G, const Layout& L, int kind, int64_
   return pl;
 }
 
+void injector_weights(const RefElem& re, int degree, double detj, const double* xi, double* psi) {
+  std::vector<double> phi((size_t)re.nd);
+  tabulate(re.dim, degree, 1, xi, phi.data(), re.kind);
+  for (int a = 0; a < re.nd; ++a) {
+    double v = 0.0;
+    for (int b = 0; b < re.nd; ++b) v = std::fma(re.Minv[(size_t)a * re.nd + b], phi[(size_t)b], v);
+    psi[a] = v / detj;
+  }
+}
+
+InjectorPlan injector_plan(const NodeGeom& G, const Layout& L, const RefElem& re, int64_t npts, const double* pts, int what) {
+  const int d = G.d;
+  InjectorPlan pl;
+  pl.own.assign((size_t)npts, 0);
+  pl.ncomp = ((what & 1) ? d : 0) + ((what & 2) ? d * d : 0);
+  double detj = 1.0;
+  for (int a = 0; a < d; ++a) detj *= G.cfg->h[a];
+  std::vector<int64_t> cell_of((size_t)npts, -1);
+  std::vector<double> xi((size_t)npts * 3, 0.0);
+  for (int64_t k = 0; k < npts; ++k) {
+    cell_of[(size_t)k] = locate_point(G, pts + k * d, &xi[(size_t)k * 3]);
+    if (cell_of[(size_t)k] < 0) continue;
+    pl.own[(size_t)k] = 1;
+    pl.row.push_back(k);
+  }
+  std::stable_sort(pl.row.begin(), pl.row.end(), [&](int64_t x, int64_t y) { return cell_of[(size_t)x] < cell_of[(size_t)y]; });
+  pl.psi.resize(pl.row.size() * (size_t)L.nd);
+  for (size_t r = 0; r < pl.row.size(); ++r) {
+    const int64_t k = pl.row[r], cell = cell_of[(size_t)k];
+    if (pl.cell.empty() || pl.cell.back() != cell) {
+      const int64_t cube = cell / L.ncls, cls = cell % L.ncls;
+      pl.cell.push_back(cell);
+      pl.item.push_back(L.item(cube, cls));
+      pl.lane.push_back((int32_t)L.lane(cube));
+      pl.start.push_back((int64_t)r);
+    }
+    injector_weights(re, G.degree, detj, &xi[(size_t)k * 3], &pl.psi[r * (size_t)L.nd]);
+  }
+  pl.start.push_back((int64_t)pl.row.size());
+  return pl;
+}
+
+std::vector<double> injector_gather(const InjectorPlan& pl, int64_t npts, int64_t nsteps, const double* amp) {
+  const size_t nown = pl.row.size(), nc = (size_t)pl.ncomp;
+  std::vector<double> out((size_t)nsteps * nown * nc);
+  for (int64_t k = 0; k < nsteps; ++k)
+    for (size_t r = 0; r < nown; ++r)
+      std::memcpy(&out[((size_t)k * nown + r) * nc], amp + ((size_t)k * (size_t)npts + (size_t)pl.row[r]) * nc, nc * sizeof(double));
+  return out;
+}
+
+bool injector_symmetric(const InjectorPlan& pl, int dim, int what, int64_t nsteps, const std::vector<double>& gathered) {
+  if (!(what & 2)) return true;
+  const size_t nown = pl.row.size(), nc = (size_t)pl.ncomp, off = (what & 1) ? (size_t)dim : 0;
+  for (size_t e = 0; e < (size_t)nsteps * nown; ++e)
+    for (int i = 0; i < dim; ++i)
+      for (int j = i + 1; j < dim; ++j)
+        if (std::memcmp(&gathered[e * nc + off + (size_t)(i * dim + j)], &gathered[e * nc + off + (size_t)(j * dim + i)], sizeof(double)) != 0)
+          return false;
+  return true;
+}
+
 extern "C" {
 
 int sg_abi_version(void) { return SG_ABI_VERSION; }
+
+int sg_injector_weights(const sg_config* cfg, int64_t npts, const double* pts, int64_t* cell, double* psi) {
+  if (!cfg || npts < 0 || (npts > 0 && (!pts || !cell || !psi))) return SG_ERR_ARG;
+  if (cfg->dim < 1 || cfg->dim > 3 || cfg->degree < 1 || cfg->degree > 4) return SG_ERR_ARG;
+  for (int a = 0; a < cfg->dim; ++a)
+    if (cfg->n[a] < 1 || !(cfg->h[a] > 0.0)) return SG_ERR_ARG;
+  NodeGeom G;
+  if (!G.init(cfg, cfg->degree)) return SG_ERR_ARG;
+  const int d = cfg->dim;
+  try {
+    const RefElem re = make_refelem(d, cfg->degree, cfg->diagonal == SG_DIAGONAL_QUAD ? KIND_TENSOR : KIND_SIMPLEX);
+    double detj = 1.0;
+    for (int a = 0; a < d; ++a) detj *= cfg->h[a];
+    for (int64_t k = 0; k < npts; ++k) {
+      double xi[3] = {0, 0, 0};
+      cell[k] = locate_point(G, pts + k * d, xi);
+      if (cell[k] >= 0)
+        injector_weights(re, cfg->degree, detj, xi, psi + k * re.nd);
+      else
+        for (int a = 0; a < re.nd; ++a) psi[k * re.nd + a] = 0.0;
+    }
+  } catch (const std::exception& e) {
+    g_create_err = e.what();
+    return SG_ERR_ARG;
+  }
+  return SG_OK;
+}
 
 int sg_locate_points(const sg_config* cfg, int64_t npts, const double* pts, int64_t* cell, double* xi) {
   if (!cfg || npts < 0 || (npts > 0 && (!pts || !cell || !xi))) return SG_ERR_ARG;

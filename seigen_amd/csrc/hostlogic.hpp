@@ -1,6 +1,6 @@
 // Host logic of libseigen_hip that needs no device and no HIP header: which kernel family runs a block, the layout of its
 // fields, the six stages of an LF4 step, the boxes and items of the regions of a split stage, node coordinates of a block,
-// point location and the receiver plan.  Defined in hostapi.cpp, which - with refelem.cpp, mesh_tables.cpp, mfma_tables.cpp,
+// point location, the receiver plan and the injector plan.  Defined in hostapi.cpp, which - with refelem.cpp, mesh_tables.cpp, mfma_tables.cpp,
 // sponge_tables.cpp and source_tables.cpp - also builds on its own for the CPU sanitizer target (`make host-asan`).
 #pragma once
 #include <cstdint>
@@ -340,3 +340,35 @@ struct ReceiverPlan {
   int ncomp = 0;               // what bit 0: velocity (dim values), bit 1: stress (dim x dim)
 };
 ReceiverPlan plan_receivers(const NodeGeom& G, const Layout& L, int kind, int64_t nrec, const double* pts, int what, int64_t capacity);
+
+// The injectors (seigen_hip.h sg_inject / sg_set_injectors): the transpose of the receivers.  Where the recorder forms
+// sum_a phi_a(xi) field[cell][a][c], an injector adds amp * psi_a to the same cell, psi = Mhat^-1 phi(xi) / |det J| - the L2
+// projection of amp * delta(x - x_r) onto the element.  psi_a = (sum_b Minv[a][b] phi_b) / |det J| over b ascending with fma
+// from zero, then one division; |det J| = the product of the cell sizes (mesh_tables.hpp: every cell of a block has it).
+void injector_weights(const sg::RefElem& re, int degree, double detj, const double* xi, double* psi);
+// What the injector calls derive from the points: of the npts points the ones this block owns (locate_point: the receivers'
+// rule), grouped by cell - the groups in ascending cell order, the points of a cell in the order given (a stable sort: the
+// order of the kernel's sum) - with the item and lane of each group's cell (Layout) and psi of each point.
+struct InjectorPlan {
+  std::vector<int32_t> own;     // [npts]
+  std::vector<int64_t> row;     // [nown] -> point index, group after group
+  std::vector<double> psi;      // [nown][nd], in the order of row
+  std::vector<int64_t> cell;    // [ngroups] block-local cell, ascending
+  std::vector<int64_t> item;    // [ngroups]
+  std::vector<int32_t> lane;    // [ngroups]
+  std::vector<int64_t> start;   // [ngroups + 1]: group g holds rows start[g] .. start[g + 1] - 1
+  int ncomp = 0;                // what bit 0: velocity (dim values), bit 1: stress (dim x dim)
+};
+InjectorPlan injector_plan(const NodeGeom& G, const Layout& L, const sg::RefElem& re, int64_t npts, const double* pts, int what);
+// The injectors' clock: entry k (k = 0 .. nsteps - 1) is added at the end of step k + 1 counted from the arming call; after
+// nsteps entries nothing is added.
+struct InjectorClock {
+  int64_t nsteps = 0;
+  int64_t steps = 0;   // completed since arming
+  bool due_at(int64_t s) const { return s >= 1 && s <= nsteps; }   // step s (1-based) has an entry
+  bool active() const { return steps < nsteps; }                    // ... and so has some later step
+};
+// amp[nsteps][npts][ncomp] of the caller -> [nsteps][nown][ncomp] in the order of the plan's rows; and whether the stress part
+// (the last dim * dim of a point's ncomp values, what bit 1) of every owned point is symmetric to the bit at every step
+std::vector<double> injector_gather(const InjectorPlan& pl, int64_t npts, int64_t nsteps, const double* amp);
+bool injector_symmetric(const InjectorPlan& pl, int dim, int what, int64_t nsteps, const std::vector<double>& gathered);

@@ -357,4 +357,27 @@ int prepare_xcorr(int nd, int gw, int ipw, int mfma, int f32, int ncu);
 // one launch on `stream`: the matrix-pipe form (mfma != 0; a.M = the A tiles) or the LDS-staged one (a.M = [nd][nd])
 int launch_xcorr(const xcorr::Args& a, int mfma, int f32, int grid, void* stream);
 
+// Point injectors (kernels_inject.hip; seigen_hip.h sg_inject / sg_set_injectors): at the end of step s (counted from the
+// arming call; s from *ctr + 1 under graph replay) with s <= nsteps, entry k = s - 1 of the series is added.  One thread per
+// (cell with points g, node a, component q): v = sum_r fma(amp[k][r][q], psi[r][a], v) from zero over the rows r = start[g] ..
+// start[g + 1] - 1 in that order, then field = field + v in double, rounded once (q < nu: the velocity, c = q; else the
+// stress, c = q - nu; in symmetric storage the i > j lines are left alone).  Field offsets as in every layout:
+// ((item * nd + a) * ncomp_field + c) * gw + lane.  A cell appears in one group only: no two threads share a word.
+namespace inject {
+struct Args {
+  const int64_t* ctr;      // graph replay: *ctr + 1 is the step that just ended; null: `step`
+  int64_t step;
+  int64_t nsteps;          // entries of the series (a step beyond them adds nothing)
+  const int64_t* item;     // [ngroups]
+  const int32_t* lane;     // [ngroups]
+  const int64_t* start;    // [ngroups + 1]
+  const double* psi;       // [nown][nd]
+  const double* amp;       // [nsteps][nown][ncomp]
+  int64_t ngroups, nown;
+  int32_t ncomp, nu;       // components per point, of which the first nu are the velocity's
+  int32_t dim, nd, gw, sym;
+};
+}  // namespace inject
+int launch_inject(void* u, void* s, const inject::Args& a, int f32, void* stream);
+
 }  // namespace sg

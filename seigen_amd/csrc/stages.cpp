@@ -11,6 +11,7 @@ struct LaunchCtx {
   bool capture_src = false;           // a capture: slice and weight of the source come from the device-side counter src_ctr_d ...
   bool capture_rec = false;           // ... and the recorder's step from rec.ctr
   bool capture_mon = false;           // ... and the monitor's from mon.ctr
+  bool capture_inj = false;           // ... and the injectors' from inj.ctr (a series that has run out: no launch)
 };
 
 // the source at the handle's step (hostlogic.hpp source_slice), with the device pointers of a capture's SrcStep
@@ -317,6 +318,34 @@ int finish_step_call(sg_handle* h) {
   return SG_OK;
 }
 
+// One launch of the injector kernel (kernels_inject.hip) on `stream`: entry step - 1 (by value, or *ctr) of `it`'s series.  The
+// fields are taken for writing: whatever remembers a field state (the sponge pre-pass of the F stages, hostlogic.hpp PrePass)
+// sees that the velocity has moved on - UTEMP's pre-pass of u1 is stale once an entry has been added to u1.
+int queue_inject(sg_handle* h, hipStream_t stream, const InjectTables& it, const int64_t* ctr, int64_t step) {
+  inject::Args a;
+  std::memset(&a, 0, sizeof(a));
+  a.ctr = ctr;
+  a.step = step;
+  a.nsteps = it.clock.nsteps;
+  a.item = it.item.get();
+  a.lane = it.lane.get();
+  a.start = it.start.get();
+  a.psi = it.psi.get();
+  a.amp = it.amp.get();
+  a.ngroups = it.ngroups;
+  a.nown = it.nown;
+  a.ncomp = it.ncomp;
+  a.nu = (it.what & 1) ? h->cfg.dim : 0;
+  a.dim = h->cfg.dim;
+  a.nd = h->re.nd;
+  a.gw = (int32_t)h->md.gw;
+  a.sym = h->sym ? 1 : 0;
+  void* u = (it.what & 1) ? (void*)h->field.write(SG_FIELD_U) : nullptr;
+  void* s = (it.what & 2) ? (void*)h->field.write(SG_FIELD_S) : nullptr;
+  if (launch_inject(u, s, a, h->f32, stream) != 0) return fail(h, SG_ERR_DEVICE, "injector launch failed");
+  return SG_OK;
+}
+
 // Per-launch timing (sg_enable_timing): an event pair around a stage launch or a halo pack on stream s, resolved lazily by
 // resolve_timing (8192 pending pairs at once, on the main stream); id as in sg_handle::ev_stage_ids.
 static int timing_begin(sg_handle* h, hipStream_t s, size_t& k) {
@@ -476,13 +505,35 @@ static int monitor_step(sg_handle* h, const LaunchCtx& ctx) {
   return SG_OK;
 }
 
-// what ends a step on the stream: the receivers' recorder, then the monitor.  Either's refusal (no room for the sample) is
-// found before anything is queued or counted; a launch error of the second leaves the first one's step counted
+// The end of a step for the injectors (sg_set_injectors), behind the recorder and the monitor, which have sampled the step:
+// entry `steps` of the series is added to u1 / s1 and belongs to the step that follows.  Eager launches name the step by value,
+// count it here and launch nothing once the series has run out; the launches of a capture read the step from inj.ctr and bump
+// that (a step beyond the series: the threads exit at once), and a capture counts nothing.
+static int inject_step(sg_handle* h, const LaunchCtx& ctx) {
+  InjectTables& it = h->inj;
+  if (it.npts == 0) return SG_OK;
+  const int64_t step = it.clock.steps + 1;
+  // (a capture counts nothing, so active() holds for all of its steps: the graphs have the launches or have none, ensure_graphs)
+  const bool launch = ctx.capture_inj ? it.clock.active() : it.clock.due_at(step);
+  if (it.nown > 0 && launch) {
+    if (int rc = join_second(h)) return rc;
+    if (int rc = queue_inject(h, ctx.stream, it, ctx.capture_inj ? it.ctr.get() : nullptr, step)) return rc;
+    if (ctx.capture_inj && launch_step_counter(it.ctr.get(), 1, 1, ctx.stream) != 0)
+      return fail(h, SG_ERR_DEVICE, "step counter launch failed");
+  }
+  if (!ctx.capture_inj) it.clock.steps = step;
+  return SG_OK;
+}
+
+// what ends a step on the stream: the receivers' recorder, then the monitor, then the injectors.  A refusal of the first two
+// (no room for the sample) is found before anything is queued or counted; a launch error of a later one leaves the earlier
+// ones' step counted
 static int end_of_step(sg_handle* h, const LaunchCtx& ctx) {
   if (monitor_no_room(h, ctx))
     return fail(h, SG_ERR_STATE, "monitor trace full: read it out (sg_get_monitor) and re-arm before stepping on");
   if (int rc = record_step(h, ctx)) return rc;
-  return monitor_step(h, ctx);
+  if (int rc = monitor_step(h, ctx)) return rc;
+  return inject_step(h, ctx);
 }
 
 // The bookkeeping of n finished steps.  Eager stage launches and record_step have counted themselves; replayed steps
@@ -494,6 +545,7 @@ static void steps_done(sg_handle* h, int64_t n, bool replayed) {
   for (int st = 0; st < 6; ++st) h->counters.launches[st] += n;
   if (h->rec.nrec > 0) h->rec.clock.steps += n;
   if (h->mon.armed) h->mon.clock.steps += n;
+  if (h->inj.npts > 0) h->inj.clock.steps += n;
   h->field.replayed();
   h->sponge.pre_state.forget();
 }
@@ -538,7 +590,7 @@ static hipGraphExec_t capture_steps(sg_handle* h, int steps, bool with_src) {
   }
   if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return nullptr;
   int rc = SG_OK;
-  const LaunchCtx ctx{h->stream, with_src, h->rec.nrec > 0, h->mon.armed};
+  const LaunchCtx ctx{h->stream, with_src, h->rec.nrec > 0, h->mon.armed, h->inj.npts > 0};
   h->sponge.pre_state.forget();      // a replay starts from whatever the buffer holds: the captured step computes its own
   for (int k = 0; k < steps && rc == SG_OK; ++k) rc = enqueue_step(h, ctx, false);
   h->sponge.pre_state.forget();      // nothing was launched: the buffer does not hold what the capture asked for
@@ -571,8 +623,10 @@ static int check_monitor_room(sg_handle* h, int64_t nsteps) {
 // a device-side counter (kernels.hpp SrcStep); one that has run out, or none: no source launches.  Armed receivers likewise.
 static int ensure_graphs(sg_handle* h) {
   const bool with_src = source_at(h, false).active, with_rec = h->rec.nrec > 0, with_mon = h->mon.armed;
+  const bool with_inj = h->inj.npts > 0 && h->inj.clock.active();   // a series that has run out: no injector launches
   if (with_src && !h->src_ctr_d.get()) return fail(h, SG_ERR_STATE, "source without a device-side step counter");
-  if (h->graph_epoch == h->epoch && h->graph_src == with_src && h->graph_rec == with_rec && h->graph_mon == with_mon)
+  if (h->graph_epoch == h->epoch && h->graph_src == with_src && h->graph_rec == with_rec && h->graph_mon == with_mon &&
+      h->graph_inj == with_inj)
     return SG_OK;
   if (h->graph1) (void)hipGraphExecDestroy(h->graph1);
   if (h->graph8) (void)hipGraphExecDestroy(h->graph8);
@@ -582,6 +636,7 @@ static int ensure_graphs(sg_handle* h) {
   h->graph_src = with_src;
   h->graph_rec = with_rec;
   h->graph_mon = with_mon;
+  h->graph_inj = with_inj;
   if (!h->graph1 || !h->graph8) h->graph_ok = false;  // same kernels, launched one by one (eager_steps)
   return SG_OK;
 }
@@ -594,6 +649,8 @@ static int replay_steps(sg_handle* h, int64_t nsteps) {
   if (h->rec.nown > 0 && launch_step_counter(h->rec.ctr.get(), h->rec.clock.steps, 0, h->stream) != 0)
     return fail(h, SG_ERR_DEVICE, "step counter launch failed");
   if (h->mon.armed && launch_step_counter(h->mon.ctr.get(), h->mon.clock.steps, 0, h->stream) != 0)
+    return fail(h, SG_ERR_DEVICE, "step counter launch failed");
+  if (h->graph_inj && h->inj.nown > 0 && launch_step_counter(h->inj.ctr.get(), h->inj.clock.steps, 0, h->stream) != 0)
     return fail(h, SG_ERR_DEVICE, "step counter launch failed");
   int64_t k = 0;
   for (; k + 8 <= nsteps; k += 8) HIPCHECK(h, hipGraphLaunch(h->graph8, h->stream));

@@ -168,6 +168,9 @@ class ElasticLF4(object):
             self._receiver_times = []
             self._monitor = None            # `every` of set_monitor
             self._monitor_times = []
+            self._injected = []             # what inject / set_injectors have added, for rewind (see _position)
+            self._armed = None              # the armed series' entries still to be logged
+            self._rewound = 0               # steps re-wound so far
 
         if self.output:
             with timed_region('i/o'):
@@ -266,10 +269,7 @@ class ElasticLF4(object):
                     raise ValueError("ElasticLF4.%s must be set before run()" % name)
             # density, l, mu: floats as in the reference's tests, or one value per cell of this
             # rank's block (build-defined heterogeneous extension)
-            rho = np.atleast_1d(np.asarray(self.density, dtype=np.float64)).ravel()
-            self._block.set_params(float(rho[0]), self.dt, self.l, self.mu)
-            if rho.size > 1 or self.density_physical:
-                self._block.set_density(rho if rho.size > 1 else float(rho[0]), self.density_physical)
+            self._upload_params(self.dt)
             if self.absorption_function is not None:
                 self._block.set_absorption(self.absorption_function.dat.data_cells,
                                            self.absorption_function.function_space().degree)
@@ -308,6 +308,12 @@ class ElasticLF4(object):
                         self._exchanger = ex
                 if not native:  # driven from here stage by stage (gloo / host-staged transports, the plain schedule)
                     self._exchanger = HaloExchanger(self._block, self.mesh.partition, dev, stream=self._torch_stream)
+
+    def _upload_params(self, dt):
+        rho = np.atleast_1d(np.asarray(self.density, dtype=np.float64)).ravel()
+        self._block.set_params(float(rho[0]), dt, self.l, self.mu)
+        if rho.size > 1 or self.density_physical:
+            self._block.set_density(rho if rho.size > 1 else float(rho[0]), self.density_physical)
 
     @property
     def loop_context(self):
@@ -517,6 +523,104 @@ class ElasticLF4(object):
         pts, every, what = self._receivers
         self._block.set_receivers(pts, what, every, len(times) // every)
         self._receiver_times = list(times[every - 1::every])
+
+    # ---- injectors: force and stress series at points (sg_inject / sg_set_injectors) -----------------
+    _INJECT_WHAT = {"velocity": 1, "stress": 2}
+
+    def _injector_args(self, points, amp, what, lead):
+        if what not in self._INJECT_WHAT:
+            raise ValueError("injectors add to 'velocity' or to 'stress', not %r" % (what,))
+        d = self.dimension
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, d)
+        amp = np.ascontiguousarray(amp, dtype=np.float64)
+        amp = amp.reshape(lead + (len(pts), d if what == "velocity" else d * d))
+        from .backend import locate_points
+        from .functionspace import block_config
+        cell, _ = locate_points(block_config(self.mesh, self.degree), pts)
+        owners = allreduce_sum_array((cell >= 0).astype(np.float64))
+        for k in range(len(pts)):
+            if owners[k] != 1:
+                raise ValueError("injector %d at %r has %d owning blocks, not one (outside the mesh?)"
+                                 % (k, tuple(pts[k]), int(owners[k])))
+        return pts, amp, self._INJECT_WHAT[what]
+
+    # What was injected through this object, so that `rewind` can take it out again: (position, points, amp, what) of every
+    # entry added, the position being the number of forward steps the fields have behind them - the library's own step
+    # count (sg_get_counters, so el.block.step() counts too) less the steps re-wound.
+    def _position(self):
+        return self._block.counters()["steps"] - self._rewound
+
+    def _log_armed_series(self):
+        """move the entries that the armed series has added so far into the log"""
+        if self._armed is None:
+            return
+        at, pts, amp, w = self._armed
+        added = len(amp) - self._block.injector_entries_left()
+        self._injected += [(at + k + 1, pts, amp[k], w) for k in range(added)]
+        self._armed = (at + added, pts, amp[added:], w) if added < len(amp) else None
+
+    def inject(self, points, amp, what="velocity"):
+        """Add amp[r] * delta(x - points[r]), L2-projected onto the cell that holds the point, to the velocity (amp [R, dim])
+        or the stress (amp [R, dim, dim]) as they stand now (sg_inject).  The library adds exactly amp * psi: 1/rho and dt of
+        a force are the caller's.  Collective with more than one rank: every block is handed all points."""
+        pts, amp, w = self._injector_args(points, amp, what, ())
+        self._block.inject(pts, amp, w)
+        self._injected.append((self._position(), pts, amp.copy(), w))
+        self._agree_on_stress_storage()
+
+    def set_injectors(self, points, series, what="velocity"):
+        """A series at `points` [R, dim]: series[k] ([R, dim] or [R, dim, dim]) is the entry BEFORE step k + 1 counted from
+        this call, k = 0 .. K - 1 - series[0] is added now (sg_inject), series[k] at the end of step k on the device inside
+        the time loop (sg_set_injectors), behind that step's receiver and monitor samples.  An empty series disarms."""
+        K = 0 if series is None else len(series)
+        self._log_armed_series()
+        if K == 0:
+            self._block.set_injectors(np.zeros((0, self.dimension)), None)
+            self._armed = None
+            return
+        pts, amp, w = self._injector_args(points, series, what, (K,))
+        self._block.inject(pts, amp[0], w)
+        self._injected.append((self._position(), pts, amp[0].copy(), w))
+        self._block.set_injectors(pts, amp[1:], w)
+        self._armed = (self._position(), pts, amp[1:].copy(), w) if K > 1 else None
+        self._agree_on_stress_storage()
+
+    def rewind(self, nsteps):
+        """Undo `nsteps` steps exactly (to round-off): the INVERSE of a step is the stages in the order (SH1, UTEMP, S1, UH1,
+        STEMP, U1) with dt negated - the stress update undone first, then the velocity update.  (Stepping on with -dt in the
+        normal order is something else: the adjoint of a step in the energy inner product, what an adjoint field is stepped
+        with; it re-winds only up to O(dt).)  What `inject` and `set_injectors` of this object added is taken out again
+        before the step it followed is undone: a forced run x_k = A x_{k-1} + q_k psi re-winds as A^-1 (x_k - q_k psi), so
+        after rewind(n) the fields are those the run held n steps earlier, the entry of that moment included.  A re-wound
+        step is no step of the run: it ends without sg_end_step, so receivers and the monitor take no sample, their traces
+        stay as the run left them, and the library's step count does not move.  Host-driven, single blocks only; ValueError
+        with a source or a sponge (the inverse does not exist) or while a series still has entries to add."""
+        if self.mesh.partition.world > 1:
+            raise ValueError("rewind drives a single block")
+        if self.source:
+            raise ValueError("rewind with a source: the source's steps cannot be run backwards")
+        if self.absorption_function is not None:
+            raise ValueError("rewind with a sponge: an absorbed field cannot be recovered")
+        self._log_armed_series()
+        if self._armed is not None:
+            raise ValueError("rewind with injectors armed: the series has %d entries left (set_injectors(points, None) disarms)"
+                             % len(self._armed[2]))
+        for name in ("density", "dt", "mu", "l"):
+            if getattr(self, name) is None:
+                raise ValueError("ElasticLF4.%s must be set before rewind()" % name)
+        self._upload_params(-self.dt)
+        try:
+            for _ in range(int(nsteps)):
+                here = self._position()
+                for at, pts, amp, w in reversed([e for e in self._injected if e[0] >= here]):
+                    self._block.inject(pts, -amp, w)
+                self._injected = [e for e in self._injected if e[0] < here]
+                for stage in (_lib.STAGE_SH1, _lib.STAGE_UTEMP, _lib.STAGE_S1, _lib.STAGE_UH1, _lib.STAGE_STEMP, _lib.STAGE_U1):
+                    self._block.run_stage(stage)
+                self._rewound += 1
+                self._step_index -= 1
+        finally:
+            self._upload_params(self.dt)
 
     # ---- monitor: L2 norms and elastic energy inside the time loop (sg_set_monitor) -----------------
     def energy_weights(self):

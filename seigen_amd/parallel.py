@@ -350,7 +350,9 @@ class HaloExchanger(object):
                 reqs = self.start(STAGE_OUTPUT[stage])
                 self.block.run_stage(stage, _lib.REGION_SECOND)
                 self.finish(reqs)
-            self.block.end_step()
+            if self.block.end_step():
+                # (HipBlock.end_step) an injector added a stress entry behind the traces of s1 that stage S1 sent: they travel again
+                self.finish(self.start(STAGE_INPUT[0]))
 
     def step_unpipelined(self, nsteps=1):
         """The plain schedule: per stage exchange the input's traces || interior, then the shell."""

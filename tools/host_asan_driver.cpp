@@ -1,5 +1,5 @@
 // CPU sanitizer driver (SURVEY 5 "sanitizers"; `make -C seigen_amd/csrc host-asan`): everything of libseigen_hip that
-// needs no device - reference elements, mesh tables, MFMA fragment tables, the sponge, source and receiver plans, the items
+// needs no device - reference elements, mesh tables, MFMA fragment tables, the sponge, source, receiver and injector plans, the items
 // of split-stage regions, the stage table, what stepping remembers between calls, the correlation's plan, the device-free C-ABI entry points - built with
 // -fsanitize=address,undefined and walked over every (dim, degree, cell type, diagonal) the library accepts, plus the
 // argument errors the entry points must refuse.  Exit code 0 and no sanitizer report = clean.
@@ -765,6 +765,133 @@ static void receiver_plans(int dim, int diagonal, int degree) {
   for (int64_t k = 0; k < np; ++k) EXPECT(owners[(size_t)k] == (cell1[(size_t)k] >= 0 ? 1 : 0));
 }
 
+// The injectors' host half (hostapi.cpp injector_plan, injector_gather, injector_symmetric; hostlogic.hpp InjectorClock) on
+// the split of receiver_plans(), every point listed twice more so that cells hold several points in interleaved order: the
+// owners are locate_point's, the groups are the cells in ascending order, a cell's rows keep the order given (the order of
+// the kernel's sum), item and lane are the cell's in every layout, psi is sg_injector_weights' and has the delta property
+static void injector_plans(int dim, int diagonal, int degree) {
+  const int kind = diagonal == SG_DIAGONAL_QUAD ? KIND_TENSOR : KIND_SIMPLEX, nd = num_nodes(dim, degree, kind), ncls = classes_of(dim, kind);
+  const RefElem re = make_refelem(dim, degree, kind);
+  sg_config whole;
+  std::memset(&whole, 0, sizeof(whole));
+  whole.dim = dim;
+  whole.degree = degree;
+  whole.diagonal = diagonal;
+  for (int a = 0; a < 3; ++a) {
+    whole.n[a] = a < dim ? 4 : 1;
+    whole.h[a] = a < dim ? 0.25 * (a + 1) : 1.0;
+  }
+  std::vector<double> once, pts;
+  const double fr[] = {0.0, 0.5, 0.3};
+  for (int cz = (dim > 2 ? -1 : 0); cz <= (dim > 2 ? 4 : 0); ++cz)
+    for (int cy = (dim > 1 ? -1 : 0); cy <= (dim > 1 ? 4 : 0); ++cy)
+      for (int cx = -1; cx <= 4; ++cx)
+        for (int f = 0; f < 3; ++f) {
+          const int c[3] = {cx, cy, cz};
+          for (int a = 0; a < dim; ++a) once.push_back((c[a] + (a == 1 ? 1.0 - fr[f] : fr[f])) * whole.h[a]);
+        }
+  // descending, ascending, descending: the same point comes back far from its first listing
+  const int64_t n1 = (int64_t)once.size() / dim;
+  for (int rep = 0; rep < 3; ++rep)
+    for (int64_t k = 0; k < n1; ++k) {
+      const int64_t src = rep == 1 ? k : n1 - 1 - k;
+      for (int a = 0; a < dim; ++a) pts.push_back(once[(size_t)src * dim + a]);
+    }
+  const int64_t np = 3 * n1;
+  double detj = 1.0;
+  for (int a = 0; a < dim; ++a) detj *= whole.h[a];
+  std::vector<double> Mone((size_t)nd, 0.0);     // |det J| Mhat 1: the functional of v = 1
+  for (int a = 0; a < nd; ++a)
+    for (int b = 0; b < nd; ++b) Mone[(size_t)a] += detj * re.Mhat[(size_t)a * nd + b];
+  std::vector<int64_t> cell(np), wcell(np);
+  std::vector<double> xi(pts.size()), wpsi((size_t)np * nd), bpsi((size_t)np * nd);
+  EXPECT(sg_injector_weights(&whole, np, pts.data(), wcell.data(), wpsi.data()) == SG_OK);
+  std::vector<int> owners(np, 0);
+  for (int b = 0; b < (1 << dim); ++b) {
+    sg_config blk = whole;
+    for (int a = 0; a < dim; ++a) {
+      const int hi = (b >> a) & 1;
+      blk.n[a] = 2;
+      blk.cube0[a] = 2 * hi;
+      blk.nbr_mask |= 1 << (2 * a + (1 - hi));
+    }
+    NodeGeom G;
+    EXPECT(G.init(&blk, degree));
+    EXPECT(sg_locate_points(&blk, np, pts.data(), cell.data(), xi.data()) == SG_OK);
+    std::vector<int64_t> icell(np);
+    EXPECT(sg_injector_weights(&blk, np, pts.data(), icell.data(), bpsi.data()) == SG_OK);
+    EXPECT(icell == cell);
+    const int64_t ncube = 1 << dim;
+    for (int gw : {1, 16, 64})
+      for (int what = 1; what <= 3; ++what) {
+        const NaiveLayout NL(gw, ncls, nd, 1, ncube);
+        const InjectorPlan pl = injector_plan(G, Layout{gw, ncls, nd}, re, np, pts.data(), what);
+        EXPECT(pl.ncomp == (what == 1 ? dim : (what == 2 ? dim * dim : dim + dim * dim)));
+        const size_t ng = pl.cell.size();
+        EXPECT((int64_t)pl.own.size() == np && pl.item.size() == ng && pl.lane.size() == ng && pl.start.size() == ng + 1 &&
+               pl.psi.size() == pl.row.size() * nd);
+        if ((int64_t)pl.own.size() != np || pl.start.size() != ng + 1 || pl.psi.size() != pl.row.size() * nd) continue;
+        int64_t nown = 0;
+        for (int64_t k = 0; k < np; ++k) {
+          EXPECT((pl.own[(size_t)k] != 0) == (cell[(size_t)k] >= 0));
+          nown += cell[(size_t)k] >= 0 ? 1 : 0;
+          if (gw == 1 && what == 1 && cell[(size_t)k] >= 0) owners[(size_t)k] += 1;
+        }
+        EXPECT((int64_t)pl.row.size() == nown && pl.start.front() == 0 && pl.start.back() == nown);
+        for (size_t g = 0; g < ng; ++g) {
+          EXPECT(g == 0 || pl.cell[g - 1] < pl.cell[g]);
+          EXPECT(pl.start[g] < pl.start[g + 1]);
+          EXPECT(pl.item[g] == NL.item[(size_t)pl.cell[g]] && pl.lane[g] == NL.lane[(size_t)pl.cell[g]]);
+          for (int64_t r = pl.start[g]; r < pl.start[g + 1] && r < nown; ++r) {
+            const int64_t k = pl.row[(size_t)r];
+            EXPECT(k >= 0 && k < np && cell[(size_t)k] == pl.cell[g]);
+            EXPECT(r == pl.start[g] || pl.row[(size_t)r - 1] < k);      // stable: the order given
+            if (k < 0 || k >= np) continue;
+            double one = 0.0;
+            for (int a = 0; a < nd; ++a) {
+              EXPECT(pl.psi[(size_t)r * nd + a] == bpsi[(size_t)k * nd + a] && bpsi[(size_t)k * nd + a] == wpsi[(size_t)k * nd + a]);
+              one += pl.psi[(size_t)r * nd + a] * Mone[(size_t)a];
+            }
+            EXPECT(std::fabs(one - 1.0) < 1e-10);
+          }
+        }
+        // the caller's table in the order of the rows; symmetric only where every owned stress entry is, to the bit
+        const int64_t nsteps = 2;
+        std::vector<double> amp((size_t)(nsteps * np * pl.ncomp));
+        for (size_t i = 0; i < amp.size(); ++i) amp[i] = 1.0 + (double)i;
+        const int off = (what & 1) ? dim : 0;
+        if (what & 2)
+          for (int64_t e = 0; e < nsteps * np; ++e)
+            for (int i = 0; i < dim; ++i)
+              for (int j = 0; j < i; ++j) amp[(size_t)(e * pl.ncomp + off + i * dim + j)] = amp[(size_t)(e * pl.ncomp + off + j * dim + i)];
+        std::vector<double> t = injector_gather(pl, np, nsteps, amp.data());
+        EXPECT(t.size() == (size_t)(nsteps * nown * pl.ncomp));
+        for (int64_t s2 = 0; s2 < nsteps; ++s2)
+          for (int64_t r = 0; r < nown; ++r)
+            for (int q = 0; q < pl.ncomp; ++q)
+              EXPECT(t[(size_t)((s2 * nown + r) * pl.ncomp + q)] == amp[(size_t)((s2 * np + pl.row[(size_t)r]) * pl.ncomp + q)]);
+        EXPECT(injector_symmetric(pl, dim, what, nsteps, t));
+        if ((what & 2) && dim > 1 && nown > 0) {
+          t[(size_t)((nsteps * nown - 1) * pl.ncomp + off + 1)] += 1.0;      // entry (0, 1) of the last owned point, last step
+          EXPECT(!injector_symmetric(pl, dim, what, nsteps, t));
+        }
+      }
+    const double far[3] = {-5.0, -5.0, -5.0};
+    const InjectorPlan none = injector_plan(G, Layout{16, ncls, nd}, re, 1, far, 3);
+    EXPECT(none.row.empty() && none.cell.empty() && none.start.size() == 1 && none.own.size() == 1 && none.own[0] == 0);
+    EXPECT(injector_plan(G, Layout{16, ncls, nd}, re, 0, nullptr, 3).own.empty());
+  }
+  for (int64_t k = 0; k < np; ++k) EXPECT(owners[(size_t)k] == (wcell[(size_t)k] >= 0 ? 1 : 0));
+  // the clock: entry k at the end of step k + 1, nothing after nsteps
+  InjectorClock c;
+  c.nsteps = 3;
+  EXPECT(!c.due_at(0) && c.due_at(1) && c.due_at(3) && !c.due_at(4) && c.active());
+  c.steps = 3;
+  EXPECT(!c.active());
+  EXPECT(sg_injector_weights(&whole, 1, nullptr, nullptr, nullptr) == SG_ERR_ARG);
+  EXPECT(sg_injector_weights(nullptr, 0, nullptr, nullptr, nullptr) == SG_ERR_ARG);
+}
+
 // The items of the regions of a split stage (hostapi.cpp region_items) against a per-cube brute force, on the ragged block
 // and the neighbour masks of regions_and_coords(), in every layout
 static void region_item_lists() {
@@ -1316,6 +1443,7 @@ int main() {
       for (int degree : {1, 3}) {
         box_ricker(dim, kind == KIND_TENSOR ? SG_DIAGONAL_QUAD : dim % 2, degree);
         receiver_plans(dim, kind == KIND_TENSOR ? SG_DIAGONAL_QUAD : dim % 2, degree);
+        injector_plans(dim, kind == KIND_TENSOR ? SG_DIAGONAL_QUAD : dim % 2, degree);
       }
     }
   // arguments the entry points must refuse
