@@ -12,7 +12,7 @@
  *     post sends and receives to several peers - and to itself - in one group without deadlock;
  *   - stream order: everything queued on `stream` before the call is complete before a byte is read, the received
  *     bytes are in place before anything queued after the call runs (the double blocks the HOST where RCCL would
- *     block the stream: stricter, never weaker);
+ *     block the stream, and its copies run on `stream` itself: stricter, never weaker);
  *   - ncclCommInitRank is collective over the nranks ranks that hold the same unique id.
  * Stricter than RCCL on purpose: a receive whose byte count differs from the matching send, a transfer that does not
  * arrive within FAKE_RCCL_TIMEOUT_S (default 60 s) and a rank number claimed twice are ERRORS (and poison the
@@ -305,12 +305,19 @@ ncclResult_t ncclCommDestroy(ncclComm_t c) {
   return ncclSuccess;
 }
 
-static ncclResult_t fk_copy(void* dst, const void* src, size_t n, int kind /* 1 h2d, 2 d2h */) {
+/* The copy runs ON THE OPERATION'S STREAM and the host waits for that stream: the promise above is about `stream`.  A plain
+ * hipMemcpy runs on the process's null stream instead, which the rank threads of one process share and which has no order
+ * with a stream created hipStreamNonBlocking (the library's are): only the host's return from the call then stood between
+ * the received bytes and the kernel queued next on `stream`. */
+static ncclResult_t fk_copy(void* dst, const void* src, size_t n, int kind /* 1 h2d, 2 d2h */, hipStream_t stream) {
   if (n == 0) return ncclSuccess;
   if (fk_host_mode) {
     memcpy(dst, src, n);
     return ncclSuccess;
   }
+  if (fk_hipMemcpyAsync)
+    return (fk_hipMemcpyAsync(dst, src, n, kind, (void*)stream) == 0 && fk_hipStreamSynchronize((void*)stream) == 0)
+               ? ncclSuccess : ncclUnhandledCudaError;
   return fk_hipMemcpy(dst, src, n, kind) == 0 ? ncclSuccess : ncclUnhandledCudaError;
 }
 
@@ -325,7 +332,7 @@ static ncclResult_t fk_do_send(fk_op* op) {
     if (fk_now() - t0 > limit) return fk_poison(c, "ncclSend: the destination does not receive", ncclSystemError);
     fk_pause(++spins);
   }
-  ncclResult_t r = fk_copy(fk_slot(c, ch, seq), op->buf, op->bytes, 2);
+  ncclResult_t r = fk_copy(fk_slot(c, ch, seq), op->buf, op->bytes, 2, op->stream);
   if (r != ncclSuccess) return fk_poison(c, "ncclSend: copy out of the send buffer failed", r);
   ch->bytes[seq % FK_NSLOT] = op->bytes;
   atomic_store_explicit(&ch->head, seq + 1, memory_order_release);
@@ -353,7 +360,7 @@ static ncclResult_t fk_do_recv(fk_op* op) {
   }
   unsigned char* slot = fk_slot(c, ch, seq);
   if (c->corrupt_recv && op->bytes) slot[0] = (unsigned char)~slot[0];
-  ncclResult_t r = fk_copy(op->buf, slot, op->bytes, 1);
+  ncclResult_t r = fk_copy(op->buf, slot, op->bytes, 1, op->stream);
   if (r != ncclSuccess) return fk_poison(c, "ncclRecv: copy into the receive buffer failed", r);
   atomic_store_explicit(&ch->tail, seq + 1, memory_order_release);
   c->recvs += 1;

@@ -487,7 +487,8 @@ def _solver(dim, P, n):
 def test_rewind_of_a_forced_run_with_observers(gpu, monkeypatch, dim, P, n):
     """The sequence INTEGRATION.md section 3 documents for the forward field: a point-force series, receivers and the monitor
     armed, run(T), the traces read, then rewind step by step beside the adjoint solver (-dt, residuals injected in reversed
-    order, sg_correlate after every step pair).  After m steps back the fields
+    order, sg_correlate after every step pair: the zero-lag loop, an imaging condition - the material gradient's mid-step
+    pairing is tests/test_gradient_gpu.py's).  After m steps back the fields
     are those a twin run holds after K - m steps of the same forced run (1e-11, the re-wind bound of
     tests/test_fullsize_gpu.py, of the fields' scale): the injected entries are taken out again, not only the steps undone.
     The receivers' and the monitor's traces are the run's, untouched by the re-wound steps, whose count does not move."""
