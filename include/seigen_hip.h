@@ -103,7 +103,29 @@ typedef struct sg_config {
                         second mode of SURVEY 8d (32 B per DoF-update; 3-D blocks on the MFMA path, 2-D blocks on the MFMA
                         tile kernels; SG_ERR_ARG elsewhere: 1-D blocks, forced generic / lane kernels).  The C-ABI
                         keeps double on the host side in both modes; halo buffers hold the device type. */
-  void* stream;      /* hipStream_t to launch on, or NULL for the handle's own stream */
+  void* stream;      /* hipStream_t to launch on, or NULL for the handle's own stream (non-blocking, made by sg_create,
+                        destroyed by sg_destroy).  A caller's stream: any stream of `device` that is not the null / legacy
+                        stream - default flags (blocking) or hipStreamNonBlocking, any priority, torch's
+                        (torch.cuda.Stream().cuda_stream) included; several handles may share one, and sg_correlate takes
+                        handles on one stream or on different ones.  It stays the caller's: the library never destroys it,
+                        sg_destroy waits for what the handle queued on it and leaves it alive and idle, and the caller
+                        destroys it after the last handle on it.  Everything the handle launches goes on it - stage
+                        kernels, captured graphs (captured on it, thread-local mode: the calling thread must not have a
+                        capture of its own under way on it) and their replays, pre-passes, sources, recorder, monitor,
+                        injectors, packs, the layout kernels and asynchronous copies of transfers - except the
+                        SG_REGION_SECOND launches of a block with neighbours, which run on a second stream of the
+                        library's own (sg_get_second_stream), ordered against this one by events in both directions.
+                        Calls that return with the launches only QUEUED, ordered on the stream against whatever the
+                        caller puts there before and after, and never waiting on the host: sg_run_stage, sg_end_step,
+                        sg_halo_pack, sg_halo_pack_sides, sg_apply_F, sg_apply_G, sg_correlate and sg_reset_correlation
+                        (release = 0).  Calls that make the host wait for the stream: sg_create (the whole device),
+                        sg_step and the native exchange's stepping (to the end of what they queued), every setter
+                        (sg_set_*, sg_leave_sym), sg_inject, sg_measure, every transfer and read-out (sg_set_field*,
+                        sg_get_field*, sg_get_receivers, sg_get_monitor, sg_get_correlation, sg_get_counters with timing
+                        on), sg_sync and sg_destroy.  The set-up paths also use the legacy stream (hipMemset, hipMemcpy)
+                        after that wait and return when those have completed (a fill is followed by a blocking copy); a
+                        non-blocking stream is not ordered against the legacy stream, so a fill that no host wait follows
+                        (sg_correlate's accumulator, sg_comm_selftest's buffers) goes on the handle's stream. */
   int32_t cube0[3];  /* index of the block's first square / cube counted from `origin` (0: origin is the block's own low
                         corner).  Node coordinates are origin + (cube0 + cube + lattice) * h with the integers added
                         first: a block of a partitioned mesh, or a slab / sub-box of a block evaluated on its own

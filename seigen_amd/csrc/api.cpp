@@ -825,7 +825,8 @@ static int correlation_prepare(sg_handle* a, CorrelationTables& ct) {
   const std::vector<double> op = ct.mfma ? xcorr_mass_tiles(a->re.Mhat, nd) : a->re.Mhat;
   HIPCHECK(a, ct.M.upload(op.data(), op.size()));
   if (ct.acc.alloc((size_t)a->ncells * 3) != hipSuccess) return fail(a, SG_ERR_NOMEM, "sg_correlate: hipMalloc of the accumulator failed");
-  HIPCHECK(a, hipMemset(ct.acc.get(), 0, (size_t)a->ncells * 3 * sizeof(double)));
+  // (on a's stream, ahead of the launch that adds to it: the legacy stream is not ordered against a non-blocking one)
+  HIPCHECK(a, hipMemsetAsync(ct.acc.get(), 0, (size_t)a->ncells * 3 * sizeof(double), a->stream));
   HIPCHECK(a, ct.ev_in.create());
   HIPCHECK(a, ct.ev_out.create());
   ct.ready = true;

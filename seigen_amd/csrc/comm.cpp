@@ -415,7 +415,9 @@ int sg_comm_selftest(sg_handle* h, int64_t* mismatches) {
         hf[i] = (float)hd[i];
       }
       HIPCHECK(h, hipMemcpy(c->send[kind][s].get(), h->f32 ? (const void*)hf.data() : (const void*)hd.data(), n * es, hipMemcpyHostToDevice));
-      HIPCHECK(h, hipMemset(c->recv[kind][s].get(), 0xff, n * es));
+      // (on the handle's stream, as every fill below: a non-blocking stream is not ordered against the legacy stream, and
+      // a hipMemset there may still be under way when the host goes on - it would land on what the exchange received)
+      HIPCHECK(h, hipMemsetAsync(c->recv[kind][s].get(), 0xff, n * es, h->stream));
     }
     int rc = exchange(h, kind ? SG_FIELD_S : SG_FIELD_U, nullptr, false);
     if (rc != SG_OK) return rc;
@@ -431,8 +433,9 @@ int sg_comm_selftest(sg_handle* h, int64_t* mismatches) {
         const double got = h->f32 ? (double)hf[i] : hd[i];
         if (!(got == want)) *mismatches += 1;
       }
-      HIPCHECK(h, hipMemset(c->send[kind][s].get(), 0, n * es));
-      HIPCHECK(h, hipMemset(c->recv[kind][s].get(), 0, n * es));
+      // ... or on the traces that the first pack and exchange of the run behind this call put there
+      HIPCHECK(h, hipMemsetAsync(c->send[kind][s].get(), 0, n * es, h->stream));
+      HIPCHECK(h, hipMemsetAsync(c->recv[kind][s].get(), 0, n * es, h->stream));
     }
   }
   c->stats = keep;

@@ -142,13 +142,19 @@ def test_per_cell_material(gpu):
 # ------------------------------------------------------------------------------------------------
 class _LocalExchange(object):
     """Same call sequence as seigen_amd.parallel.HaloExchanger.step, with the point-to-point
-    transport replaced by device-to-device copies between blocks living on one GPU."""
+    transport replaced by device-to-device copies between blocks living on one GPU.
 
-    def __init__(self, blocks, parts):
+    host_sync=False: every block launches on the caller's stream `stream` (a torch.cuda.Stream), the copies run on that
+    stream too, and the host never waits between pack, copy and stage: the stream alone orders them (and the blocks'
+    second streams against it, sg_run_stage)."""
+
+    def __init__(self, blocks, parts, host_sync=True, stream=None):
         import torch
         from seigen_amd import _lib
         self.torch, self.lib = torch, _lib
         self.blocks, self.parts = blocks, parts
+        self.host_sync, self.stream = host_sync, stream
+        assert host_sync or stream is not None, "without host synchronisation the copies need the blocks' stream"
         self.send, self.recv = [], []
         for b, p in zip(blocks, parts):
             snd, rcv = {}, {}
@@ -179,14 +185,17 @@ class _LocalExchange(object):
             for s in range(2 * p.dim):
                 if p.neighbour(s) is not None:
                     b.halo_pack(field, s, self.send[r][(kind, s)].data_ptr())
-        for b in self.blocks:
-            b.sync()
-        for r, p in enumerate(self.parts):
-            for s in range(2 * p.dim):
-                nb = p.neighbour(s)
-                if nb is not None:
-                    self.recv[r][(kind, s)].copy_(self.send[nb][(kind, s ^ 1)])
-        self.torch.cuda.synchronize()
+        if self.host_sync:
+            for b in self.blocks:
+                b.sync()
+        with self.torch.cuda.stream(self.stream):      # (None: torch's current stream, as ever)
+            for r, p in enumerate(self.parts):
+                for s in range(2 * p.dim):
+                    nb = p.neighbour(s)
+                    if nb is not None:
+                        self.recv[r][(kind, s)].copy_(self.send[nb][(kind, s ^ 1)])
+        if self.host_sync:
+            self.torch.cuda.synchronize()
 
     def step(self, nsteps, pipelined=True):
         from seigen_amd.parallel import STAGE_INPUT, STAGE_OUTPUT
@@ -207,17 +216,20 @@ class _LocalExchange(object):
                     self._exchange(STAGE_INPUT[stage])
                     for b in self.blocks:
                         b.run_stage(stage, lib.REGION_BOUNDARY)
-                for b in self.blocks:
-                    b.sync()
+                if self.host_sync:
+                    for b in self.blocks:
+                        b.sync()
             for b in self.blocks:
                 b.end_step()
 
 
 def _multiblock_case(dim, degree, n, grid, pipelined, extras=False, dtype="f64", separable=False, diagonal="left",
-                     sym=False):
+                     sym=False, stream=None, host_sync=True):
     """Steps the mesh as one block and as the blocks of `grid` and asserts the two agree bitwise.  sym: a symmetric
-    initial stress (the blocks stay in symmetric-stress mode).  Returns the single block's inputs and results (u0, s0,
-    dt, sigma, src_nodes, src_steps - the source values of each step -, u, s) and the stage kernels the split blocks name."""
+    initial stress (the blocks stay in symmetric-stress mode).  stream: a torch.cuda.Stream that every block made here
+    launches on (sg_config::stream), None: each block's own; host_sync: _LocalExchange.  Returns the single block's inputs
+    and results (u0, s0, dt, sigma, src_nodes, src_steps - the source values of each step -, u, s), the stage kernels the
+    split blocks name and their (stream, second stream) pointers."""
     torch = pytest.importorskip("torch")
     if not torch.cuda.is_available():
         pytest.skip("torch sees no GPU")
@@ -226,7 +238,8 @@ def _multiblock_case(dim, degree, n, grid, pipelined, extras=False, dtype="f64",
     from seigen_amd.mesh import Partition
     L = tuple(1.0 for _ in range(dim))
     h = [L[a] / n[a] for a in range(dim)]
-    single = HipBlock(dim, degree, n, h, [0.0] * dim, diagonal, dtype=dtype)
+    sptr = None if stream is None else stream.cuda_stream
+    single = HipBlock(dim, degree, n, h, [0.0] * dim, diagonal, stream=sptr, dtype=dtype)
     u0 = seeded(single.field_shape(_lib.FIELD_U), 11)
     s0 = seeded(single.field_shape(_lib.FIELD_S), 12)
     if sym:
@@ -274,7 +287,7 @@ def _multiblock_case(dim, degree, n, grid, pipelined, extras=False, dtype="f64",
     blocks = []
     for p in parts:
         origin = [p.start[a] * h[a] for a in range(dim)]
-        b = HipBlock(dim, degree, p.n, h, origin, diagonal, p.nbr_mask, dtype=dtype)
+        b = HipBlock(dim, degree, p.n, h, origin, diagonal, p.nbr_mask, stream=sptr, dtype=dtype)
         sel = cells_of(p)
         b.set_params(1.0, dt, 0.5, 0.25)
         b.set_field(_lib.FIELD_U, u0[sel])
@@ -289,14 +302,15 @@ def _multiblock_case(dim, degree, n, grid, pipelined, extras=False, dtype="f64",
             else:
                 b.set_source(mynodes, src_vals[:, mine] if mine else None)
         blocks.append(b)
-    ex = _LocalExchange(blocks, parts)
+    ex = _LocalExchange(blocks, parts, host_sync=host_sync, stream=stream)
     names = sorted({b.stage_kernel_name(st) for b in blocks for st in range(6)})     # halo buffers attached: as they run
     ex.step(3, pipelined)
     for b, p in zip(blocks, parts):
         sel = cells_of(p)
         assert np.array_equal(b.get_field(_lib.FIELD_U), uref[sel]), "velocity differs from the single-block run"
         assert np.array_equal(b.get_field(_lib.FIELD_S), sref[sel]), "stress differs from the single-block run"
-    return dict(u0=u0, s0=s0, dt=dt, sigma=sigma, src_nodes=src_nodes, src_steps=src_steps, u=uref, s=sref, names=names)
+    return dict(u0=u0, s0=s0, dt=dt, sigma=sigma, src_nodes=src_nodes, src_steps=src_steps, u=uref, s=sref, names=names,
+                streams=[(b.stream_ptr(), b.stream2_ptr()) for b in blocks] + [(single.stream_ptr(), single.stream2_ptr())])
 
 
 @pytest.mark.parametrize("dim,degree,n,grid", [

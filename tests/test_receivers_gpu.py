@@ -38,10 +38,11 @@ FAMILIES = [
 ]
 
 
-def make_case(dim, degree, n, diagonal, dtype, sym):
-    """a block of the unit box with smooth fields, an active box-Ricker source and a sponge; returns (block, dt)"""
+def make_case(dim, degree, n, diagonal, dtype, sym, stream=None):
+    """a block of the unit box with smooth fields, an active box-Ricker source and a sponge; returns (block, dt).
+    stream: a hipStream_t of the caller's (as an integer) for the block to launch on, None: the block's own"""
     h = [1.0 / k for k in n]
-    blk = HipBlock(dim, degree, n, h, [0.0] * dim, diagonal, dtype=dtype)
+    blk = HipBlock(dim, degree, n, h, [0.0] * dim, diagonal, stream=stream, dtype=dtype)
     dt = 0.1 * min(h) / degree ** 2
     blk.set_params(1.0, dt, 0.5, 0.25)
     X = blk.node_coords()
