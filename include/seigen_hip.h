@@ -388,6 +388,54 @@ int sg_get_correlation(sg_handle* a, double* out, size_t nbytes);
 /* zero the accumulator (behind what a has queued); release != 0: free it and the tables with it */
 int sg_reset_correlation(sg_handle* a, int release);
 
+/* ---- spectra: running Fourier transforms of the wavefield, accumulated on the device inside the time loop (on-the-fly DFT,
+ * Sirgue, Etgen and Albertin 2008: what frequency-domain imaging and inversion built on time-domain modelling keep instead of
+ * the forward states; it needs no reverse sweep and works with sources and sponges) ---------------------------------------
+ * Armed with nfreq frequencies, `every` and `nsamples`, the handle takes sample j (0-based) after completed step
+ * (j + 1) * every counted from the arming call - through sg_step (graph replay or eager, with or without a communicator) and
+ * through sg_end_step after host-driven stages alike - behind the receivers' recorder and the monitor and BEFORE the
+ * injectors: the sample of step k + 1 never contains injector entry k.  For every word x of a selected field and every
+ * frequency f
+ *   re[f] = fma(w_re, x, re[f]),   im[f] = fma(w_im, x, im[f]),   (w_re, w_im) = w[j][f]
+ * with the caller's table: wu[nsamples][nfreq][2] for the velocity u = SG_FIELD_U (what bit 0, it lives at t) and
+ * ws[nsamples][nfreq][2] for the stress s = SG_FIELD_S (bit 1, at t + dt / 2) - the receivers' bits.  The library adds
+ * exactly w * field, as the injectors add exactly amp * psi: exp(-i omega t), the quadrature weight every * dt, a taper and
+ * the half-step stagger all belong to the caller.  After nsamples samples nothing is added and nothing is refused.
+ * Storage: per selected field and frequency two device buffers (re, im) of doubles in the field's own device layout, word
+ * ((item * nd + a) * ncomp + c) * gw + lane - double for FP32 blocks too, x is converted first (exactly).  A frequency costs
+ * 2 (dim + dim^2) doubles per node.  A word has one writer and there are no atomics: the bits depend only on the field
+ * contents and the weights - the same under graph replay and eager launches, for sg_step(n) and n calls of sg_step(1), for
+ * host-driven stages, with timing on or off, and on a split block (each block accumulates its own cells).
+ * Symmetric-stress storage: only the i <= j lines are accumulated; when the block leaves it (sg_leave_sym, an upload or an
+ * injector table that is not symmetric) the stress accumulators' i > j lines are filled from their mirrors and all lines are
+ * accumulated from then on.
+ * nfreq = 0 disarms and frees; arming again zeroes the accumulators and restarts the count.  A failed call - SG_ERR_ARG: what
+ * outside 1..3, nfreq < 0 or > SG_SPECTRA_MAX_FREQ, every < 1, nsamples < 1, no table for a selected field; SG_ERR_NOMEM -
+ * leaves the spectra armed before it with accumulators and count intact; all buffers are allocated or none.  The host waits
+ * for the handle's stream, as in every setter. */
+#define SG_SPECTRA_MAX_FREQ 8
+int sg_set_spectra(sg_handle* h, int nfreq, int what, int64_t every, int64_t nsamples, const double* wu, const double* ws);
+/* one accumulator -> host[cell][node][comp], the layout of sg_get_field (in symmetric storage the i > j entries from their
+ * mirrors); field 0: velocity, 1: stress; part 0: re, 1: im.  SG_ERR_STATE: nothing armed or the field not selected;
+ * SG_ERR_ARG: another nbytes, freq outside 0 .. nfreq - 1, another part.  The host waits for the handle's stream. */
+int sg_get_spectrum(sg_handle* h, int field, int freq, int part, double* host, size_t nbytes);
+/* samples taken so far (0 when nothing is armed) */
+int sg_spectra_samples(sg_handle* h, int64_t* taken);
+/* The correlation of two handles' spectra, into the accumulator sg_correlate owns (sg_get_correlation / sg_reset_correlation):
+ *   acc_a[c][k] += w[k] |det J| Re( z conj(a^_fa) . b^_fb )_k,c      k = uu, ss, tt
+ * the forms B_k of sg_correlate taken of frequency fa of a against frequency fb of b.  By bilinearity these are launches of
+ * sg_correlate's kernels in double on the accumulators (FP32 blocks too), in this order: (re, re) and (im, im) with weight
+ * z_r w, then - unless z = NULL or z[1] == 0, which both mean z = (1, 0) - (re, im) with -z_i w and (im, re) with +z_i w.
+ * Handles, ordering and failures as in sg_correlate; both handles must have armed the fields a non-zero weight asks for
+ * (w[0]: velocity; w[1], w[2]: stress), else SG_ERR_STATE.  b may be a. */
+int sg_correlate_spectra(sg_handle* a, int fa, sg_handle* b, int fb, const double w[3], const double z[2]);
+/* The spectra's clock and line list as the library keeps them (device-free).  With `steps` steps completed since arming:
+ * out = { step steps + 1 is a sample step (0 / 1), its sample index or -1, some later step is one (0 / 1: "active", the
+ * graph cache key), samples taken once `more` further steps are done }. */
+int sg_spectra_clock(int64_t every, int64_t nsamples, int64_t steps, int64_t more, int64_t out[4]);
+/* the stress lines c = i * dim + j accumulated in full (sym = 0) or symmetric storage, ascending; returns their number */
+int sg_spectra_lines(int dim, int sym, int32_t* lines, int max_lines);
+
 /* un-fused operators for stage-level parity tests:
  *   out = Minv f(w; s_in, u_abs)   (elastic.py:204-209 + :358-367)
  *   out = Minv g(v; u_in)          (elastic.py:211-219 + :358-367)

@@ -14,6 +14,7 @@ ABI_VERSION = 2      # SG_ABI_VERSION of include/seigen_hip.h this binding was w
 FIELD_U, FIELD_UH, FIELD_S, FIELD_SH = 0, 1, 2, 3
 STAGE_UH1, STAGE_STEMP, STAGE_U1, STAGE_SH1, STAGE_UTEMP, STAGE_S1 = range(6)
 REGION_ALL, REGION_INTERIOR, REGION_BOUNDARY, REGION_FIRST, REGION_SECOND = 0, 1, 2, 3, 4
+SPECTRA_MAX_FREQ = 8  # SG_SPECTRA_MAX_FREQ
 
 
 class SgConfig(C.Structure):
@@ -79,6 +80,12 @@ SYMBOLS = {
     "sg_correlate": (C.c_int, [_P, _P, _P]),
     "sg_get_correlation": (C.c_int, [_P, _P, C.c_size_t]),
     "sg_reset_correlation": (C.c_int, [_P, C.c_int]),
+    "sg_set_spectra": (C.c_int, [_P, C.c_int, C.c_int, C.c_int64, C.c_int64, _P, _P]),
+    "sg_get_spectrum": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t]),
+    "sg_spectra_samples": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "sg_correlate_spectra": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P]),
+    "sg_spectra_clock": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P]),
+    "sg_spectra_lines": (C.c_int, [C.c_int, C.c_int, _P, C.c_int]),
     "sg_locate_points": (C.c_int, [C.POINTER(SgConfig), C.c_int64, _P, _P, _P]),
     "sg_apply_F": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     "sg_apply_G": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),

@@ -340,6 +340,66 @@ class HipBlock(object):
         """Zero the accumulator; release: free it (get_correlation then raises until the next correlate)."""
         check(self.lib.sg_reset_correlation(self.h, int(bool(release))), self.h)
 
+    # ---- spectra (sg_set_spectra / sg_get_spectrum / sg_spectra_samples / sg_correlate_spectra) ---------
+    def set_spectra(self, wu=None, ws=None, every=1):
+        """Arm running Fourier transforms: sample j is taken after step (j + 1) * every counted from this call, behind the
+        recorder and the monitor and before the injectors, and adds w[j][f] * field to accumulator f.  wu / ws: the complex
+        weights [nsamples, nfreq] of the velocity / the stress (or real [nsamples, nfreq, 2]); None: the field is not
+        selected.  Both None: disarm and free."""
+        tabs = []
+        for w in (wu, ws):
+            if w is None:
+                tabs.append(None)
+                continue
+            w = np.asarray(w)
+            if np.iscomplexobj(w):
+                w = np.stack([w.real, w.imag], axis=-1)
+            w = _f64(w)
+            if w.ndim != 3 or w.shape[2] != 2:
+                raise ValueError("weights are complex [nsamples, nfreq] or real [nsamples, nfreq, 2], not %r" % (w.shape,))
+            tabs.append(w)
+        given = [w for w in tabs if w is not None]
+        if not given:
+            check(self.lib.sg_set_spectra(self.h, 0, 0, 1, 0, None, None), self.h)
+            self._spc = None
+            return
+        if len(given) == 2 and given[0].shape != given[1].shape:
+            raise ValueError("the two weight tables differ in shape: %r and %r" % (given[0].shape, given[1].shape))
+        nsamples, nfreq = given[0].shape[:2]
+        what = (1 if tabs[0] is not None else 0) | (2 if tabs[1] is not None else 0)
+        check(self.lib.sg_set_spectra(self.h, int(nfreq), what, int(every), int(nsamples),
+                                      None if tabs[0] is None else tabs[0].ctypes.data,
+                                      None if tabs[1] is None else tabs[1].ctypes.data), self.h)
+        self._spc = (what, int(nfreq))
+
+    def get_spectrum(self, field, freq):
+        """The accumulator of frequency `freq` of the velocity (field 0 / FIELD_U) or the stress (1 / FIELD_S) as a complex
+        array of the field's host shape."""
+        k = {0: 0, 1: 1, _lib.FIELD_S: 1}[int(field)]
+        shape = self.field_shape(_lib.FIELD_S if k else _lib.FIELD_U)
+        re, im = np.empty(shape), np.empty(shape)
+        check(self.lib.sg_get_spectrum(self.h, k, int(freq), 0, re.ctypes.data, re.nbytes), self.h)
+        check(self.lib.sg_get_spectrum(self.h, k, int(freq), 1, im.ctypes.data, im.nbytes), self.h)
+        return re + 1j * im
+
+    def spectra_samples(self):
+        """Samples taken since the arming call (0: nothing armed)."""
+        n = C.c_int64()
+        check(self.lib.sg_spectra_samples(self.h, C.byref(n)), self.h)
+        return int(n.value)
+
+    def correlate_spectra(self, other, f, f_other=None, w=None, z=1.0):
+        """acc[c] += w * |det J| * Re(z conj(a^_f) . b^_f_other) in the forms (uu, ss, tt) of correlate(), of this block's
+        spectra against `other`'s, into the accumulator of correlate() (get_correlation / reset_correlation)."""
+        if w is not None:
+            w = _f64(w)
+            if w.shape != (3,):
+                raise ValueError("weights are one (w_uu, w_ss, w_tt), not %r" % (w.shape,))
+        z = complex(z)
+        zz = _f64([z.real, z.imag])
+        check(self.lib.sg_correlate_spectra(self.h, int(f), other.h, int(f if f_other is None else f_other),
+                                            None if w is None else w.ctypes.data, zz.ctypes.data), self.h)
+
     def apply_F(self, s_in, u_abs, u_out):
         check(self.lib.sg_apply_F(self.h, s_in, u_abs, u_out), self.h)
 

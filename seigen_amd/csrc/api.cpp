@@ -912,6 +912,158 @@ int sg_reset_correlation(sg_handle* a, int release) {
   return SG_OK;
 }
 
+// The spectra (kernels_spectra.hip): weight tables and zeroed accumulators are built in locals and moved into the handle once
+// nothing can fail any more, as the receivers' and the monitor's are.
+int sg_set_spectra(sg_handle* h, int nfreq, int what, int64_t every, int64_t nsamples, const double* wu, const double* ws) {
+  if (!h) return SG_ERR_ARG;
+  if (nfreq < 0 || nfreq > SG_SPECTRA_MAX_FREQ)
+    return fail(h, SG_ERR_ARG, "sg_set_spectra: nfreq must be 0 (disarm) .. " + std::to_string(SG_SPECTRA_MAX_FREQ));
+  SpectraTables sp;
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  if (nfreq > 0) {
+    if (what < 1 || what > 3) return fail(h, SG_ERR_ARG, "sg_set_spectra: what must be 1 (velocity), 2 (stress) or 3");
+    if (every < 1) return fail(h, SG_ERR_ARG, "sg_set_spectra: every must be >= 1");
+    if (nsamples < 1) return fail(h, SG_ERR_ARG, "sg_set_spectra: nsamples must be >= 1");
+    if (nsamples > ((int64_t)1 << 32)) return fail(h, SG_ERR_ARG, "sg_set_spectra: more than 2^32 samples");
+    const double* tables[2] = {wu, ws};
+    const int fields[2] = {SG_FIELD_U, SG_FIELD_S};
+    for (int k = 0; k < 2; ++k)
+      if ((what & (1 << k)) && !tables[k]) return fail(h, SG_ERR_ARG, "sg_set_spectra: no weight table for a selected field");
+    sp.nfreq = nfreq;
+    sp.what = what;
+    sp.clock.every = every;
+    sp.clock.nsamples = nsamples;
+    for (int k = 0; k < 2; ++k) {
+      if (!(what & (1 << k))) continue;
+      const size_t n = (size_t)2 * nfreq * h->field_alloc[fields[k]];
+      if (sp.acc[k].alloc(n) != hipSuccess || sp.w[k].alloc((size_t)nsamples * nfreq * 2) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, SG_ERR_NOMEM, "sg_set_spectra: hipMalloc of the accumulators (" + std::to_string(n * sizeof(double)) +
+                                         " bytes) or of the weight table failed");
+      }
+    }
+    for (int k = 0; k < 2; ++k) {
+      if (!(what & (1 << k))) continue;
+      HIPCHECK(h, hipMemcpy(sp.w[k].get(), tables[k], (size_t)nsamples * nfreq * 2 * sizeof(double), hipMemcpyHostToDevice));
+      // (on the handle's stream, which the host waits for below: the legacy stream is not ordered against a non-blocking one)
+      HIPCHECK(h, hipMemsetAsync(sp.acc[k].get(), 0, (size_t)2 * nfreq * h->field_alloc[fields[k]] * sizeof(double), h->stream));
+    }
+    const int64_t zero = 0;
+    HIPCHECK(h, sp.ctr.upload(&zero, 1));
+  }
+  HIPCHECK(h, sync_all(h));
+  h->spc = std::move(sp);
+  h->epoch += 1;
+  return SG_OK;
+}
+
+int sg_get_spectrum(sg_handle* h, int field, int freq, int part, double* host, size_t nbytes) {
+  if (!h) return SG_ERR_ARG;
+  if (field < 0 || field > 1) return fail(h, SG_ERR_ARG, "sg_get_spectrum: field is 0 (velocity) or 1 (stress)");
+  const SpectraTables& sp = h->spc;
+  if (!sp.has(field)) return fail(h, SG_ERR_STATE, "sg_get_spectrum: no spectra armed for this field (sg_set_spectra)");
+  if (freq < 0 || freq >= sp.nfreq) return fail(h, SG_ERR_ARG, "sg_get_spectrum: frequency outside 0 .. nfreq - 1");
+  if (part < 0 || part > 1) return fail(h, SG_ERR_ARG, "sg_get_spectrum: part is 0 (re) or 1 (im)");
+  const int f = field == 0 ? SG_FIELD_U : SG_FIELD_S;
+  if (!host || nbytes != h->field_len[f] * sizeof(double)) return fail(h, SG_ERR_ARG, "sg_get_spectrum: size mismatch");
+  HIPCHECK(h, hipSetDevice(h->cfg.device));
+  return download_layout(h, f, sp.acc[field].get() + (size_t)(2 * freq + part) * h->field_alloc[f], host);
+}
+
+int sg_spectra_samples(sg_handle* h, int64_t* taken) {
+  if (!h || !taken) return SG_ERR_ARG;
+  *taken = h->spc.nfreq > 0 ? h->spc.clock.samples() : 0;
+  return SG_OK;
+}
+
+// By bilinearity up to four launches of sg_correlate's kernel, double instantiation, on the accumulators of the two handles.
+int sg_correlate_spectra(sg_handle* a, int fa, sg_handle* b, int fb, const double w[3], const double z[2]) {
+  if (!a) return SG_ERR_ARG;
+  if (!b) return fail(a, SG_ERR_ARG, "sg_correlate_spectra: no second handle");
+  if (b != a) {
+    const std::string diff = xcorr_first_difference(a->cfg, (int)a->md.gw, b->cfg, (int)b->md.gw);
+    if (!diff.empty()) return fail(a, SG_ERR_ARG, "sg_correlate_spectra: the handles differ in " + diff);
+  }
+  double wk[3];
+  for (int k = 0; k < 3; ++k) wk[k] = w ? w[k] : 1.0;
+  const bool need_u = wk[0] != 0.0, need_s = wk[1] != 0.0 || wk[2] != 0.0;
+  for (const sg_handle* x : {(const sg_handle*)a, (const sg_handle*)b}) {
+    if (x->spc.nfreq == 0) return fail(a, SG_ERR_STATE, "sg_correlate_spectra: a handle has no spectra armed (sg_set_spectra)");
+    if ((need_u && !x->spc.has(0)) || (need_s && !x->spc.has(1)))
+      return fail(a, SG_ERR_STATE, "sg_correlate_spectra: a weight asks for a field whose spectra a handle has not armed");
+  }
+  if (fa < 0 || fa >= a->spc.nfreq || fb < 0 || fb >= b->spc.nfreq)
+    return fail(a, SG_ERR_ARG, "sg_correlate_spectra: frequency outside 0 .. nfreq - 1");
+  if (!need_u && !need_s) return SG_OK;
+  HIPCHECK(a, hipSetDevice(a->cfg.device));
+  CorrelationTables fresh;
+  if (!a->cor.ready)
+    if (int rc = correlation_prepare(a, fresh)) return rc;
+  CorrelationTables& ct = a->cor.ready ? a->cor : fresh;
+  if (ct.grid64 == 0) {   // the double instantiation: the handle's own unless the block is FP32
+    ct.grid64 = a->f32 ? prepare_xcorr(a->re.nd, (int)a->md.gw, ct.ipw, ct.mfma ? 1 : 0, 0, a->ncu) : ct.grid;
+    if (ct.grid64 <= 0) {
+      ct.grid64 = 0;
+      return fail(a, SG_ERR_DEVICE, "sg_correlate_spectra: no kernel for this element");
+    }
+  }
+  const int dim = a->cfg.dim;
+  xcorr::Args x;
+  std::memset(&x, 0, sizeof(x));
+  x.M = ct.M.get();
+  x.acc = ct.acc.get();
+  double detj = 1.0;
+  for (int k = 0; k < dim; ++k) detj *= a->cfg.h[k];
+  x.nitems = ct.nitems;
+  x.ncube = a->md.ncube;
+  x.nd = a->re.nd;
+  x.dim = dim;
+  x.gw = (int32_t)a->md.gw;
+  x.ncls = a->ncls;
+  x.ipw = ct.ipw;
+  // the kernel reads the velocity's components and then the listed ones of the stress: a stress no weight asks for is not
+  // listed, a velocity no weight asks for is read from a's and b's own buffers of something finite - the stress accumulators,
+  // which are longer - and its form enters with the weight 0
+  const std::vector<XcorrComp> comps = xcorr_components(dim, a->sym, b->sym);
+  x.ncomp = need_s ? (int32_t)comps.size() : dim;
+  for (int k = 0; k < x.ncomp; ++k) {
+    x.comp_a[k] = comps[k].comp_a;
+    x.comp_b[k] = comps[k].comp_b;
+    x.diag[k] = comps[k].diag ? 1 : 0;
+    x.mult[k] = comps[k].mult;
+  }
+  const size_t nu = a->field_alloc[SG_FIELD_U], ns = a->field_alloc[SG_FIELD_S];
+  auto part_of = [&](const sg_handle* h, int freq, int part, const void*& u, const void*& s) {
+    const double* su = h->spc.has(1) ? h->spc.acc[1].get() + (size_t)(2 * freq + part) * ns : nullptr;
+    s = su;
+    u = h->spc.has(0) ? h->spc.acc[0].get() + (size_t)(2 * freq + part) * nu : su;
+  };
+  // behind everything both handles have queued; b's later work behind the launches
+  if (int rc = join_second(a)) return rc;
+  if (b != a) {
+    if (join_second(b) != SG_OK) return fail(a, SG_ERR_DEVICE, std::string("sg_correlate_spectra: second handle: ") + b->err);
+    HIPCHECK(a, hipEventRecord(ct.ev_in.get(), b->stream));
+    HIPCHECK(a, hipStreamWaitEvent(a->stream, ct.ev_in.get(), 0));
+  }
+  const double zr = z ? z[0] : 1.0, zi = z ? z[1] : 0.0;
+  const struct {
+    int pa, pb;
+    double zw;
+  } terms[4] = {{0, 0, zr}, {1, 1, zr}, {0, 1, -zi}, {1, 0, zi}};
+  for (int t = 0; t < (zi != 0.0 ? 4 : 2); ++t) {
+    part_of(a, fa, terms[t].pa, x.ua, x.sa);
+    part_of(b, fb, terms[t].pb, x.ub, x.sb);
+    for (int k = 0; k < 3; ++k) x.wd[k] = terms[t].zw * wk[k] * detj;
+    if (launch_xcorr(x, ct.mfma ? 1 : 0, 0, ct.grid64, a->stream) != 0) return fail(a, SG_ERR_DEVICE, "correlation launch failed");
+  }
+  if (b != a) {
+    HIPCHECK(a, hipEventRecord(ct.ev_out.get(), a->stream));
+    HIPCHECK(a, hipStreamWaitEvent(b->stream, ct.ev_out.get(), 0));
+  }
+  if (!a->cor.ready) a->cor = std::move(fresh);
+  return SG_OK;
+}
+
 int sg_get_sym(const sg_handle* h, int* sym) {
   if (!h || !sym) return SG_ERR_ARG;
   *sym = h->sym ? 1 : 0;

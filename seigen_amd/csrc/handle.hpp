@@ -1,11 +1,11 @@
 // The handle behind the C-ABI (include/seigen_hip.h) and what its translation units share:
-//   api.cpp      create / destroy, parameters, sponge, source, receivers, injectors, monitor, correlation: device checks, uploads, the move into the handle
+//   api.cpp      create / destroy, parameters, sponge, source, receivers, injectors, monitor, correlation, spectra: device checks, uploads, the move into the handle
 //   transfer.cpp host <-> device field transfers (layout conversion, pinned pipeline)
 //   stages.cpp   regions, stage launches, the LF4 step, graphs, halo packs, timing
 // and, without a device or a HIP header (the CPU sanitizer build, `make host-asan`):
 //   hostapi.cpp (hostlogic.hpp)  family choice, field layout, stage table, region boxes / items, point location, receiver and injector plans;
 //                                what stepping remembers between calls: field write counts, the sponge pre-pass's state,
-//                                the source's slice at a step, the receivers' and the injectors' clocks
+//                                the source's slice at a step, the receivers', the injectors' and the spectra's clocks
 //   sponge_tables.cpp            what sg_set_absorption derives from the nodal sigma
 //   source_tables.cpp            what the source setters derive from the caller's nodes and values
 #pragma once
@@ -139,6 +139,18 @@ struct InjectTables {
   DevBuf<int64_t> ctr;        // graph replay: the step index of the launches of a capture (the role of ReceiverTables::ctr)
 };
 
+// The spectra of sg_set_spectra (kernels_spectra.hip), on the device: per selected field the weight table and the accumulators,
+// which have the field's own layout (double for FP32 blocks too)
+struct SpectraTables {
+  int nfreq = 0;              // frequencies armed (0: none)
+  int what = 0;               // bit 0: velocity, bit 1: stress
+  DevBuf<double> w[2];        // [nsamples][nfreq][2] of the velocity / of the stress
+  DevBuf<double> acc[2];      // [nfreq][2][field_alloc] of the velocity / of the stress
+  SpectraClock clock;         // every, nsamples, steps completed since arming (hostlogic.hpp)
+  DevBuf<int64_t> ctr;        // graph replay: the step index of the launches of a capture (the role of ReceiverTables::ctr)
+  bool has(int k) const { return nfreq > 0 && (what & (1 << k)) != 0; }   // k = 0: velocity, 1: stress
+};
+
 // The monitor of sg_set_monitor and the scratch of sg_measure (kernels_measure.hip), on the device
 struct MonitorTables {
   bool armed = false;
@@ -192,6 +204,7 @@ struct CorrelationTables {
   bool mfma = false;          // the matrix-pipe form (SEIGEN_HIP_XCORR=lds: the LDS-staged one on its layouts too)
   int ipw = 0;                // xcorr::Args::ipw
   int grid = 0;               // persistent grid of the matrix-pipe form
+  int grid64 = 0;             // ... of its double instantiation on an FP32 block (sg_correlate_spectra: prepared by its first call)
   int64_t nitems = 0;
   DevEvent ev_in, ev_out;     // the other handle's stream -> the launch -> the other handle's stream
   bool ready = false;
@@ -270,6 +283,8 @@ struct sg_handle {
   bool graph_mon = false;     // the captured graphs contain the monitor's launches
   InjectTables inj;
   bool graph_inj = false;     // the captured graphs contain the injector launches
+  SpectraTables spc;
+  bool graph_spc = false;     // the captured graphs contain the spectra launches
   CorrelationTables cor;
   // halo
   const double* ghost[4][6] = {};
@@ -364,6 +379,8 @@ int resolve_timing(sg_handle* h);
 int finish_step_call(sg_handle* h);   // stages.cpp: the end of sg_step and comm_step (ev1, synchronise, last_ms)
 int queue_inject(sg_handle* h, hipStream_t stream, const InjectTables& it, const int64_t* ctr, int64_t step);   // stages.cpp: one launch of the injector kernel
 int measure_prepare(sg_handle* h);    // api.cpp: the scratch of the monitor's samples (MeasureScratch), built once
+// transfer.cpp: one buffer in the device layout of field `field` (doubles) -> host[cell][node][comp], behind everything queued
+int download_layout(sg_handle* h, int field, const double* dev, double* host);
 // comm.cpp
 int comm_step(sg_handle* h, int64_t nsteps);
 void comm_release(sg_handle* h);

@@ -345,6 +345,27 @@ extern "C" {
 
 int sg_abi_version(void) { return SG_ABI_VERSION; }
 
+int sg_spectra_clock(int64_t every, int64_t nsamples, int64_t steps, int64_t more, int64_t out[4]) {
+  if (!out || every < 1 || nsamples < 0 || steps < 0 || more < 0) return SG_ERR_ARG;
+  SpectraClock c;
+  c.every = every;
+  c.nsamples = nsamples;
+  c.steps = steps;
+  out[0] = c.due_at(steps + 1) ? 1 : 0;
+  out[1] = c.due_at(steps + 1) ? c.sample_at(steps + 1) : -1;
+  out[2] = c.active() ? 1 : 0;
+  out[3] = c.samples_after(more);
+  return SG_OK;
+}
+
+int sg_spectra_lines(int dim, int sym, int32_t* lines, int max_lines) {
+  if (dim < 1 || dim > 3 || !lines) return SG_ERR_ARG;
+  const std::vector<int32_t> r = spectra_lines(dim, sym != 0);
+  if ((int)r.size() > max_lines) return SG_ERR_ARG;
+  std::copy(r.begin(), r.end(), lines);
+  return (int)r.size();
+}
+
 int sg_injector_weights(const sg_config* cfg, int64_t npts, const double* pts, int64_t* cell, double* psi) {
   if (!cfg || npts < 0 || (npts > 0 && (!pts || !cell || !psi))) return SG_ERR_ARG;
   if (cfg->dim < 1 || cfg->dim > 3 || cfg->degree < 1 || cfg->degree > 4) return SG_ERR_ARG;

@@ -3,6 +3,7 @@
 // point location, the receiver plan and the injector plan.  Defined in hostapi.cpp, which - with refelem.cpp, mesh_tables.cpp, mfma_tables.cpp,
 // sponge_tables.cpp and source_tables.cpp - also builds on its own for the CPU sanitizer target (`make host-asan`).
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <string>
@@ -372,3 +373,25 @@ struct InjectorClock {
 // (the last dim * dim of a point's ncomp values, what bit 1) of every owned point is symmetric to the bit at every step
 std::vector<double> injector_gather(const InjectorPlan& pl, int64_t npts, int64_t nsteps, const double* amp);
 bool injector_symmetric(const InjectorPlan& pl, int dim, int what, int64_t nsteps, const std::vector<double>& gathered);
+
+// The spectra (seigen_hip.h sg_set_spectra; kernels_spectra.hip) keep the receivers' rhythm and the injectors' end: sample j
+// (0-based) after step (j + 1) * every counted from the arming call, nsamples samples, after which nothing is added and
+// nothing is refused.
+struct SpectraClock {
+  int64_t every = 1, nsamples = 0;
+  int64_t steps = 0;   // completed since arming
+  bool due_at(int64_t s) const { return s >= 1 && s % every == 0 && s / every <= nsamples; }   // step s (1-based) is a sample step
+  int64_t sample_at(int64_t s) const { return s / every - 1; }                                    // ... of this sample
+  bool active() const { return (steps + every) / every <= nsamples; }                            // some later step is one
+  int64_t samples_after(int64_t n) const { return std::min((steps + n) / every, nsamples); }     // taken once n more steps are done
+  int64_t samples() const { return samples_after(0); }
+};
+// The lines c = i * dim + j of a stress word ((item * nd + a) * dim^2 + c) * gw + lane that are accumulated: all dim^2 of full
+// storage, the i <= j ones of symmetric storage (the others hold no valid stress there)
+inline bool spectra_line_kept(int dim, bool sym, int c) { return !sym || c / dim <= c % dim; }
+inline std::vector<int32_t> spectra_lines(int dim, bool sym) {
+  std::vector<int32_t> r;
+  for (int c = 0; c < dim * dim; ++c)
+    if (spectra_line_kept(dim, sym, c)) r.push_back(c);
+  return r;
+}

@@ -380,4 +380,24 @@ struct Args {
 }  // namespace inject
 int launch_inject(void* u, void* s, const inject::Args& a, int f32, void* stream);
 
+// Spectra (kernels_spectra.hip; seigen_hip.h sg_set_spectra): at the end of step s (counted from the arming call; s from
+// *ctr + 1 under graph replay) with s % every == 0 and j = s / every - 1 < nsamples, every word x of the field's n words
+// enters acc[f][part][idx] = fma(w[j][f][part], x, acc[f][part][idx]) - but the words of the lines (idx / gw) % ncomp = i * dim + j
+// with i > j where sym is set (a stress field in symmetric storage).  One flat pass over the field, of at most `grid` blocks.
+namespace spectra {
+struct Args {
+  const int64_t* ctr;      // graph replay: *ctr + 1 is the step that just ended; null: `step`
+  int64_t step;
+  int64_t every, nsamples; // (a sample beyond the series adds nothing)
+  const double* w;         // [nsamples][nfreq][2]
+  double* acc;             // [nfreq][2][n]
+  int64_t n;               // words of the field as allocated (the layout's padding included)
+  int32_t nfreq;
+  int32_t gw, ncomp, dim;  // the line of a word (only looked at where sym is set)
+  int32_t sym;
+  int32_t vec_line;        // the words of a 16-byte access lie on one line (gw is a multiple of their number)
+};
+}  // namespace spectra
+int launch_spectra(const void* field, const spectra::Args& a, int f32, int grid, void* stream);
+
 }  // namespace sg

@@ -12,6 +12,7 @@ struct LaunchCtx {
   bool capture_rec = false;           // ... and the recorder's step from rec.ctr
   bool capture_mon = false;           // ... and the monitor's from mon.ctr
   bool capture_inj = false;           // ... and the injectors' from inj.ctr (a series that has run out: no launch)
+  bool capture_spc = false;           // ... and the spectra's from spc.ctr (likewise)
 };
 
 // the source at the handle's step (hostlogic.hpp source_slice), with the device pointers of a capture's SrcStep
@@ -525,14 +526,62 @@ static int inject_step(sg_handle* h, const LaunchCtx& ctx) {
   return SG_OK;
 }
 
-// what ends a step on the stream: the receivers' recorder, then the monitor, then the injectors.  A refusal of the first two
-// (no room for the sample) is found before anything is queued or counted; a launch error of a later one leaves the earlier
-// ones' step counted
+// One launch of the spectra kernel per selected field (kernels_spectra.hip) on `stream`: the fields as they stand there enter
+// the accumulators when the step (by value, or *ctr + 1) is a sample step of the series.
+static int queue_spectra(sg_handle* h, hipStream_t stream, const int64_t* ctr, int64_t step) {
+  const SpectraTables& sp = h->spc;
+  const int fields[2] = {SG_FIELD_U, SG_FIELD_S};
+  for (int k = 0; k < 2; ++k) {
+    if (!sp.has(k)) continue;
+    spectra::Args a;
+    std::memset(&a, 0, sizeof(a));
+    a.ctr = ctr;
+    a.step = step;
+    a.every = sp.clock.every;
+    a.nsamples = sp.clock.nsamples;
+    a.w = sp.w[k].get();
+    a.acc = sp.acc[k].get();
+    a.n = (int64_t)h->field_alloc[fields[k]];
+    a.nfreq = sp.nfreq;
+    a.gw = (int32_t)h->md.gw;
+    a.dim = h->cfg.dim;
+    a.ncomp = k == 1 ? h->cfg.dim * h->cfg.dim : h->cfg.dim;
+    a.sym = (k == 1 && h->sym) ? 1 : 0;
+    a.vec_line = a.gw % (h->f32 ? 4 : 2) == 0 ? 1 : 0;
+    if (launch_spectra(h->field.read(fields[k]), a, h->f32, 8 * std::max(h->ncu, 1), stream) != 0)
+      return fail(h, SG_ERR_DEVICE, "spectra launch failed");
+  }
+  return SG_OK;
+}
+
+// The end of a step for the spectra (sg_set_spectra), behind the recorder and the monitor and before the injectors: the sample
+// is of u1 and s1 of the step that just ended, without the entry the injectors add for the next one.  By the injectors' rules:
+// eager launches name the step by value, count it here and launch nothing on a step that is no sample step or once the
+// series has run out; the launches of a capture read the step from spc.ctr and bump that, and a capture counts nothing.
+static int spectra_step(sg_handle* h, const LaunchCtx& ctx) {
+  SpectraTables& sp = h->spc;
+  if (sp.nfreq == 0) return SG_OK;
+  const int64_t step = sp.clock.steps + 1;
+  const bool launch = ctx.capture_spc ? sp.clock.active() : sp.clock.due_at(step);
+  if (launch) {
+    if (int rc = join_second(h)) return rc;
+    if (int rc = queue_spectra(h, ctx.stream, ctx.capture_spc ? sp.ctr.get() : nullptr, step)) return rc;
+    if (ctx.capture_spc && launch_step_counter(sp.ctr.get(), 1, 1, ctx.stream) != 0)
+      return fail(h, SG_ERR_DEVICE, "step counter launch failed");
+  }
+  if (!ctx.capture_spc) sp.clock.steps = step;
+  return SG_OK;
+}
+
+// what ends a step on the stream: the receivers' recorder, then the monitor, then the spectra, then the injectors.  A refusal
+// of the first two (no room for the sample) is found before anything is queued or counted; a launch error of a later one
+// leaves the earlier ones' step counted
 static int end_of_step(sg_handle* h, const LaunchCtx& ctx) {
   if (monitor_no_room(h, ctx))
     return fail(h, SG_ERR_STATE, "monitor trace full: read it out (sg_get_monitor) and re-arm before stepping on");
   if (int rc = record_step(h, ctx)) return rc;
   if (int rc = monitor_step(h, ctx)) return rc;
+  if (int rc = spectra_step(h, ctx)) return rc;
   return inject_step(h, ctx);
 }
 
@@ -546,6 +595,7 @@ static void steps_done(sg_handle* h, int64_t n, bool replayed) {
   if (h->rec.nrec > 0) h->rec.clock.steps += n;
   if (h->mon.armed) h->mon.clock.steps += n;
   if (h->inj.npts > 0) h->inj.clock.steps += n;
+  if (h->spc.nfreq > 0) h->spc.clock.steps += n;
   h->field.replayed();
   h->sponge.pre_state.forget();
 }
@@ -590,7 +640,7 @@ static hipGraphExec_t capture_steps(sg_handle* h, int steps, bool with_src) {
   }
   if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return nullptr;
   int rc = SG_OK;
-  const LaunchCtx ctx{h->stream, with_src, h->rec.nrec > 0, h->mon.armed, h->inj.npts > 0};
+  const LaunchCtx ctx{h->stream, with_src, h->rec.nrec > 0, h->mon.armed, h->inj.npts > 0, h->spc.nfreq > 0};
   h->sponge.pre_state.forget();      // a replay starts from whatever the buffer holds: the captured step computes its own
   for (int k = 0; k < steps && rc == SG_OK; ++k) rc = enqueue_step(h, ctx, false);
   h->sponge.pre_state.forget();      // nothing was launched: the buffer does not hold what the capture asked for
@@ -624,9 +674,10 @@ static int check_monitor_room(sg_handle* h, int64_t nsteps) {
 static int ensure_graphs(sg_handle* h) {
   const bool with_src = source_at(h, false).active, with_rec = h->rec.nrec > 0, with_mon = h->mon.armed;
   const bool with_inj = h->inj.npts > 0 && h->inj.clock.active();   // a series that has run out: no injector launches
+  const bool with_spc = h->spc.nfreq > 0 && h->spc.clock.active();  // ... and no spectra launches
   if (with_src && !h->src_ctr_d.get()) return fail(h, SG_ERR_STATE, "source without a device-side step counter");
   if (h->graph_epoch == h->epoch && h->graph_src == with_src && h->graph_rec == with_rec && h->graph_mon == with_mon &&
-      h->graph_inj == with_inj)
+      h->graph_inj == with_inj && h->graph_spc == with_spc)
     return SG_OK;
   if (h->graph1) (void)hipGraphExecDestroy(h->graph1);
   if (h->graph8) (void)hipGraphExecDestroy(h->graph8);
@@ -637,6 +688,7 @@ static int ensure_graphs(sg_handle* h) {
   h->graph_rec = with_rec;
   h->graph_mon = with_mon;
   h->graph_inj = with_inj;
+  h->graph_spc = with_spc;
   if (!h->graph1 || !h->graph8) h->graph_ok = false;  // same kernels, launched one by one (eager_steps)
   return SG_OK;
 }
@@ -651,6 +703,8 @@ static int replay_steps(sg_handle* h, int64_t nsteps) {
   if (h->mon.armed && launch_step_counter(h->mon.ctr.get(), h->mon.clock.steps, 0, h->stream) != 0)
     return fail(h, SG_ERR_DEVICE, "step counter launch failed");
   if (h->graph_inj && h->inj.nown > 0 && launch_step_counter(h->inj.ctr.get(), h->inj.clock.steps, 0, h->stream) != 0)
+    return fail(h, SG_ERR_DEVICE, "step counter launch failed");
+  if (h->graph_spc && launch_step_counter(h->spc.ctr.get(), h->spc.clock.steps, 0, h->stream) != 0)
     return fail(h, SG_ERR_DEVICE, "step counter launch failed");
   int64_t k = 0;
   for (; k + 8 <= nsteps; k += 8) HIPCHECK(h, hipGraphLaunch(h->graph8, h->stream));

@@ -10,6 +10,12 @@ int leave_sym_mode(sg_handle* h) {
   for (int f : {SG_FIELD_S, SG_FIELD_SH}) {
     if (launch_mirror(h->md, h->field.write(f), h->f32, h->stream) != 0) return fail(h, SG_ERR_DEVICE, "mirror kernel launch failed");
   }
+  // the stress spectra (sg_set_spectra) have accumulated the i <= j lines only: every accumulator is a stress field in double
+  if (h->spc.has(1)) {
+    const size_t n = h->field_alloc[SG_FIELD_S];
+    for (int k = 0; k < 2 * h->spc.nfreq; ++k)
+      if (launch_mirror(h->md, h->spc.acc[1].get() + (size_t)k * n, 0, h->stream) != 0) return fail(h, SG_ERR_DEVICE, "mirror kernel launch failed");
+  }
   HIPCHECK(h, sync_all(h));
   h->sym = false;
   return SG_OK;
@@ -144,6 +150,38 @@ static int transfer(sg_handle* h, int field, int64_t cell0, int64_t ncells, doub
       if (rc != SG_OK) return rc;
       return transfer(h, field, cell0, ncells, host, true);
     }
+  }
+  return SG_OK;
+}
+
+// One buffer in the device layout of field `field`, in double whatever the block's dtype (an accumulator of the spectra), ->
+// host[cell][node][comp] through the staging buffer and the layout kernel of the fields' own downloads; a stress buffer of a
+// block in symmetric storage takes its (i > j) entries from their mirrors.
+int download_layout(sg_handle* h, int field, const double* dev, double* host) {
+  if (int rc = join_second(h)) return rc;
+  HIPCHECK(h, sync_all(h));
+  const size_t per_cell = h->field_len[field] / (size_t)h->ncells;
+  if (h->md.gw == 1) {
+    HIPCHECK(h, hipMemcpy(host, dev, h->field_len[field] * sizeof(double), hipMemcpyDeviceToHost));
+    return SG_OK;
+  }
+  const size_t per_cell_max = (size_t)h->re.nd * h->cfg.dim * h->cfg.dim;
+  const size_t cap_cells = std::max<size_t>(1, ((size_t)32 << 20) / per_cell_max);
+  if (!h->staging.get()) {
+    const size_t len = std::min(cap_cells, (size_t)h->ncells) * per_cell_max;
+    HIPCHECK(h, h->staging.alloc(len));
+    h->staging_len = len;
+  }
+  const size_t chunk = h->staging_len / per_cell;
+  if (chunk == 0) return fail(h, SG_ERR_STATE, "staging buffer smaller than one cell");
+  const int comps = (int)(per_cell / h->re.nd);
+  const int symdl = (h->sym && field_is_stress(field)) ? 1 : 0;
+  for (int64_t done = 0; done < h->ncells; done += (int64_t)chunk) {
+    const int64_t n = std::min<int64_t>((int64_t)chunk, h->ncells - done);
+    if (launch_layout(h->md, comps, 1, const_cast<double*>(dev), h->staging.get(), done, n, symdl, nullptr, 0, h->stream) != 0)
+      return fail(h, SG_ERR_DEVICE, "layout kernel launch failed");
+    HIPCHECK(h, sync_all(h));
+    HIPCHECK(h, hipMemcpy(host + (size_t)done * per_cell, h->staging.get(), (size_t)n * per_cell * sizeof(double), hipMemcpyDeviceToHost));
   }
   return SG_OK;
 }

@@ -78,6 +78,23 @@ def sensitivity(dim, density, lam, mu, corr):
             "mu": -ss / (2.0 * mu ** 2) + lam * (dim * lam + 4.0 * mu) / (2.0 * mu ** 2 * k ** 2) * tt}
 
 
+def spectra_weights(freqs, dt, every, nsamples, t0=0.0, stagger=0.0, window=None):
+    """The complex weights [nsamples, nfreq, 2] = (re, im) of a running Fourier transform (sg_set_spectra) by the rectangle
+    rule: w[j][f] = every * dt * window[j] * exp(-2 pi i freqs[f] t_j) at the sample times t_j = t0 + (j + 1) * every * dt +
+    stagger - stagger = dt / 2 for the stress, which lives half a step behind the velocity.  window: [nsamples] (a taper),
+    None = 1.  The library adds exactly w * field; everything else is decided here."""
+    freqs = np.atleast_1d(np.asarray(freqs, dtype=np.float64)).ravel()
+    nsamples, every = int(nsamples), int(every)
+    if every < 1 or nsamples < 0:
+        raise ValueError("spectra_weights needs every >= 1 and nsamples >= 0")
+    win = np.ones(nsamples) if window is None else np.asarray(window, dtype=np.float64).ravel()
+    if win.shape != (nsamples,):
+        raise ValueError("the window holds one value per sample (%d), not %r" % (nsamples, win.shape))
+    t = float(t0) + (np.arange(nsamples) + 1.0) * every * float(dt) + float(stagger)
+    w = (every * float(dt)) * win[:, None] * np.exp(-2j * np.pi * freqs[None, :] * t[:, None])
+    return np.ascontiguousarray(np.stack([w.real, w.imag], axis=-1))
+
+
 def _device_for_rank():
     if "SEIGEN_HIP_DEVICE" in os.environ:
         return int(os.environ["SEIGEN_HIP_DEVICE"])
@@ -174,6 +191,8 @@ class ElasticLF4(object):
             self._receiver_times = []
             self._monitor = None            # `every` of set_monitor
             self._monitor_times = []
+            self._spectra = None            # (freqs, every, nsamples, what, window) of set_spectra
+            self._spectra_freqs = None      # the frequencies armed by the last run
             self._injected = []             # what inject / set_injectors have added, for rewind (see _position)
             self._armed = None              # the armed series' entries still to be logged
             self._rewound = 0               # steps re-wound so far
@@ -668,6 +687,65 @@ class ElasticLF4(object):
         self._block.set_monitor(every, max(1, len(times) // every), self.energy_weights())
         self._monitor_times = list(times[every - 1::every])
 
+    # ---- spectra: running Fourier transforms inside the time loop (sg_set_spectra) ---------------------
+    def set_spectra(self, freqs, every=1, nsamples=None, fields=("velocity", "stress"), window=None):
+        """Accumulate the Fourier transforms of `fields` ("velocity" = VelocityNew at t, "stress" = StressNew at t + dt/2) at
+        the frequencies `freqs` (Hz) over the next runs, on the device inside the time loop: sample j after step
+        (j + 1) * every with the weights of spectra_weights (the rectangle rule, t from 0 at the start of the run, stagger
+        dt / 2 for the stress), `nsamples` of them (None: all the run has).  No frequencies: none.  It works with a source
+        and a sponge, and keeps 2 (dim + dim^2) doubles per node and frequency."""
+        freqs = np.atleast_1d(np.asarray([] if freqs is None else freqs, dtype=np.float64)).ravel()
+        if freqs.size == 0:
+            self._spectra = None
+            return
+        what = 0
+        for f in fields:
+            if f not in ("velocity", "stress"):
+                raise ValueError("spectra fields are 'velocity' and 'stress', not %r" % (f,))
+            what |= 1 if f == "velocity" else 2
+        if what == 0 or int(every) < 1 or freqs.size > _lib.SPECTRA_MAX_FREQ:
+            raise ValueError("set_spectra needs at least one field, every >= 1 and at most %d frequencies" % _lib.SPECTRA_MAX_FREQ)
+        self._spectra = (freqs, int(every), None if nsamples is None else int(nsamples), what, window)
+
+    def _arm_spectra(self, times):
+        if self._spectra is None:
+            if self._spectra_freqs is not None:
+                self._block.set_spectra(None, None)
+                self._spectra_freqs = None
+            return
+        freqs, every, nsamples, what, window = self._spectra
+        n = len(times) // every if nsamples is None else nsamples
+        if n < 1:
+            raise ValueError("set_spectra: the run has no sample step (every = %d, %d steps)" % (every, len(times)))
+        wu = spectra_weights(freqs, self.dt, every, n, window=window) if what & 1 else None
+        ws = spectra_weights(freqs, self.dt, every, n, stagger=0.5 * self.dt, window=window) if what & 2 else None
+        self._block.set_spectra(wu, ws, every)
+        self._spectra_freqs = freqs
+
+    def _spectrum_index(self, f):
+        if self._spectra_freqs is None:
+            raise RuntimeError("no spectra: call set_spectra before run")
+        k = np.nonzero(self._spectra_freqs == float(f))[0]
+        if k.size == 0:
+            raise ValueError("frequency %r is none of the armed ones %r" % (f, list(self._spectra_freqs)))
+        return int(k[0])
+
+    def spectrum(self, field, f):
+        """The transform of `field` ("velocity" or "stress") at the armed frequency `f` as accumulated so far: a complex array
+        in the shape of the Function's data ([nodes, dim] or [nodes, dim, dim]), of this rank's block."""
+        if field not in ("velocity", "stress"):
+            raise ValueError("spectra fields are 'velocity' and 'stress', not %r" % (field,))
+        d = self.dimension
+        out = self._block.get_spectrum(0 if field == "velocity" else 1, self._spectrum_index(f))
+        return out.reshape((-1, d) if field == "velocity" else (-1, d, d))
+
+    def correlate_spectra(self, other, f, f_other=None, weights=(1.0, 1.0, 1.0), z=1 + 0j):
+        """Add weights * Re(z conj(a^(f)) . b^(f_other)) in the forms (uu, ss, tt) of `correlate` - a^ this solver's spectra,
+        b^ `other`'s (f_other = None: the same frequency) - to this block's per-cell accumulator (correlation,
+        reset_correlation): the frequency-domain imaging condition is the sum of these calls over the frequencies."""
+        fo = f if f_other is None else f_other
+        self._block.correlate_spectra(other._block, self._spectrum_index(f), other._spectrum_index(fo), weights, z)
+
     # ---- correlation with another solver's fields, cell by cell (sg_correlate) ------------------------
     def correlate(self, other, weights=(1.0, 1.0, 1.0)):
         """Add weights * (uu, ss, tt) of this solver's (u1, s1) against `other`'s - an ElasticLF4 on the same mesh and
@@ -726,6 +804,7 @@ class ElasticLF4(object):
             self._agree_on_stress_storage()
             self._arm_receivers(times)
             self._arm_monitor(times)
+            self._arm_spectra(times)
             with self.loop_context():
                 if self.output:
                     for t in times:

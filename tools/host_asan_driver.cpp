@@ -1396,7 +1396,50 @@ static void correlation_compatibility() {
   b = a; b.degree = 3; b.dtype = 1; named(b, 64, "degree");
 }
 
+// The spectra's clock and line list (hostlogic.hpp SpectraClock, spectra_lines; sg_spectra_clock, sg_spectra_lines) against
+// the list of sample steps written out: sample j after step (j + 1) * every, nsamples of them.
+static void spectra_clock_and_lines() {
+  for (int64_t every : {1, 2, 3, 5})
+    for (int64_t nsamples : {0, 1, 3, 4}) {
+      std::vector<int64_t> at;
+      for (int64_t j = 0; j < nsamples; ++j) at.push_back((j + 1) * every);
+      for (int64_t steps = 0; steps < 24; ++steps) {
+        SpectraClock c;
+        c.every = every;
+        c.nsamples = nsamples;
+        c.steps = steps;
+        const auto hit = std::find(at.begin(), at.end(), steps + 1);
+        EXPECT(c.due_at(steps + 1) == (hit != at.end()));
+        if (hit != at.end()) EXPECT(c.sample_at(steps + 1) == hit - at.begin());
+        EXPECT(c.active() == (!at.empty() && at.back() > steps));
+        for (int64_t more : {0, 1, 7}) {
+          const int64_t taken = std::count_if(at.begin(), at.end(), [&](int64_t s) { return s <= steps + more; });
+          EXPECT(c.samples_after(more) == taken);
+          int64_t out[4] = {-9, -9, -9, -9};
+          EXPECT(sg_spectra_clock(every, nsamples, steps, more, out) == SG_OK);
+          EXPECT(out[0] == (hit != at.end() ? 1 : 0) && out[1] == (hit != at.end() ? hit - at.begin() : -1));
+          EXPECT(out[2] == (c.active() ? 1 : 0) && out[3] == taken);
+        }
+      }
+    }
+  int64_t out[4];
+  EXPECT(sg_spectra_clock(0, 1, 0, 0, out) == SG_ERR_ARG && sg_spectra_clock(1, 1, 0, 0, nullptr) == SG_ERR_ARG);
+  for (int dim = 1; dim <= 3; ++dim)
+    for (int sym : {0, 1}) {
+      std::vector<int32_t> want;
+      for (int i = 0; i < dim; ++i)
+        for (int j = 0; j < dim; ++j)
+          if (!sym || i <= j) want.push_back(i * dim + j);
+      EXPECT(spectra_lines(dim, sym != 0) == want);
+      std::vector<int32_t> got(want.size(), -1);
+      EXPECT(sg_spectra_lines(dim, sym, got.data(), (int)got.size()) == (int)want.size() && got == want);
+      if (want.size() > 1) EXPECT(sg_spectra_lines(dim, sym, got.data(), (int)got.size() - 1) == SG_ERR_ARG);   // no room: nothing written past the end
+    }
+  EXPECT(sg_spectra_lines(4, 0, nullptr, 16) == SG_ERR_ARG);
+}
+
 int main() {
+  spectra_clock_and_lines();
   for (int cell_type : {0, 1})
     for (int dim = 1; dim <= 3; ++dim)
       for (int degree = 1; degree <= 4; ++degree)
