@@ -189,7 +189,12 @@ static int family_tables(sg_handle* h, Frags& fr) {
   HIPCHECK(h, h->Lt.upload(Lt.data(), Lt.size()));
   HIPCHECK(h, h->md_dev.upload(&h->md, 1));
   if (h->family == Family::Mfma) {
-    const MfmaConst mk = mfma_const(h->md);
+    MfmaConst mk;
+    try {
+      mk = mfma_const(h->md);      // (checks the facet rule the F kernels' trace loads are written to: mfma_trace_lines)
+    } catch (const std::exception& e) {
+      return fail(h, SG_ERR_ARG, e.what());
+    }
     HIPCHECK(h, h->mk_dev.upload(&mk, 1));
     std::vector<int32_t> ft, tab;
     mfma_trace_offsets(h->md, 9, ft);

@@ -42,7 +42,21 @@ struct MfmaClassConst {
   uint32_t nbw[4][MK_KSF];    // [f][ks] byte q: neighbour ELEMENT node matching my facet node 4 ks + q (MeshDev::nb_node)
   uint32_t nfw[4][MK_KSF];    // same, as position in the neighbour's facet list (MeshDev::nb_fnode)
   int32_t nb_face[4];         // neighbour's local facet (MeshDev::nb_face)
+  // F stages: the stress lines facet f's scaled normal can see (mfma_trace_lines): the columns j with (c n)_j != 0 in
+  // ascending order ([1] = -1 on a cube-face facet, which has one), offset of the line of T(i, tr_col[c]) in values of the
+  // field type [storage 0: full tensor, 1: symmetric][f][3 c + i] (c = 1 repeats c = 0 where there is no second column),
+  // and (c n) at those columns (0 for the missing one)
+  int32_t tr_col[4][2];
+  int32_t tr_line[2][4][6];
+  double tr_cn[4][2];
 };
+// The rule the F stage kernels are written to (kernels_mfma.hip do_lifts), stated once: facets 0 and 3 of every class lie on
+// a cube face (nb_axis >= 0) and (c n) has ONE non-zero entry, at nb_axis; facets 1 and 2 are inside the cube (nb_axis < 0)
+// and (c n) has TWO; every other entry is exactly zero.  Fills tr_col / tr_line / tr_cn of `kc` for class k; throws
+// std::runtime_error if the mesh tables do not have that shape (sg_create then fails: never a flux from a wrong line).
+void mfma_trace_lines(const MeshDev& md_host, int k, MfmaClassConst& kc);
+// line of T(i, j) in a node's nine slots: slot min * 3 + max in symmetric storage, i * 3 + j in full storage
+inline int stress_line_slot(bool sym, int i, int j) { return sym ? (i < j ? i : j) * 3 + (i < j ? j : i) : i * 3 + j; }
 struct MfmaConst {
   int32_t n[3];
   int32_t halo_per_cube;

@@ -205,43 +205,47 @@ __device__ __forceinline__ void load_tensor(const R* p, int stride, R (&T)[9]) {
 }
 __device__ __forceinline__ constexpr bool upper(int ij) { return (ij / 3) <= (ij % 3); }
 
-// Neighbour tensor at one facet node.  GHOST = 0 (a block without neighbour blocks): out of the
-// field, exactly load_tensor.  GHOST = 1: a lane whose neighbour lives in another block reads the
-// packed remote trace instead, which holds only the column g_i = T_i,axis of the block side's axis
-// (kernels.hip pack_one).  The other columns meet (c n)_j = 0 on such a facet, so ANY finite value
-// in their place gives the same flux bit for bit: the loads stay unconditional and only their
-// offsets differ per lane - c * 16 into a field, or into the 3-word record such that every needed
-// (i, axis) entry (or, in symmetric mode, the pair that stands for it) finds g_i:
-//   full tensor: (i, j) -> i;   pairs i <= j: axis 0 -> j, axis 1 -> i + j - 1 (clamped), axis 2 -> i.
-// `axis` is uniform over the wave (a property of class and facet).  No branch: a divergent branch
-// around the loads costs the F stages a factor two (the hand-pipelined load/MFMA interleaving is lost).
+// Neighbour stress at one facet node: only the lines the facet's scaled normal can see.  The flux is (c n)_j T_ij, and on
+// the Kuhn classes (c n) has one non-zero entry on the facets that lie on a cube face (facets 0 and 3, column a = nb_axis)
+// and two on the facets inside the cube (1 and 2); which ones is a property of (class, facet), tabulated on the host
+// and checked at create (mfma_tables.cpp mfma_trace_lines, MfmaClassConst::tr_*).  A line that only ever meets an exact
+// zero is not loaded.
+//   cube face: three loads, T[i] = T(i, a).  tl[i] = offset of that line, uniform over the wave.  GHOST = 1: a lane whose
+//     neighbour lives in another block reads the packed remote trace instead, whose record IS g_i = T(i, a) (kernels.hip
+//     pack_one): offset i.  Remote records exist on these facets only.
+//   else, symmetric storage: the six lines at their compile-time offsets, T[] = T00 T01 T02 T11 T12 T22.  Five of them
+//     are seen; picking those five takes selected offsets and a selection of the three flux rows, and measured slower
+//     than the sixth load (profiles/r10/f_trace_lines_variants.txt).
+//   else, full storage: six loads, T[3 c + i] = T(i, column c).
+// The loads stay unconditional and only their offsets are selected: a branch around them costs the F stages a factor
+// two (the hand-pipelined load/MFMA interleaving is lost).
+// (cube_face is a constant of the unrolled facet loop, not a run-time value)
 template <int SYM, int GHOST, typename R>
-__device__ __forceinline__ void load_trace(const R* p, bool ghost, int axis, R (&T)[9]) {
-  if (!GHOST) {
-    load_tensor<SYM>(p, 16, T);
-    return;
-  }
-  auto at = [&](int i, int j) {
-    int og = i;
+__device__ __forceinline__ void load_trace(const bool cube_face, const R* p, bool ghost, const int (&tl)[6], R (&T)[6]) {
+  // (full storage: the lines of a column are 3 * 16 apart - one selected base per column, compile-time offsets from there)
+  if (cube_face) {
     if (SYM) {
-      const int mid = (i + j - 1 < 0) ? 0 : (i + j - 1 > 2 ? 2 : i + j - 1);
-      og = (axis == 0) ? j : (axis == 1 ? mid : i);
-    }
-    return p[ghost ? og : (i * 3 + j) * 16];
-  };
-  if (SYM) {
-    T[0] = at(0, 0);
-    T[1] = at(0, 1);
-    T[2] = at(0, 2);
-    T[4] = at(1, 1);
-    T[5] = at(1, 2);
-    T[8] = at(2, 2);
-    T[3] = T[1];
-    T[6] = T[2];
-    T[7] = T[5];
-  } else {
 #pragma unroll
-    for (int c = 0; c < 9; ++c) T[c] = at(c / 3, c % 3);
+      for (int i = 0; i < 3; ++i) T[i] = p[GHOST ? (ghost ? i : tl[i]) : tl[i]];
+    } else {
+      const R* pa = p + ((GHOST && ghost) ? 0 : tl[0]);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) T[i] = pa[GHOST ? (ghost ? i : i * 48) : i * 48];
+    }
+  } else if (SYM) {
+    T[0] = p[0];
+    T[1] = p[1 * 16];
+    T[2] = p[2 * 16];
+    T[3] = p[4 * 16];
+    T[4] = p[5 * 16];
+    T[5] = p[8 * 16];
+  } else {
+    const R *pa = p + tl[0], *pb = p + tl[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      T[i] = pa[i * 48];
+      T[3 + i] = pb[i * 48];
+    }
   }
 }
 
@@ -464,6 +468,23 @@ __device__ __forceinline__ float ndot<float>(float c0, float c1, float c2, float
   r = __builtin_fmaf(c1, t1, r);
   r = __builtin_fmaf(c2, t2, r);
   return r;
+}
+__device__ __forceinline__ double fma_of(double a, double b, double c) { return __builtin_fma(a, b, c); }
+__device__ __forceinline__ float fma_of(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+
+// Row i of a facet's flux, wf (c n)_j T_ij, out of the lines load_trace left in T: ndot with its exactly-zero terms left
+// out - the lower column's product first, the other one added by an fma, then wf.  A term 0 * finite changes no rounding,
+// so the value is what ndot over all three columns gives (the sign of a zero may differ).  cnf: (c n) of the facet,
+// tc: its entries at the non-zero columns (MfmaClassConst::tr_cn).
+template <int SYM, typename R>
+__device__ __forceinline__ R trace_flux(const bool cube_face, int i, R wf, const R (&cnf)[3], const R (&tc)[2], const R (&T)[6]) {
+  if (cube_face) return wf * (tc[0] * T[i]);
+  if (SYM) {  // row i of the symmetric tensor in T00 T01 T02 T11 T12 T22
+    const int s0 = i, s1 = i == 0 ? 1 : (i == 1 ? 3 : 4), s2 = i == 0 ? 2 : (i == 1 ? 4 : 5);
+    return wf * ndot<R>(cnf[0], cnf[1], cnf[2], T[s0], T[s1], T[s2]);
+  }
+  const R r = tc[0] * T[i];
+  return wf * fma_of(tc[1], T[3 + i], r);
 }
 
 
@@ -1187,31 +1208,39 @@ __global__ __launch_bounds__(256, (mfma_resident_blocks<R, P>())) void mfma_stag
       //      carries +1/2 (c n).T- on interior facets and -1/2 (c n).T+ on boundary facets (which
       //      cancels the folded half): wf * (c n).T of whatever np[f] points at, the 1/2 being part
       //      of the lift tiles.
-      constexpr int PFL = sizeof(R) == 4 ? 3 : 2;  // facet k-steps of neighbour traces in flight
+      // facet k-steps of neighbour traces in flight (three in double, in the registers the unseen lines freed, leave the
+      // step where it is: profiles/r10/f_trace_lines_variants.txt)
+      constexpr int PFL = sizeof(R) == 4 ? 3 : 2;
       const R* np[4];
       R wf[4];
       int noff[4][KSF];
       bool gh[4];
-      int fax[4];
+      // the lines each facet's normal can see and (c n) at their columns (load_trace, trace_flux): wave-uniform
+      int tl[4][6];
+      R tc[4][2];
 #pragma unroll
       for (int f = 0; f < 4; ++f) {
         const NbrRef<R> NR = nbr_from_entry<ND, NF, 9>(A, nbe[f], 2 * kc.nb_axis[f] + (kc.nb_dir[f] > 0 ? 1 : 0), own);
         np[f] = NR.p;
         gh[f] = GHOST && NR.ghost;
-        fax[f] = GHOST ? kc.nb_axis[f] : 0;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) tl[f][c] = kc.tr_line[SYM ? 1 : 0][f][c];
+        tc[f][0] = (R)kc.tr_cn[f][0];
+        tc[f][1] = (R)kc.tr_cn[f][1];
         wf[f] = NR.physical ? R(-1) : R(1);
         const int var = NR.ghost ? 1 : (NR.physical ? 2 : 0);
         const nbr4 o4 = sFt[((var * 6 + k) * 4 + f) * 4 + q];
 #pragma unroll
         for (int ks = 0; ks < KSF; ++ks) noff[f][ks] = o4[ks];
       }
-      R nq[PFL][9];
+      R nq[PFL][6];
+      auto cube_face = [](int f) { return f == 0 || f == 3; };
       STAMP(sta);   // diagnostic builds: end of the neighbour set-up
       {
         constexpr int NS = 4 * KSF;
 #pragma unroll
         for (int s = 0; s < PFL; ++s)
-          load_trace<SYM, GHOST>(np[s / KSF] + noff[s / KSF][s % KSF], gh[s / KSF], fax[s / KSF], nq[s]);
+          load_trace<SYM, GHOST>(cube_face(s / KSF), np[s / KSF] + noff[s / KSF][s % KSF], gh[s / KSF], tl[s / KSF], nq[s]);
 #pragma unroll
         for (int f = 0; f < 4; ++f) {
           if (f == 1) STAMP(stb);   // diagnostic builds: end of facet 0
@@ -1221,11 +1250,10 @@ __global__ __launch_bounds__(256, (mfma_resident_blocks<R, P>())) void mfma_stag
             R fl[3];
 #pragma unroll
             for (int i = 0; i < 3; ++i)
-              fl[i] = wf[f] * ndot<R>(cnf[f][0], cnf[f][1], cnf[f][2], nq[s % PFL][i * 3 + 0], nq[s % PFL][i * 3 + 1],
-                                      nq[s % PFL][i * 3 + 2]);
+              fl[i] = trace_flux<SYM>(cube_face(f), i, wf[f], cnf[f], tc[f], nq[s % PFL]);
             if (s + PFL < NS) {
               const int f1 = (s + PFL) / KSF, k1 = (s + PFL) % KSF;
-              load_trace<SYM, GHOST>(np[f1] + noff[f1][k1], gh[f1], fax[f1], nq[s % PFL]);
+              load_trace<SYM, GHOST>(cube_face(f1), np[f1] + noff[f1][k1], gh[f1], tl[f1], nq[s % PFL]);
             }
 #pragma unroll
             for (int t = 0; t < MTT; ++t) {

@@ -354,8 +354,37 @@ MfmaConst mfma_const(const MeshDev& md) {
         kc.nfw[f][ks] = pack(md.nb_fnode[k][f], ks);
       }
     }
+    mfma_trace_lines(md, k, kc);
   }
   return c;
+}
+
+void mfma_trace_lines(const MeshDev& md, int k, MfmaClassConst& kc) {
+  for (int f = 0; f < 4; ++f) {
+    int col[2] = {-1, -1}, nnz = 0;
+    for (int j = 0; j < 3; ++j) {
+      const double c = md.cn[k][f][j];
+      if (!std::isfinite(c)) throw std::runtime_error("MFMA trace lines: a scaled normal is not finite");
+      if (c != 0.0) {
+        if (nnz < 2) col[nnz] = j;
+        nnz += 1;
+      }
+    }
+    const bool cube_face = f == 0 || f == 3;
+    const int axis = md.nb_axis[k][f];
+    const bool ok = cube_face ? (nnz == 1 && axis >= 0 && axis < 3 && col[0] == axis) : (nnz == 2 && axis < 0);
+    if (!ok)
+      throw std::runtime_error("MFMA trace lines: class " + std::to_string(k) + " facet " + std::to_string(f) + " has " + std::to_string(nnz) +
+                               " non-zero normal entries and nb_axis " + std::to_string(axis) +
+                               "; the F stage kernels need one along nb_axis on facets 0 and 3, two and no axis on facets 1 and 2");
+    for (int c = 0; c < 2; ++c) {
+      const int j = col[c] >= 0 ? col[c] : col[0];
+      kc.tr_col[f][c] = col[c];
+      kc.tr_cn[f][c] = col[c] >= 0 ? md.cn[k][f][col[c]] : 0.0;
+      for (int sym = 0; sym < 2; ++sym)
+        for (int i = 0; i < 3; ++i) kc.tr_line[sym][f][3 * c + i] = stress_line_slot(sym != 0, i, j) * 16;
+    }
+  }
 }
 
 

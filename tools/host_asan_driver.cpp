@@ -105,6 +105,97 @@ static void mfma_tables_3d(int degree) {
     }
 }
 
+// The stress lines a facet's scaled normal can see (mfma_tables.cpp mfma_trace_lines, read by kernels_mfma.hip load_trace /
+// trace_flux) on two anisotropic cell sizes: one column along nb_axis on facets 0 and 3, two on facets 1 and 2; the flux
+// formed from the listed lines alone equals the one over all three columns, in both storages, on a tensor that is not
+// symmetric in full storage; and tables that break the rule are refused.
+static void trace_lines_3d(int degree) {
+  RefElem re = make_refelem(3, degree, KIND_SIMPLEX);
+  const double hs[2][3] = {{0.3, 0.5, 0.7}, {2.0, 0.125, 0.75}};
+  auto refused = [](const MeshDev& m, int k) {
+    MfmaClassConst kc;
+    std::memset(&kc, 0, sizeof(kc));
+    try {
+      mfma_trace_lines(m, k, kc);
+    } catch (const std::runtime_error&) {
+      return true;
+    }
+    return false;
+  };
+  for (const auto& h : hs) {
+    MeshDev md;
+    std::memset(&md, 0, sizeof(md));
+    md.nd = re.nd;
+    md.nf = re.nf;
+    build_mesh_tables(3, degree, 0, h, re.fnode.data(), re.lattice.data(), md);
+    for (int k = 0; k < 6; ++k) {
+      MfmaClassConst kc;
+      std::memset(&kc, 0, sizeof(kc));
+      mfma_trace_lines(md, k, kc);
+      for (int f = 0; f < 4; ++f) {
+        const bool cube_face = f == 0 || f == 3;
+        int nnz = 0;
+        for (int j = 0; j < 3; ++j) nnz += md.cn[k][f][j] != 0.0;
+        EXPECT(nnz == (cube_face ? 1 : 2));
+        EXPECT(cube_face ? (kc.tr_col[f][0] == md.nb_axis[k][f] && kc.tr_col[f][1] == -1)
+                         : (md.nb_axis[k][f] < 0 && kc.tr_col[f][0] >= 0 && kc.tr_col[f][0] < kc.tr_col[f][1] && kc.tr_col[f][1] < 3));
+        EXPECT(cube_face ? kc.tr_cn[f][1] == 0.0 : kc.tr_cn[f][1] == md.cn[k][f][kc.tr_col[f][1]]);
+        EXPECT(kc.tr_cn[f][0] == md.cn[k][f][kc.tr_col[f][0]]);
+        for (int sym = 0; sym < 2; ++sym) {
+          double slot[9];      // a node's nine slots: full storage holds T(i, j) at i * 3 + j, symmetric only the i <= j ones
+          for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) slot[i * 3 + j] = (!sym || i <= j) ? 1.0 + 0.37 * i - 0.61 * j + 0.05 * i * j : std::nan("");
+          for (int i = 0; i < 3; ++i) {
+            double full = 0.0, part = 0.0;
+            for (int j = 0; j < 3; ++j) full = std::fma(md.cn[k][f][j], slot[stress_line_slot(sym != 0, i, j)], full);
+            for (int c = 0; c < (cube_face ? 1 : 2); ++c) {
+              const int line = kc.tr_line[sym][f][3 * c + i];
+              EXPECT(line >= 0 && line < 9 * 16 && line % 16 == 0);
+              if (line < 0 || line >= 9 * 16) continue;
+              EXPECT(line / 16 == stress_line_slot(sym != 0, i, kc.tr_col[f][c]));
+              part = std::fma(kc.tr_cn[f][c], slot[line / 16], part);
+            }
+            EXPECT(full == part && std::isfinite(part));
+          }
+          // the entries the kernels never read still point into the node
+          for (int c = 0; c < 6; ++c) EXPECT(kc.tr_line[sym][f][c] >= 0 && kc.tr_line[sym][f][c] < 9 * 16);
+        }
+      }
+    }
+    // what the kernels could not run on
+    MeshDev bad = md;
+    bad.cn[2][0][(md.nb_axis[2][0] + 1) % 3] = 1e-300;      // a second entry on a cube-face facet, however small
+    EXPECT(refused(bad, 2) && !refused(md, 2));
+    bad = md;
+    for (int j = 0; j < 3; ++j)
+      if (md.cn[1][1][j] == 0.0) bad.cn[1][1][j] = 1.0;      // a third entry on an inner facet
+    EXPECT(refused(bad, 1));
+    bad = md;
+    bad.cn[4][2][0] = bad.cn[4][2][1] = bad.cn[4][2][2] = 0.0;
+    bad.cn[4][2][1] = 1.0;                                   // one entry on an inner facet
+    EXPECT(refused(bad, 4));
+    bad = md;
+    bad.nb_axis[0][3] = -1;                                  // a cube-face facet without its axis
+    EXPECT(refused(bad, 0));
+    bad = md;
+    bad.nb_axis[5][0] = (md.nb_axis[5][0] + 1) % 3;          // the entry is not along the axis
+    EXPECT(refused(bad, 5));
+    bad = md;
+    bad.nb_axis[3][1] = 0;                                   // an inner facet that claims an axis
+    EXPECT(refused(bad, 3));
+    bad = md;
+    bad.cn[0][0][md.nb_axis[0][0]] = std::nan("");
+    EXPECT(refused(bad, 0));
+    bool whole_refused = false;
+    try {
+      (void)mfma_const(bad);
+    } catch (const std::runtime_error&) {
+      whole_refused = true;
+    }
+    EXPECT(whole_refused);
+  }
+}
+
 static void tile_tables_2d(int degree, int kind) {
   RefElem re = make_refelem(2, degree, kind);
   EXPECT(!tile2d_frags_V(re, 1.0).empty() && !tile2d_frags_V(re, -1.0).empty() && !tile2d_frags_L(re).empty());
@@ -1462,6 +1553,7 @@ int main() {
       }
   for (int degree = 1; degree <= 4; ++degree) {
     mfma_tables_3d(degree);
+    trace_lines_3d(degree);
     tile_tables_2d(degree, KIND_SIMPLEX);
     tile_tables_2d(degree, KIND_TENSOR);
   }
