@@ -304,6 +304,19 @@ static int init_launch(sg_handle* h) {
   return SG_OK;
 }
 
+// The tail of every setter of an end-of-step hook (handle.hpp StepSeries), once nothing of its own can fail any more: armed
+// tables get their device-side step counter, a zero; the host waits for whatever still reads the old tables; the new ones
+// move into the handle; the captured graphs are out of date.
+template <typename Tables>
+static int arm_hook(sg_handle* h, Tables& slot, Tables& fresh, bool armed) {
+  const int64_t zero = 0;
+  if (armed) HIPCHECK(h, fresh.ctr.upload(&zero, 1));
+  HIPCHECK(h, sync_all(h));
+  slot = std::move(fresh);
+  h->epoch += 1;
+  return SG_OK;
+}
+
 extern "C" {
 
 const char* sg_last_error(const sg_handle* h) { return h ? h->err.c_str() : g_create_err.c_str(); }
@@ -666,20 +679,16 @@ int sg_set_receivers(sg_handle* h, int64_t nrec, const double* pts, int what, in
     rt.what = what;
     rt.ncomp = pl.ncomp;
     rt.clock.every = every;
-    rt.clock.capacity = capacity;
+    rt.clock.count = capacity;
     const size_t tlen = (size_t)(capacity * rt.nown * rt.ncomp);
-    const int64_t zero = 0;
     HIPCHECK(h, rt.item.upload(pl.item.data(), pl.item.size()));
     HIPCHECK(h, rt.lane.upload(pl.lane.data(), pl.lane.size()));
     HIPCHECK(h, rt.phi.upload(pl.phi.data(), pl.phi.size()));
     if (rt.trace.alloc(tlen) != hipSuccess) return fail(h, SG_ERR_NOMEM, "sg_set_receivers: hipMalloc of the trace failed");
     HIPCHECK(h, hipMemset(rt.trace.get(), 0, std::max<size_t>(tlen, 1) * sizeof(double)));
-    HIPCHECK(h, rt.ctr.upload(&zero, 1));
     rt.row = std::move(pl.row);
   }
-  HIPCHECK(h, sync_all(h));
-  h->rec = std::move(rt);
-  h->epoch += 1;
+  if (int rc = arm_hook(h, h->rec, rt, nrec > 0)) return rc;
   if (owned) std::memcpy(owned, pl.own.data(), pl.own.size() * sizeof(int32_t));
   return SG_OK;
 }
@@ -687,7 +696,7 @@ int sg_set_receivers(sg_handle* h, int64_t nrec, const double* pts, int what, in
 int sg_get_receivers(sg_handle* h, double* out, size_t nbytes, int64_t* nsamples) {
   if (!h || !nsamples) return SG_ERR_ARG;
   const ReceiverTables& rt = h->rec;
-  const size_t want = (size_t)(rt.clock.capacity * rt.nrec * rt.ncomp) * sizeof(double);
+  const size_t want = (size_t)(rt.clock.count * rt.nrec * rt.ncomp) * sizeof(double);
   if (nbytes != want || (want > 0 && !out))
     return fail(h, SG_ERR_ARG, "sg_get_receivers: the buffer must hold capacity x nrec x ncomp doubles (" + std::to_string(want) + " bytes)");
   HIPCHECK(h, hipSetDevice(h->cfg.device));
@@ -706,7 +715,7 @@ int sg_get_receivers(sg_handle* h, double* out, size_t nbytes, int64_t* nsamples
 
 // The injectors: located, weighted and grouped by cell on the host (hostlogic.hpp injector_plan: locate_point, the rule of
 // sg_locate_points; psi from the element's Mhat^-1), uploaded into a local InjectTables.  Nothing of the handle changes here
-// but - last, once nothing else can fail - the storage mode, which a stress table that is not symmetric makes the block leave.
+// but - last, once nothing else here can fail - the storage mode, which a stress table that is not symmetric makes the block leave.
 static int build_injectors(sg_handle* h, const char* who, int64_t npts, const double* pts, int what, int64_t nsteps, const double* amp,
                            InjectTables& it, std::vector<int32_t>& own) {
   if (npts < 0 || nsteps < 0) return fail(h, SG_ERR_ARG, std::string(who) + ": npts and nsteps must be >= 0");
@@ -727,14 +736,12 @@ static int build_injectors(sg_handle* h, const char* who, int64_t npts, const do
   it.ngroups = (int64_t)pl.cell.size();
   it.what = what;
   it.ncomp = pl.ncomp;
-  it.clock.nsteps = nsteps;
-  const int64_t zero = 0;
+  it.clock.count = nsteps;
   HIPCHECK(h, it.item.upload(pl.item.data(), pl.item.size()));
   HIPCHECK(h, it.lane.upload(pl.lane.data(), pl.lane.size()));
   HIPCHECK(h, it.start.upload(pl.start.data(), pl.start.size()));
   HIPCHECK(h, it.psi.upload(pl.psi.data(), pl.psi.size()));
   HIPCHECK(h, it.amp.upload(table.data(), table.size()));
-  HIPCHECK(h, it.ctr.upload(&zero, 1));
   own = std::move(pl.own);
   if (h->sym && !injector_symmetric(pl, h->cfg.dim, what, nsteps, table))
     if (int rc = leave_sym_mode(h)) return rc;
@@ -751,9 +758,7 @@ int sg_set_injectors(sg_handle* h, int64_t npts, const double* pts, int what, in
   } else if (npts < 0 || nsteps < 0) {
     return fail(h, SG_ERR_ARG, "sg_set_injectors: npts and nsteps must be >= 0");
   }
-  HIPCHECK(h, sync_all(h));
-  h->inj = std::move(it);
-  h->epoch += 1;
+  if (int rc = arm_hook(h, h->inj, it, it.npts > 0)) return rc;
   if (owned && !own.empty()) std::memcpy(owned, own.data(), own.size() * sizeof(int32_t));
   return SG_OK;
 }
@@ -786,24 +791,19 @@ int sg_set_monitor(sg_handle* h, int64_t every, int64_t capacity, const double* 
     if (int rc = measure_prepare(h)) return rc;
     mt.armed = true;
     mt.clock.every = every;
-    mt.clock.capacity = capacity;
+    mt.clock.count = capacity;
     if (w && per_cell) HIPCHECK(h, mt.w.upload(w, (size_t)h->ncells * 3));
     if (w && !per_cell) std::memcpy(mt.w0, w, sizeof(mt.w0));
-    const int64_t zero = 0;
     if (mt.trace.alloc((size_t)capacity * 5) != hipSuccess) return fail(h, SG_ERR_NOMEM, "sg_set_monitor: hipMalloc of the trace failed");
     HIPCHECK(h, hipMemset(mt.trace.get(), 0, (size_t)capacity * 5 * sizeof(double)));
-    HIPCHECK(h, mt.ctr.upload(&zero, 1));
   }
-  HIPCHECK(h, sync_all(h));
-  h->mon = std::move(mt);
-  h->epoch += 1;
-  return SG_OK;
+  return arm_hook(h, h->mon, mt, every > 0);
 }
 
 int sg_get_monitor(sg_handle* h, double* out, size_t nbytes, int64_t* nsamples) {
   if (!h || !nsamples) return SG_ERR_ARG;
   const MonitorTables& mt = h->mon;
-  const size_t want = mt.armed ? (size_t)mt.clock.capacity * 5 * sizeof(double) : 0;
+  const size_t want = mt.armed ? (size_t)mt.clock.count * 5 * sizeof(double) : 0;
   if (nbytes != want || (want > 0 && !out))
     return fail(h, SG_ERR_ARG, "sg_get_monitor: the buffer must hold capacity x 5 doubles (" + std::to_string(want) + " bytes)");
   HIPCHECK(h, hipSetDevice(h->cfg.device));
@@ -937,7 +937,7 @@ int sg_set_spectra(sg_handle* h, int nfreq, int what, int64_t every, int64_t nsa
     sp.nfreq = nfreq;
     sp.what = what;
     sp.clock.every = every;
-    sp.clock.nsamples = nsamples;
+    sp.clock.count = nsamples;
     for (int k = 0; k < 2; ++k) {
       if (!(what & (1 << k))) continue;
       const size_t n = (size_t)2 * nfreq * h->field_alloc[fields[k]];
@@ -953,13 +953,8 @@ int sg_set_spectra(sg_handle* h, int nfreq, int what, int64_t every, int64_t nsa
       // (on the handle's stream, which the host waits for below: the legacy stream is not ordered against a non-blocking one)
       HIPCHECK(h, hipMemsetAsync(sp.acc[k].get(), 0, (size_t)2 * nfreq * h->field_alloc[fields[k]] * sizeof(double), h->stream));
     }
-    const int64_t zero = 0;
-    HIPCHECK(h, sp.ctr.upload(&zero, 1));
   }
-  HIPCHECK(h, sync_all(h));
-  h->spc = std::move(sp);
-  h->epoch += 1;
-  return SG_OK;
+  return arm_hook(h, h->spc, sp, nfreq > 0);
 }
 
 int sg_get_spectrum(sg_handle* h, int field, int freq, int part, double* host, size_t nbytes) {
@@ -977,7 +972,7 @@ int sg_get_spectrum(sg_handle* h, int field, int freq, int part, double* host, s
 
 int sg_spectra_samples(sg_handle* h, int64_t* taken) {
   if (!h || !taken) return SG_ERR_ARG;
-  *taken = h->spc.nfreq > 0 ? h->spc.clock.samples() : 0;
+  *taken = h->spc.nfreq > 0 ? h->spc.clock.capped_samples() : 0;   // the spectra run out: no more than nsamples
   return SG_OK;
 }
 

@@ -5,7 +5,7 @@
 // and, without a device or a HIP header (the CPU sanitizer build, `make host-asan`):
 //   hostapi.cpp (hostlogic.hpp)  family choice, field layout, stage table, region boxes / items, point location, receiver and injector plans;
 //                                what stepping remembers between calls: field write counts, the sponge pre-pass's state,
-//                                the source's slice at a step, the receivers', the injectors' and the spectra's clocks
+//                                the source's slice at a step, the clock of the end-of-step hooks (StepClock)
 //   sponge_tables.cpp            what sg_set_absorption derives from the nodal sigma
 //   source_tables.cpp            what the source setters derive from the caller's nodes and values
 #pragma once
@@ -104,9 +104,18 @@ struct SourceTables {
   DevBuf<int32_t> slot, idx;
 };
 
+// What each of the four end-of-step hooks - receivers, monitor, spectra, injectors (stages.cpp hooks) - keeps besides its
+// tables.  ctr serves graph replay: it is the step index of the hook's launches in a capture - they read it (the kernels'
+// Args::ctr), a one-thread launch bumps it behind them, and sg_step sets it to clock.steps before it replays: the role of
+// sg_handle::src_ctr_d for the source.  A setter puts a zero there when it arms (api.cpp arm_hook).
+struct StepSeries {
+  StepClock clock;            // every, count, steps completed since arming (hostlogic.hpp)
+  DevBuf<int64_t> ctr;
+};
+
 // The receivers of sg_set_receivers (the points of tests/explosive_source/uy.py:31-43), on the device: the owned ones'
 // cells and basis values, and the trace the recorder (kernels_recv.hip) fills at the end of every `every`-th step
-struct ReceiverTables {
+struct ReceiverTables : StepSeries {   // clock.count: the capacity of the trace
   int64_t nrec = 0;           // receivers armed (0: none; every block of a mesh is handed all of them)
   int64_t nown = 0;           // ... of which this block owns these, in the order given
   std::vector<int64_t> row;   // [nown] -> receiver index (the row of sg_get_receivers' output)
@@ -115,16 +124,12 @@ struct ReceiverTables {
   DevBuf<double> phi;         // [nown][nd] basis of the cell at the point
   int what = 0;               // bit 0: velocity (dim values), bit 1: stress (dim x dim, row-major)
   int ncomp = 0;
-  ReceiverClock clock;        // every, capacity, steps completed since arming (hostlogic.hpp)
   DevBuf<double> trace;       // [capacity][nown][ncomp]
-  // graph replay: the step index of the launches of a capture (RecvArgs::ctr), set by sg_step before it replays and
-  // bumped by a one-thread launch after the recorder (the role of sg_handle::src_ctr_d for the receivers)
-  DevBuf<int64_t> ctr;
 };
 
 // The injectors of sg_set_injectors (and, for the one launch, of sg_inject), on the device: the owned points grouped by cell
 // (hostlogic.hpp InjectorPlan), their psi, and the series that the kernel (kernels_inject.hip) adds at the end of the steps
-struct InjectTables {
+struct InjectTables : StepSeries {   // clock.count: the entries of the series, clock.every = 1
   int64_t npts = 0;           // points armed (0: none; every block of a mesh is handed all of them)
   int64_t nown = 0;           // ... of which this block owns these
   int64_t ngroups = 0;        // cells with points
@@ -135,30 +140,24 @@ struct InjectTables {
   DevBuf<double> amp;         // [nsteps][nown][ncomp]
   int what = 0;               // bit 0: velocity (dim values), bit 1: stress (dim x dim, row-major)
   int ncomp = 0;
-  InjectorClock clock;        // entries, steps completed since arming (hostlogic.hpp)
-  DevBuf<int64_t> ctr;        // graph replay: the step index of the launches of a capture (the role of ReceiverTables::ctr)
 };
 
 // The spectra of sg_set_spectra (kernels_spectra.hip), on the device: per selected field the weight table and the accumulators,
 // which have the field's own layout (double for FP32 blocks too)
-struct SpectraTables {
+struct SpectraTables : StepSeries {   // clock.count: nsamples
   int nfreq = 0;              // frequencies armed (0: none)
   int what = 0;               // bit 0: velocity, bit 1: stress
   DevBuf<double> w[2];        // [nsamples][nfreq][2] of the velocity / of the stress
   DevBuf<double> acc[2];      // [nfreq][2][field_alloc] of the velocity / of the stress
-  SpectraClock clock;         // every, nsamples, steps completed since arming (hostlogic.hpp)
-  DevBuf<int64_t> ctr;        // graph replay: the step index of the launches of a capture (the role of ReceiverTables::ctr)
   bool has(int k) const { return nfreq > 0 && (what & (1 << k)) != 0; }   // k = 0: velocity, 1: stress
 };
 
 // The monitor of sg_set_monitor and the scratch of sg_measure (kernels_measure.hip), on the device
-struct MonitorTables {
+struct MonitorTables : StepSeries {   // clock.count: the capacity of the trace
   bool armed = false;
-  MonitorClock clock;         // every, capacity, steps completed since arming (hostlogic.hpp)
   DevBuf<double> w;           // [ncells][3] per-cell weights, or empty: w0
   double w0[3] = {0.0, 0.0, 0.0};
   DevBuf<double> trace;       // [capacity][5]
-  DevBuf<int64_t> ctr;        // graph replay: the step index of the launches of a capture (the role of ReceiverTables::ctr)
 };
 // what every sample needs, built by the first sg_measure / sg_set_monitor of the handle and kept
 struct MeasureScratch {
@@ -275,16 +274,13 @@ struct sg_handle {
   // launch bumps at the end of every step (kernels.hpp SrcStep); sg_step sets it to src_step before it replays.
   // Allocated by the first source and kept.
   DevBuf<int64_t> src_ctr_d;
-  bool graph_src = false;     // the captured graphs contain the source launches
   ReceiverTables rec;
-  bool graph_rec = false;     // the captured graphs contain the recorder launches
   MonitorTables mon;
   MeasureScratch msr;
-  bool graph_mon = false;     // the captured graphs contain the monitor's launches
   InjectTables inj;
-  bool graph_inj = false;     // the captured graphs contain the injector launches
   SpectraTables spc;
-  bool graph_spc = false;     // the captured graphs contain the spectra launches
+  // whose launches the captured graphs contain: bit 0 the source's, bit 1 + k those of end-of-step hook k (stages.cpp hooks)
+  uint32_t in_graphs = 0;
   CorrelationTables cor;
   // halo
   const double* ghost[4][6] = {};

@@ -347,14 +347,11 @@ int sg_abi_version(void) { return SG_ABI_VERSION; }
 
 int sg_spectra_clock(int64_t every, int64_t nsamples, int64_t steps, int64_t more, int64_t out[4]) {
   if (!out || every < 1 || nsamples < 0 || steps < 0 || more < 0) return SG_ERR_ARG;
-  SpectraClock c;
-  c.every = every;
-  c.nsamples = nsamples;
-  c.steps = steps;
+  const StepClock c{every, nsamples, steps};
   out[0] = c.due_at(steps + 1) ? 1 : 0;
   out[1] = c.due_at(steps + 1) ? c.sample_at(steps + 1) : -1;
   out[2] = c.active() ? 1 : 0;
-  out[3] = c.samples_after(more);
+  out[3] = c.capped_samples_after(more);   // the spectra run out: no more than nsamples
   return SG_OK;
 }
 

@@ -171,22 +171,29 @@ inline SourceSlice source_slice(const SourceFacts& s, int64_t step, bool capture
   return r;
 }
 
-// The receivers' clock (seigen_hip.h sg_set_receivers): sample j is taken after step (j + 1) * every, and the trace holds
-// `capacity` samples.
-struct ReceiverClock {
-  int64_t every = 1, capacity = 0;
+// The clock of everything that runs at the end of a step (stages.cpp hooks): sample j (0-based) belongs to step (j + 1) * every
+// counted from the arming call, and there are `count` of them - the capacity of the receivers' and the monitor's trace, the
+// spectra's nsamples, the injectors' nsteps (every = 1: entry k is added at the end of step k + 1).  What happens when the
+// series is full is the hook's business, not the clock's: the receivers and the monitor refuse the step (fits, no_room_at;
+// their count of samples is the uncapped one, which the refusals keep within count), the spectra and the injectors run out
+// silently (due_at, active; their count of samples is the capped one).
+struct StepClock {
+  int64_t every = 1, count = 0;
   int64_t steps = 0;   // completed since arming
-  int64_t samples_after(int64_t n) const { return (steps + n) / every; }
+  bool due_at(int64_t s) const { return s >= 1 && s % every == 0 && s / every <= count; }   // step s (1-based) has a sample
+  int64_t sample_at(int64_t s) const { return s / every - 1; }                                 // ... this one
+  bool active() const { return (steps + every) / every <= count; }                            // ... and so has some later step
+  int64_t samples_after(int64_t n) const { return (steps + n) / every; }                      // due once n more steps are done
   int64_t samples() const { return samples_after(0); }
-  bool fits(int64_t n) const { return samples_after(n) <= capacity; }                       // n more steps
-  bool no_room_at(int64_t s) const { return s % every == 0 && s / every > capacity; }       // step s is due a sample and has none
+  int64_t capped_samples_after(int64_t n) const { return std::min(samples_after(n), count); }   // ... and taken: no more than count
+  int64_t capped_samples() const { return capped_samples_after(0); }
+  bool fits(int64_t n) const { return samples_after(n) <= count; }                          // n more steps
+  bool no_room_at(int64_t s) const { return s % every == 0 && s / every > count; }          // step s is due a sample and has none
 };
 
-// The monitor (seigen_hip.h sg_set_monitor) keeps the receivers' clock: sample j after step (j + 1) * every, `capacity`
-// samples, the same two refusals.  What its kernels read, in the order they read it (kernels_measure.hip): the dim
+// What the monitor's kernels (seigen_hip.h sg_set_monitor) read, in the order they read it (kernels_measure.hip): the dim
 // components of the velocity, then the stress's - all dim^2 of full storage, the i <= j ones of symmetric storage, where an
 // off-diagonal form counts twice; the diagonal ones also make up the trace t.
-using MonitorClock = ReceiverClock;
 struct MonitorComp {
   int comp = 0;        // index of the component in its field (velocity: i, stress: i * dim + j)
   bool stress = false, diag = false;
@@ -361,32 +368,12 @@ struct InjectorPlan {
   int ncomp = 0;                // what bit 0: velocity (dim values), bit 1: stress (dim x dim)
 };
 InjectorPlan injector_plan(const NodeGeom& G, const Layout& L, const sg::RefElem& re, int64_t npts, const double* pts, int what);
-// The injectors' clock: entry k (k = 0 .. nsteps - 1) is added at the end of step k + 1 counted from the arming call; after
-// nsteps entries nothing is added.
-struct InjectorClock {
-  int64_t nsteps = 0;
-  int64_t steps = 0;   // completed since arming
-  bool due_at(int64_t s) const { return s >= 1 && s <= nsteps; }   // step s (1-based) has an entry
-  bool active() const { return steps < nsteps; }                    // ... and so has some later step
-};
 // amp[nsteps][npts][ncomp] of the caller -> [nsteps][nown][ncomp] in the order of the plan's rows; and whether the stress part
 // (the last dim * dim of a point's ncomp values, what bit 1) of every owned point is symmetric to the bit at every step
 std::vector<double> injector_gather(const InjectorPlan& pl, int64_t npts, int64_t nsteps, const double* amp);
 bool injector_symmetric(const InjectorPlan& pl, int dim, int what, int64_t nsteps, const std::vector<double>& gathered);
 
-// The spectra (seigen_hip.h sg_set_spectra; kernels_spectra.hip) keep the receivers' rhythm and the injectors' end: sample j
-// (0-based) after step (j + 1) * every counted from the arming call, nsamples samples, after which nothing is added and
-// nothing is refused.
-struct SpectraClock {
-  int64_t every = 1, nsamples = 0;
-  int64_t steps = 0;   // completed since arming
-  bool due_at(int64_t s) const { return s >= 1 && s % every == 0 && s / every <= nsamples; }   // step s (1-based) is a sample step
-  int64_t sample_at(int64_t s) const { return s / every - 1; }                                    // ... of this sample
-  bool active() const { return (steps + every) / every <= nsamples; }                            // some later step is one
-  int64_t samples_after(int64_t n) const { return std::min((steps + n) / every, nsamples); }     // taken once n more steps are done
-  int64_t samples() const { return samples_after(0); }
-};
-// The lines c = i * dim + j of a stress word ((item * nd + a) * dim^2 + c) * gw + lane that are accumulated: all dim^2 of full
+// The spectra (seigen_hip.h sg_set_spectra; kernels_spectra.hip): the lines c = i * dim + j of a stress word ((item * nd + a) * dim^2 + c) * gw + lane that are accumulated: all dim^2 of full
 // storage, the i <= j ones of symmetric storage (the others hold no valid stress there)
 inline bool spectra_line_kept(int dim, bool sym, int c) { return !sym || c / dim <= c % dim; }
 inline std::vector<int32_t> spectra_lines(int dim, bool sym) {

@@ -1,5 +1,7 @@
 // Stage launches of the C-ABI: the choice of a stage's kernel, regions of a split stage, the six fused launches of an LF4 step
 // (seigen/elastic.py:283-313), hipGraph replay, un-fused operator applications, halo packs, timing.
+#include <array>
+
 #include "handle.hpp"
 
 // ---- stage launches --------------------------------------------------------------------
@@ -9,10 +11,7 @@
 struct LaunchCtx {
   hipStream_t stream;                 // the stream of this launch and of what belongs to it (pre-pass, source)
   bool capture_src = false;           // a capture: slice and weight of the source come from the device-side counter src_ctr_d ...
-  bool capture_rec = false;           // ... and the recorder's step from rec.ctr
-  bool capture_mon = false;           // ... and the monitor's from mon.ctr
-  bool capture_inj = false;           // ... and the injectors' from inj.ctr (a series that has run out: no launch)
-  bool capture_spc = false;           // ... and the spectra's from spc.ctr (likewise)
+  bool capture = false;               // ... and the step of every armed end-of-step hook from its own counter (StepSeries::ctr)
 };
 
 // the source at the handle's step (hostlogic.hpp source_slice), with the device pointers of a capture's SrcStep
@@ -327,7 +326,7 @@ int queue_inject(sg_handle* h, hipStream_t stream, const InjectTables& it, const
   std::memset(&a, 0, sizeof(a));
   a.ctr = ctr;
   a.step = step;
-  a.nsteps = it.clock.nsteps;
+  a.nsteps = it.clock.count;
   a.item = it.item.get();
   a.lane = it.lane.get();
   a.start = it.start.get();
@@ -410,41 +409,29 @@ int sg_run_stage(sg_handle* h, int stage, int region) {
   return SG_OK;
 }
 
-// The end of a step for the receivers (sg_set_receivers): the recorder samples u1 and s1 of the step that just ended, on
-// the main stream behind stage S1's SECOND launch.  Eager launches name the step by value and count it here; the launches
-// of a capture read it from rec.ctr and bump that (sg_step sets it before it replays and counts the replayed steps).
-// SG_ERR_STATE, nothing queued and nothing counted: the step is due a sample the trace has no room for.
-static int record_step(sg_handle* h, const LaunchCtx& ctx) {
-  ReceiverTables& rt = h->rec;
-  if (rt.nrec == 0) return SG_OK;
-  const int64_t step = rt.clock.steps + 1;
-  if (!ctx.capture_rec && rt.clock.no_room_at(step))
-    return fail(h, SG_ERR_STATE, "receiver trace full: read it out (sg_get_receivers) and re-arm before stepping on");
-  if (rt.nown > 0) {
-    if (int rc = join_second(h)) return rc;
-    RecvArgs a;
-    std::memset(&a, 0, sizeof(a));
-    a.ctr = ctx.capture_rec ? rt.ctr.get() : nullptr;
-    a.step = step;
-    a.every = rt.clock.every;
-    a.capacity = rt.clock.capacity;
-    a.item = rt.item.get();
-    a.lane = rt.lane.get();
-    a.phi = rt.phi.get();
-    a.trace = rt.trace.get();
-    a.nown = rt.nown;
-    a.ncomp = rt.ncomp;
-    a.nu = (rt.what & 1) ? h->cfg.dim : 0;
-    a.dim = h->cfg.dim;
-    a.nd = h->re.nd;
-    a.gw = (int32_t)h->md.gw;
-    a.sym = h->sym ? 1 : 0;
-    if (launch_receivers(h->field.read(SG_FIELD_U), h->field.read(SG_FIELD_S), a, h->f32, ctx.stream) != 0)
-      return fail(h, SG_ERR_DEVICE, "receiver launch failed");
-    if (ctx.capture_rec && launch_step_counter(rt.ctr.get(), 1, 1, ctx.stream) != 0)
-      return fail(h, SG_ERR_DEVICE, "step counter launch failed");
-  }
-  if (!ctx.capture_rec) rt.clock.steps = step;
+// One launch of the recorder (kernels_recv.hip) on `stream`: u1 and s1 as they stand there at the owned receivers, into the
+// trace's sample of the step (by value, or *ctr + 1) when that is a sample step.
+static int queue_receivers(sg_handle* h, hipStream_t stream, const int64_t* ctr, int64_t step) {
+  const ReceiverTables& rt = h->rec;
+  RecvArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.ctr = ctr;
+  a.step = step;
+  a.every = rt.clock.every;
+  a.capacity = rt.clock.count;
+  a.item = rt.item.get();
+  a.lane = rt.lane.get();
+  a.phi = rt.phi.get();
+  a.trace = rt.trace.get();
+  a.nown = rt.nown;
+  a.ncomp = rt.ncomp;
+  a.nu = (rt.what & 1) ? h->cfg.dim : 0;
+  a.dim = h->cfg.dim;
+  a.nd = h->re.nd;
+  a.gw = (int32_t)h->md.gw;
+  a.sym = h->sym ? 1 : 0;
+  if (launch_receivers(h->field.read(SG_FIELD_U), h->field.read(SG_FIELD_S), a, h->f32, stream) != 0)
+    return fail(h, SG_ERR_DEVICE, "receiver launch failed");
   return SG_OK;
 }
 
@@ -486,44 +473,14 @@ static int queue_measure(sg_handle* h, hipStream_t stream, const double* w_cells
   return SG_OK;
 }
 
-// The end of a step for the monitor (sg_set_monitor), by the receivers' rules (record_step): the sample of u1 and s1 on the
-// main stream behind stage S1's SECOND launch; eager launches name the step by value and count it here, the launches of a
-// capture read it from mon.ctr and bump that.  No room for the sample: end_of_step refuses before anything is queued.
-static bool monitor_no_room(const sg_handle* h, const LaunchCtx& ctx) {
-  return h->mon.armed && !ctx.capture_mon && h->mon.clock.no_room_at(h->mon.clock.steps + 1);
+// ... of the armed monitor (sg_set_monitor), into its trace
+static int queue_monitor(sg_handle* h, hipStream_t stream, const int64_t* ctr, int64_t step) {
+  const MonitorTables& mt = h->mon;
+  return queue_measure(h, stream, mt.w.get(), mt.w0, ctr, step, mt.clock.every, mt.clock.count, mt.trace.get());
 }
-static int monitor_step(sg_handle* h, const LaunchCtx& ctx) {
-  MonitorTables& mt = h->mon;
-  if (!mt.armed) return SG_OK;
-  const int64_t step = mt.clock.steps + 1;
-  if (int rc = join_second(h)) return rc;
-  if (int rc = queue_measure(h, ctx.stream, mt.w.get(), mt.w0, ctx.capture_mon ? mt.ctr.get() : nullptr, step, mt.clock.every,
-                             mt.clock.capacity, mt.trace.get()))
-    return rc;
-  if (ctx.capture_mon && launch_step_counter(mt.ctr.get(), 1, 1, ctx.stream) != 0)
-    return fail(h, SG_ERR_DEVICE, "step counter launch failed");
-  if (!ctx.capture_mon) mt.clock.steps = step;
-  return SG_OK;
-}
-
-// The end of a step for the injectors (sg_set_injectors), behind the recorder and the monitor, which have sampled the step:
-// entry `steps` of the series is added to u1 / s1 and belongs to the step that follows.  Eager launches name the step by value,
-// count it here and launch nothing once the series has run out; the launches of a capture read the step from inj.ctr and bump
-// that (a step beyond the series: the threads exit at once), and a capture counts nothing.
-static int inject_step(sg_handle* h, const LaunchCtx& ctx) {
-  InjectTables& it = h->inj;
-  if (it.npts == 0) return SG_OK;
-  const int64_t step = it.clock.steps + 1;
-  // (a capture counts nothing, so active() holds for all of its steps: the graphs have the launches or have none, ensure_graphs)
-  const bool launch = ctx.capture_inj ? it.clock.active() : it.clock.due_at(step);
-  if (it.nown > 0 && launch) {
-    if (int rc = join_second(h)) return rc;
-    if (int rc = queue_inject(h, ctx.stream, it, ctx.capture_inj ? it.ctr.get() : nullptr, step)) return rc;
-    if (ctx.capture_inj && launch_step_counter(it.ctr.get(), 1, 1, ctx.stream) != 0)
-      return fail(h, SG_ERR_DEVICE, "step counter launch failed");
-  }
-  if (!ctx.capture_inj) it.clock.steps = step;
-  return SG_OK;
+// the armed injectors' launch (sg_set_injectors): entry step - 1 of their series, which belongs to the step that follows
+static int queue_injectors(sg_handle* h, hipStream_t stream, const int64_t* ctr, int64_t step) {
+  return queue_inject(h, stream, h->inj, ctr, step);
 }
 
 // One launch of the spectra kernel per selected field (kernels_spectra.hip) on `stream`: the fields as they stand there enter
@@ -538,7 +495,7 @@ static int queue_spectra(sg_handle* h, hipStream_t stream, const int64_t* ctr, i
     a.ctr = ctr;
     a.step = step;
     a.every = sp.clock.every;
-    a.nsamples = sp.clock.nsamples;
+    a.nsamples = sp.clock.count;
     a.w = sp.w[k].get();
     a.acc = sp.acc[k].get();
     a.n = (int64_t)h->field_alloc[fields[k]];
@@ -554,48 +511,73 @@ static int queue_spectra(sg_handle* h, hipStream_t stream, const int64_t* ctr, i
   return SG_OK;
 }
 
-// The end of a step for the spectra (sg_set_spectra), behind the recorder and the monitor and before the injectors: the sample
-// is of u1 and s1 of the step that just ended, without the entry the injectors add for the next one.  By the injectors' rules:
-// eager launches name the step by value, count it here and launch nothing on a step that is no sample step or once the
-// series has run out; the launches of a capture read the step from spc.ctr and bump that, and a capture counts nothing.
-static int spectra_step(sg_handle* h, const LaunchCtx& ctx) {
-  SpectraTables& sp = h->spc;
-  if (sp.nfreq == 0) return SG_OK;
-  const int64_t step = sp.clock.steps + 1;
-  const bool launch = ctx.capture_spc ? sp.clock.active() : sp.clock.due_at(step);
-  if (launch) {
+// What runs at the end of every step, on the main stream behind stage S1's SECOND launch, as values: the hooks in the order
+// they run.  The receivers' recorder and the monitor sample u1 and s1 of the step that just ended, and so do the spectra -
+// before the injectors add the entry that belongs to the step that follows.  All four keep one protocol (hook_step, and the
+// callers that walk this table); they differ in what stands here.
+struct Hook {
+  StepSeries* series;   // the clock and the device-side step counter
+  bool armed;           // a disarmed hook does nothing and counts nothing
+  bool has_launches;    // on this block (the points of the receivers and the injectors have one owner); steps count on every block
+  // a full series - true: refuses the step (end_of_step, check_room), and the hook launches at every step: its kernel tells
+  // the sample steps; false: has run out silently, and the hook launches at the due steps only
+  bool refuses;
+  const char* name;     // ... and what a refusal calls the trace and
+  const char* getter;   // ... the call that reads it out
+  int (*queue)(sg_handle* h, hipStream_t stream, const int64_t* ctr, int64_t step);   // the step by value, or *ctr + 1
+  uint32_t bit;         // in sg_handle::in_graphs
+};
+using Hooks = std::array<Hook, 4>;
+static Hooks hooks(sg_handle* h) {
+  return {{{&h->rec, h->rec.nrec > 0, h->rec.nown > 0, true, "receiver", "sg_get_receivers", queue_receivers, 2u << 0},
+           {&h->mon, h->mon.armed, true, true, "monitor", "sg_get_monitor", queue_monitor, 2u << 1},
+           {&h->spc, h->spc.nfreq > 0, true, false, "", "", queue_spectra, 2u << 2},
+           {&h->inj, h->inj.npts > 0, h->inj.nown > 0, false, "", "", queue_injectors, 2u << 3}}};
+}
+
+// The end of a step for one hook.  Eager launches name the step by value and count it here; the launches of a capture read
+// it from the hook's counter and bump that, and a capture counts nothing (sg_step sets the counter before it replays and
+// counts the replayed steps) - so active() holds for all of a capture's steps: the graphs have a run-out hook's launches, the
+// kernel's threads exiting at once beyond the series, or have none (ensure_graphs).
+static int hook_step(sg_handle* h, const LaunchCtx& ctx, const Hook& k) {
+  if (!k.armed) return SG_OK;
+  StepClock& c = k.series->clock;
+  const int64_t step = c.steps + 1;
+  const bool launch = k.refuses || (ctx.capture ? c.active() : c.due_at(step));
+  if (k.has_launches && launch) {
     if (int rc = join_second(h)) return rc;
-    if (int rc = queue_spectra(h, ctx.stream, ctx.capture_spc ? sp.ctr.get() : nullptr, step)) return rc;
-    if (ctx.capture_spc && launch_step_counter(sp.ctr.get(), 1, 1, ctx.stream) != 0)
+    if (int rc = k.queue(h, ctx.stream, ctx.capture ? k.series->ctr.get() : nullptr, step)) return rc;
+    if (ctx.capture && launch_step_counter(k.series->ctr.get(), 1, 1, ctx.stream) != 0)
       return fail(h, SG_ERR_DEVICE, "step counter launch failed");
   }
-  if (!ctx.capture_spc) sp.clock.steps = step;
+  if (!ctx.capture) c.steps = step;
   return SG_OK;
 }
 
-// what ends a step on the stream: the receivers' recorder, then the monitor, then the spectra, then the injectors.  A refusal
-// of the first two (no room for the sample) is found before anything is queued or counted; a launch error of a later one
-// leaves the earlier ones' step counted
+// What ends a step on the stream: the hooks in their order.  A refusal (no room for the step's sample) is found before
+// anything is queued or counted - where two traces are full the later hook's, the monitor's, is reported; a launch error of
+// a later hook leaves the earlier ones' step counted.  A capture refuses nothing: sg_step has checked its steps (check_room).
 static int end_of_step(sg_handle* h, const LaunchCtx& ctx) {
-  if (monitor_no_room(h, ctx))
-    return fail(h, SG_ERR_STATE, "monitor trace full: read it out (sg_get_monitor) and re-arm before stepping on");
-  if (int rc = record_step(h, ctx)) return rc;
-  if (int rc = monitor_step(h, ctx)) return rc;
-  if (int rc = spectra_step(h, ctx)) return rc;
-  return inject_step(h, ctx);
+  const Hooks hs = hooks(h);
+  for (auto it = hs.rbegin(); it != hs.rend() && !ctx.capture; ++it) {
+    const Hook& k = *it;
+    if (k.armed && k.refuses && k.series->clock.no_room_at(k.series->clock.steps + 1))
+      return fail(h, SG_ERR_STATE, std::string(k.name) + " trace full: read it out (" + k.getter + ") and re-arm before stepping on");
+  }
+  for (const Hook& k : hs)
+    if (int rc = hook_step(h, ctx, k)) return rc;
+  return SG_OK;
 }
 
-// The bookkeeping of n finished steps.  Eager stage launches and record_step have counted themselves; replayed steps
+// The bookkeeping of n finished steps.  Eager stage launches and hook_step have counted themselves; replayed steps
 // count here, and what a replay wrote is new to everything that remembers a field state.
 static void steps_done(sg_handle* h, int64_t n, bool replayed) {
   h->src_step += n;
   h->counters.steps += n;
   if (!replayed) return;
   for (int st = 0; st < 6; ++st) h->counters.launches[st] += n;
-  if (h->rec.nrec > 0) h->rec.clock.steps += n;
-  if (h->mon.armed) h->mon.clock.steps += n;
-  if (h->inj.npts > 0) h->inj.clock.steps += n;
-  if (h->spc.nfreq > 0) h->spc.clock.steps += n;
+  for (const Hook& k : hooks(h))
+    if (k.armed) k.series->clock.steps += n;
   h->field.replayed();
   h->sponge.pre_state.forget();
 }
@@ -640,7 +622,7 @@ static hipGraphExec_t capture_steps(sg_handle* h, int steps, bool with_src) {
   }
   if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) return nullptr;
   int rc = SG_OK;
-  const LaunchCtx ctx{h->stream, with_src, h->rec.nrec > 0, h->mon.armed, h->inj.npts > 0, h->spc.nfreq > 0};
+  const LaunchCtx ctx{h->stream, with_src, true};
   h->sponge.pre_state.forget();      // a replay starts from whatever the buffer holds: the captured step computes its own
   for (int k = 0; k < steps && rc == SG_OK; ++k) rc = enqueue_step(h, ctx, false);
   h->sponge.pre_state.forget();      // nothing was launched: the buffer does not hold what the capture asked for
@@ -653,42 +635,35 @@ static hipGraphExec_t capture_steps(sg_handle* h, int steps, bool with_src) {
   return ge;
 }
 
-// the receivers' samples of all nsteps steps must fit the trace: checked before anything is queued (native exchange too)
-static int check_receiver_room(sg_handle* h, int64_t nsteps) {
-  const ReceiverClock& c = h->rec.clock;
-  if (h->rec.nrec == 0 || c.fits(nsteps)) return SG_OK;
-  return fail(h, SG_ERR_STATE, "sg_step: the receiver trace has room for " + std::to_string(c.capacity - c.samples()) +
-                                   " more samples, these steps take " + std::to_string(c.samples_after(nsteps) - c.samples()));
-}
-// ... and the monitor's
-static int check_monitor_room(sg_handle* h, int64_t nsteps) {
-  const MonitorClock& c = h->mon.clock;
-  if (!h->mon.armed || c.fits(nsteps)) return SG_OK;
-  return fail(h, SG_ERR_STATE, "sg_step: the monitor trace has room for " + std::to_string(c.capacity - c.samples()) +
-                                   " more samples, these steps take " + std::to_string(c.samples_after(nsteps) - c.samples()));
+// The samples of all nsteps steps must fit the trace of every hook that refuses: checked before anything is queued (native
+// exchange too).
+static int check_room(sg_handle* h, int64_t nsteps) {
+  for (const Hook& k : hooks(h)) {
+    const StepClock& c = k.series->clock;
+    if (!k.armed || !k.refuses || c.fits(nsteps)) continue;
+    return fail(h, SG_ERR_STATE, std::string("sg_step: the ") + k.name + " trace has room for " + std::to_string(c.count - c.samples()) +
+                                     " more samples, these steps take " + std::to_string(c.samples_after(nsteps) - c.samples()));
+  }
+  return SG_OK;
 }
 
-// The graphs of one and of eight steps, captured again when a setter changed kernel arguments (epoch) or the source or the
-// receivers came or went.  A source that is still active is part of them: its launches take the step's slice and weight from
-// a device-side counter (kernels.hpp SrcStep); one that has run out, or none: no source launches.  Armed receivers likewise.
+// The graphs of one and of eight steps, captured again when a setter changed kernel arguments (epoch) or the source or a hook
+// came or went.  A source that is still active is part of them: its launches take the step's slice and weight from a
+// device-side counter (kernels.hpp SrcStep); one that has run out, or none: no source launches.  An armed hook likewise,
+// while its series has a step to come (a hook that refuses always has: a full trace stops the stepping).
 static int ensure_graphs(sg_handle* h) {
-  const bool with_src = source_at(h, false).active, with_rec = h->rec.nrec > 0, with_mon = h->mon.armed;
-  const bool with_inj = h->inj.npts > 0 && h->inj.clock.active();   // a series that has run out: no injector launches
-  const bool with_spc = h->spc.nfreq > 0 && h->spc.clock.active();  // ... and no spectra launches
+  const bool with_src = source_at(h, false).active;
   if (with_src && !h->src_ctr_d.get()) return fail(h, SG_ERR_STATE, "source without a device-side step counter");
-  if (h->graph_epoch == h->epoch && h->graph_src == with_src && h->graph_rec == with_rec && h->graph_mon == with_mon &&
-      h->graph_inj == with_inj && h->graph_spc == with_spc)
-    return SG_OK;
+  uint32_t with = with_src ? 1u : 0u;
+  for (const Hook& k : hooks(h))
+    if (k.armed && (k.refuses || k.series->clock.active())) with |= k.bit;
+  if (h->graph_epoch == h->epoch && h->in_graphs == with) return SG_OK;
   if (h->graph1) (void)hipGraphExecDestroy(h->graph1);
   if (h->graph8) (void)hipGraphExecDestroy(h->graph8);
   h->graph1 = capture_steps(h, 1, with_src);
   h->graph8 = h->graph1 ? capture_steps(h, 8, with_src) : nullptr;
   h->graph_epoch = h->epoch;
-  h->graph_src = with_src;
-  h->graph_rec = with_rec;
-  h->graph_mon = with_mon;
-  h->graph_inj = with_inj;
-  h->graph_spc = with_spc;
+  h->in_graphs = with;
   if (!h->graph1 || !h->graph8) h->graph_ok = false;  // same kernels, launched one by one (eager_steps)
   return SG_OK;
 }
@@ -696,16 +671,12 @@ static int ensure_graphs(sg_handle* h) {
 // nsteps steps as graph replays; the device-side counters start from the step the replay starts from
 static int replay_steps(sg_handle* h, int64_t nsteps) {
   // (tile path: the counter is bumped by the launch that OPENS a step, so it starts one short)
-  if (h->graph_src && launch_step_counter(h->src_ctr_d.get(), h->src_step - (h->src.fused ? 1 : 0), 0, h->stream) != 0)
+  if ((h->in_graphs & 1u) && launch_step_counter(h->src_ctr_d.get(), h->src_step - (h->src.fused ? 1 : 0), 0, h->stream) != 0)
     return fail(h, SG_ERR_DEVICE, "step counter launch failed");
-  if (h->rec.nown > 0 && launch_step_counter(h->rec.ctr.get(), h->rec.clock.steps, 0, h->stream) != 0)
-    return fail(h, SG_ERR_DEVICE, "step counter launch failed");
-  if (h->mon.armed && launch_step_counter(h->mon.ctr.get(), h->mon.clock.steps, 0, h->stream) != 0)
-    return fail(h, SG_ERR_DEVICE, "step counter launch failed");
-  if (h->graph_inj && h->inj.nown > 0 && launch_step_counter(h->inj.ctr.get(), h->inj.clock.steps, 0, h->stream) != 0)
-    return fail(h, SG_ERR_DEVICE, "step counter launch failed");
-  if (h->graph_spc && launch_step_counter(h->spc.ctr.get(), h->spc.clock.steps, 0, h->stream) != 0)
-    return fail(h, SG_ERR_DEVICE, "step counter launch failed");
+  // a hook that is in the graphs and has launches there (each a word of its own: the order of these launches is the table's)
+  for (const Hook& k : hooks(h))
+    if ((h->in_graphs & k.bit) && k.has_launches && launch_step_counter(k.series->ctr.get(), k.series->clock.steps, 0, h->stream) != 0)
+      return fail(h, SG_ERR_DEVICE, "step counter launch failed");
   int64_t k = 0;
   for (; k + 8 <= nsteps; k += 8) HIPCHECK(h, hipGraphLaunch(h->graph8, h->stream));
   for (; k < nsteps; ++k) HIPCHECK(h, hipGraphLaunch(h->graph1, h->stream));
@@ -724,8 +695,7 @@ static int eager_steps(sg_handle* h, int64_t nsteps) {
 int sg_step(sg_handle* h, int64_t nsteps) {
   if (!h || nsteps < 0) return SG_ERR_ARG;
   if (!h->params_set) return fail(h, SG_ERR_STATE, "sg_set_params must be called before stepping");
-  if (int rc = check_receiver_room(h, nsteps)) return rc;
-  if (int rc = check_monitor_room(h, nsteps)) return rc;
+  if (int rc = check_room(h, nsteps)) return rc;
   HIPCHECK(h, hipSetDevice(h->cfg.device));
   for (int s = 0; s < 6; ++s)
     if (h->md.has_nbr[s]) {

@@ -856,7 +856,7 @@ static void receiver_plans(int dim, int diagonal, int degree) {
   for (int64_t k = 0; k < np; ++k) EXPECT(owners[(size_t)k] == (cell1[(size_t)k] >= 0 ? 1 : 0));
 }
 
-// The injectors' host half (hostapi.cpp injector_plan, injector_gather, injector_symmetric; hostlogic.hpp InjectorClock) on
+// The injectors' host half (hostapi.cpp injector_plan, injector_gather, injector_symmetric; hostlogic.hpp StepClock) on
 // the split of receiver_plans(), every point listed twice more so that cells hold several points in interleaved order: the
 // owners are locate_point's, the groups are the cells in ascending order, a cell's rows keep the order given (the order of
 // the kernel's sum), item and lane are the cell's in every layout, psi is sg_injector_weights' and has the delta property
@@ -974,8 +974,8 @@ static void injector_plans(int dim, int diagonal, int degree) {
   }
   for (int64_t k = 0; k < np; ++k) EXPECT(owners[(size_t)k] == (wcell[(size_t)k] >= 0 ? 1 : 0));
   // the clock: entry k at the end of step k + 1, nothing after nsteps
-  InjectorClock c;
-  c.nsteps = 3;
+  StepClock c;   // every = 1
+  c.count = 3;
   EXPECT(!c.due_at(0) && c.due_at(1) && c.due_at(3) && !c.due_at(4) && c.active());
   c.steps = 3;
   EXPECT(!c.active());
@@ -1081,7 +1081,7 @@ static void stage_table() {
   for (int k = 0; k < 6; ++k) std::printf("stage %d: %d %d\n", k, lf4_stage_input(k), lf4_stage_output(k));
 }
 
-// What stepping remembers between calls (hostlogic.hpp FieldVersions, PrePass, source_slice, ReceiverClock, MonitorClock), against models
+// What stepping remembers between calls (hostlogic.hpp FieldVersions, PrePass, source_slice, StepClock), against models
 // written out here that share nothing with them.
 //
 // The pre-pass: the model gives every field a content id, raised whenever a launch or an upload writes the field, and tags the
@@ -1286,9 +1286,9 @@ static void stepping_state() {
   for (int64_t every : {1, 2, 5})
     for (int64_t capacity : {0, 1, 3})
       for (int64_t call = 1; call <= 7; ++call) {
-        ReceiverClock c;
+        StepClock c;
         c.every = every;
-        c.capacity = capacity;
+        c.count = capacity;
         int64_t done = 0;      // the model: steps completed, and the multiples of `every` among 1..done counted one by one
         auto multiples = [&](int64_t upto) {
           int64_t n = 0;
@@ -1323,9 +1323,9 @@ static void stepping_state() {
   for (int64_t every : {1, 3, 4})
     for (int64_t capacity : {1, 2, 5})
       for (int64_t call : {1, 2, 11}) {
-        MonitorClock c;
+        StepClock c;
         c.every = every;
-        c.capacity = capacity;
+        c.count = capacity;
         std::vector<int> taken((size_t)capacity, 0);
         auto step_done = [&](int64_t s) {     // what the kernels do with step s (kernels_measure.hip sample_index)
           if (s % every != 0) return;
@@ -1487,7 +1487,7 @@ static void correlation_compatibility() {
   b = a; b.degree = 3; b.dtype = 1; named(b, 64, "degree");
 }
 
-// The spectra's clock and line list (hostlogic.hpp SpectraClock, spectra_lines; sg_spectra_clock, sg_spectra_lines) against
+// The spectra's clock and line list (hostlogic.hpp StepClock, spectra_lines; sg_spectra_clock, sg_spectra_lines) against
 // the list of sample steps written out: sample j after step (j + 1) * every, nsamples of them.
 static void spectra_clock_and_lines() {
   for (int64_t every : {1, 2, 3, 5})
@@ -1495,9 +1495,9 @@ static void spectra_clock_and_lines() {
       std::vector<int64_t> at;
       for (int64_t j = 0; j < nsamples; ++j) at.push_back((j + 1) * every);
       for (int64_t steps = 0; steps < 24; ++steps) {
-        SpectraClock c;
+        StepClock c;
         c.every = every;
-        c.nsamples = nsamples;
+        c.count = nsamples;
         c.steps = steps;
         const auto hit = std::find(at.begin(), at.end(), steps + 1);
         EXPECT(c.due_at(steps + 1) == (hit != at.end()));
@@ -1505,7 +1505,7 @@ static void spectra_clock_and_lines() {
         EXPECT(c.active() == (!at.empty() && at.back() > steps));
         for (int64_t more : {0, 1, 7}) {
           const int64_t taken = std::count_if(at.begin(), at.end(), [&](int64_t s) { return s <= steps + more; });
-          EXPECT(c.samples_after(more) == taken);
+          EXPECT(c.capped_samples_after(more) == taken);
           int64_t out[4] = {-9, -9, -9, -9};
           EXPECT(sg_spectra_clock(every, nsamples, steps, more, out) == SG_OK);
           EXPECT(out[0] == (hit != at.end() ? 1 : 0) && out[1] == (hit != at.end() ? hit - at.begin() : -1));
