@@ -305,13 +305,16 @@ static int init_launch(sg_handle* h) {
 }
 
 // The tail of every setter of an end-of-step hook (handle.hpp StepSeries), once nothing of its own can fail any more: armed
-// tables get their device-side step counter, a zero; the host waits for whatever still reads the old tables; the new ones
-// move into the handle; the captured graphs are out of date.
+// tables get their device-side step counter, a zero; the host waits for whatever still reads the old tables; a table that is
+// not symmetric makes the block leave symmetric storage - the last step that can fail, and it fails before the mode changes;
+// the new ones move into the handle; the captured graphs are out of date.
 template <typename Tables>
-static int arm_hook(sg_handle* h, Tables& slot, Tables& fresh, bool armed) {
+static int arm_hook(sg_handle* h, Tables& slot, Tables& fresh, bool armed, bool leave_sym = false) {
   const int64_t zero = 0;
   if (armed) HIPCHECK(h, fresh.ctr.upload(&zero, 1));
   HIPCHECK(h, sync_all(h));
+  if (leave_sym)
+    if (int rc = leave_sym_mode(h)) return rc;
   slot = std::move(fresh);
   h->epoch += 1;
   return SG_OK;
@@ -558,7 +561,9 @@ int sg_set_absorption(sg_handle* h, const double* sigma_nodes, int sigma_degree)
     }
     if (!pl.sig.empty()) up(sp.sigma, pl.sig);
     up(sp.B, pl.B);
-    if (e != hipSuccess) return fail(h, SG_ERR_NOMEM, "sg_set_absorption: hipMalloc / upload of the sponge tables failed");
+    if (e != hipSuccess)
+      return fail(h, e == hipErrorOutOfMemory ? SG_ERR_NOMEM : SG_ERR_DEVICE,
+                  std::string("sg_set_absorption: hipMalloc / upload of the sponge tables failed: ") + hipGetErrorString(e));
   }
   HIPCHECK(h, sync_all(h));
   h->sponge = std::move(sp);
@@ -573,6 +578,8 @@ int sg_set_absorption(sg_handle* h, const double* sigma_nodes, int sigma_degree)
 static int set_source(sg_handle* h, int64_t nnz, const int64_t* nodes, int64_t nsteps, const double* values, const double* weights) {
   HIPCHECK(h, hipSetDevice(h->cfg.device));
   SourceTables src;
+  DevBuf<int64_t> ctr;        // the device-side step counter, where the handle has none yet
+  bool leave_sym = false;
   if (nnz != 0 && nsteps != 0) {
     if (!nodes || !values || nsteps < -1) return SG_ERR_ARG;
     SourceRequest rq;
@@ -607,14 +614,15 @@ static int set_source(sg_handle* h, int64_t nnz, const int64_t* nodes, int64_t n
     }
     if (!h->src_ctr_d.get()) {   // device-side step counter for graph replay (stages.cpp sg_step), kept across sources
       const int64_t zero = 0;
-      HIPCHECK(h, h->src_ctr_d.upload(&zero, 1));
+      HIPCHECK(h, ctr.upload(&zero, 1));
     }
-    if (h->sym && !pl.symmetric) {
-      int rc = leave_sym_mode(h);
-      if (rc != SG_OK) return rc;
-    }
+    leave_sym = h->sym && !pl.symmetric;
   }
   HIPCHECK(h, sync_all(h));
+  // (the last step that can fail, and it fails before the storage mode changes)
+  if (leave_sym)
+    if (int rc = leave_sym_mode(h)) return rc;
+  if (ctr.get()) h->src_ctr_d = std::move(ctr);
   h->src = std::move(src);
   h->src_step = 0;
   h->epoch += 1;
@@ -714,10 +722,11 @@ int sg_get_receivers(sg_handle* h, double* out, size_t nbytes, int64_t* nsamples
 }
 
 // The injectors: located, weighted and grouped by cell on the host (hostlogic.hpp injector_plan: locate_point, the rule of
-// sg_locate_points; psi from the element's Mhat^-1), uploaded into a local InjectTables.  Nothing of the handle changes here
-// but - last, once nothing else here can fail - the storage mode, which a stress table that is not symmetric makes the block leave.
+// sg_locate_points; psi from the element's Mhat^-1), uploaded into a local InjectTables.  Nothing of the handle changes here:
+// leave_sym tells the caller that the stress table is not symmetric and the block has to leave symmetric storage - which the
+// caller does once nothing else of its own can fail (a failed call leaves the handle as it was, the storage mode included).
 static int build_injectors(sg_handle* h, const char* who, int64_t npts, const double* pts, int what, int64_t nsteps, const double* amp,
-                           InjectTables& it, std::vector<int32_t>& own) {
+                           InjectTables& it, std::vector<int32_t>& own, bool& leave_sym) {
   if (npts < 0 || nsteps < 0) return fail(h, SG_ERR_ARG, std::string(who) + ": npts and nsteps must be >= 0");
   if (what < 1 || what > 3) return fail(h, SG_ERR_ARG, std::string(who) + ": what must be 1 (velocity), 2 (stress) or 3");
   if (!pts || !amp) return fail(h, SG_ERR_ARG, std::string(who) + ": no points or no amplitudes");
@@ -743,8 +752,7 @@ static int build_injectors(sg_handle* h, const char* who, int64_t npts, const do
   HIPCHECK(h, it.psi.upload(pl.psi.data(), pl.psi.size()));
   HIPCHECK(h, it.amp.upload(table.data(), table.size()));
   own = std::move(pl.own);
-  if (h->sym && !injector_symmetric(pl, h->cfg.dim, what, nsteps, table))
-    if (int rc = leave_sym_mode(h)) return rc;
+  leave_sym = h->sym && !injector_symmetric(pl, h->cfg.dim, what, nsteps, table);
   return SG_OK;
 }
 
@@ -753,12 +761,13 @@ int sg_set_injectors(sg_handle* h, int64_t npts, const double* pts, int what, in
   HIPCHECK(h, hipSetDevice(h->cfg.device));
   InjectTables it;
   std::vector<int32_t> own;
+  bool leave_sym = false;
   if (npts != 0 && nsteps != 0) {
-    if (int rc = build_injectors(h, "sg_set_injectors", npts, pts, what, nsteps, amp, it, own)) return rc;
+    if (int rc = build_injectors(h, "sg_set_injectors", npts, pts, what, nsteps, amp, it, own, leave_sym)) return rc;
   } else if (npts < 0 || nsteps < 0) {
     return fail(h, SG_ERR_ARG, "sg_set_injectors: npts and nsteps must be >= 0");
   }
-  if (int rc = arm_hook(h, h->inj, it, it.npts > 0)) return rc;
+  if (int rc = arm_hook(h, h->inj, it, it.npts > 0, leave_sym)) return rc;
   if (owned && !own.empty()) std::memcpy(owned, own.data(), own.size() * sizeof(int32_t));
   return SG_OK;
 }
@@ -769,11 +778,20 @@ int sg_inject(sg_handle* h, int64_t npts, const double* pts, int what, const dou
   HIPCHECK(h, hipSetDevice(h->cfg.device));
   InjectTables it;
   std::vector<int32_t> own;
-  if (int rc = build_injectors(h, "sg_inject", npts, pts, what, 1, amp, it, own)) return rc;
-  if (it.nown == 0) return SG_OK;
+  bool leave_sym = false;
+  if (int rc = build_injectors(h, "sg_inject", npts, pts, what, 1, amp, it, own, leave_sym)) return rc;
+  if (it.nown == 0) return SG_OK;   // (no point of this block's: its table is symmetric)
   if (int rc = join_second(h)) return rc;
-  if (int rc = queue_inject(h, h->stream, it, nullptr, 1)) return rc;
-  HIPCHECK(h, hipStreamSynchronize(h->stream));   // the tables are this call's: they go when it returns
+  // A table that is not symmetric: the mirrors, then the launch in full storage; the block leaves symmetric storage once
+  // both are queued and done - a call that fails before leaves the handle as it was.
+  if (leave_sym)
+    if (int rc = queue_sym_mirrors(h)) return rc;
+  if (int rc = queue_inject(h, h->stream, it, nullptr, 1, leave_sym ? 0 : -1)) return rc;
+  HIPCHECK(h, sync_all(h));   // the tables are this call's: they go when it returns
+  if (leave_sym) {
+    h->sym = false;
+    h->epoch += 1;
+  }
   return SG_OK;
 }
 

@@ -326,12 +326,13 @@ struct sg_handle {
 
 static_assert(SG_MAX_BOXES == SG_MAX_REGION_BOXES, "kernels.hpp and seigen_hip.h disagree on the box limit");
 
+// (an allocation the device refuses is SG_ERR_NOMEM wherever it happens - DevBuf::alloc / upload, hipHostMalloc)
 #define HIPCHECK(h, expr)                                                                        \
   do {                                                                                           \
     hipError_t _e = (expr);                                                                      \
     if (_e != hipSuccess) {                                                                      \
       (h)->err = std::string(#expr) + ": " + hipGetErrorString(_e);                              \
-      return SG_ERR_DEVICE;                                                                      \
+      return _e == hipErrorOutOfMemory ? SG_ERR_NOMEM : SG_ERR_DEVICE;                           \
     }                                                                                            \
   } while (0)
 
@@ -363,6 +364,7 @@ inline hipError_t sync_all(sg_handle* h) {
 
 // transfer.cpp: make the (i > j) lines of both stress buffers valid again and continue with the full-tensor kernels
 int leave_sym_mode(sg_handle* h);
+int queue_sym_mirrors(sg_handle* h);   // ... its launches alone: sg_inject changes the mode behind its own launch
 
 // hostlogic.hpp: the layout of the block's fields
 inline Layout layout(const sg_handle* h) { return Layout{h->md.gw, h->ncls, h->re.nd}; }
@@ -373,7 +375,8 @@ inline void region_boxes(const sg_handle* h, int region, std::vector<Box>& out) 
 }
 int resolve_timing(sg_handle* h);
 int finish_step_call(sg_handle* h);   // stages.cpp: the end of sg_step and comm_step (ev1, synchronise, last_ms)
-int queue_inject(sg_handle* h, hipStream_t stream, const InjectTables& it, const int64_t* ctr, int64_t step);   // stages.cpp: one launch of the injector kernel
+// stages.cpp: one launch of the injector kernel (sym: the storage mode the launch writes in, -1: the handle's)
+int queue_inject(sg_handle* h, hipStream_t stream, const InjectTables& it, const int64_t* ctr, int64_t step, int sym = -1);
 int measure_prepare(sg_handle* h);    // api.cpp: the scratch of the monitor's samples (MeasureScratch), built once
 // transfer.cpp: one buffer in the device layout of field `field` (doubles) -> host[cell][node][comp], behind everything queued
 int download_layout(sg_handle* h, int field, const double* dev, double* host);

@@ -450,16 +450,7 @@ int launch_stage(const void* kernel, int dim, int P, const StageArgs& a, void* s
 // the components and nodes of one facet: 64 different lines per wavefront, and every index through 64-bit divisions
 // and loads from the device copy of MeshDev - 0.12 ms per launch for 6-12 MB, on the critical path of a split stage:
 // the FIRST launch, its pack and the exchange follow one another.)  Everything the kernel needs travels by value.
-struct PackArgs {
-  int nside;
-  int side[6];
-  void* out[6];
-  int start[7];          // element ranges of the sides within the launch
-  int n2[6];             // boundary cubes of each side
-  int n[3], nd, nf, ncls, hpc, dim, gw;
-  signed char side_cls[6][2], side_face[6][2];
-  unsigned char fnode[MAX_FACES][MAX_NF + 1];
-};
+// (PackArgs: kernels.hpp)
 
 template <typename T>
 __global__ void pack_kernel(const T* field, int ncomp, PackArgs P, int sym) {

@@ -259,6 +259,18 @@ int launch_mirror(const MeshDev& md_host, void* field, int f32, void* stream);
 int launch_pack(const MeshDev* md_dev, const MeshDev& md_host, const void* field, int ncomp, int nside,
                 const int* sides, void* const* outs, int sym, int f32, void* stream);
 
+// what pack_kernel (kernels.hip) takes by value: the sides of one launch, their send buffers and the facet tables
+struct PackArgs {
+  int nside;
+  int side[6];
+  void* out[6];
+  int start[7];          // element ranges of the sides within the launch
+  int n2[6];             // boundary cubes of each side
+  int n[3], nd, nf, ncls, hpc, dim, gw;
+  signed char side_cls[6][2], side_face[6][2];
+  unsigned char fnode[MAX_FACES][MAX_NF + 1];
+};
+
 // field[off[k] + c*gw] += coef * values[k][c] at the sparse source nodes (off = device offset of comp 0)
 // (values are scaled by `scale` and rounded first: a separable source's weight of this step)
 int launch_source(void* field, int ncomp, int gw, int64_t nnz, const int64_t* offs, const double* values, double coef,

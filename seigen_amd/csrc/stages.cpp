@@ -321,7 +321,7 @@ int finish_step_call(sg_handle* h) {
 // One launch of the injector kernel (kernels_inject.hip) on `stream`: entry step - 1 (by value, or *ctr) of `it`'s series.  The
 // fields are taken for writing: whatever remembers a field state (the sponge pre-pass of the F stages, hostlogic.hpp PrePass)
 // sees that the velocity has moved on - UTEMP's pre-pass of u1 is stale once an entry has been added to u1.
-int queue_inject(sg_handle* h, hipStream_t stream, const InjectTables& it, const int64_t* ctr, int64_t step) {
+int queue_inject(sg_handle* h, hipStream_t stream, const InjectTables& it, const int64_t* ctr, int64_t step, int sym) {
   inject::Args a;
   std::memset(&a, 0, sizeof(a));
   a.ctr = ctr;
@@ -339,7 +339,7 @@ int queue_inject(sg_handle* h, hipStream_t stream, const InjectTables& it, const
   a.dim = h->cfg.dim;
   a.nd = h->re.nd;
   a.gw = (int32_t)h->md.gw;
-  a.sym = h->sym ? 1 : 0;
+  a.sym = sym >= 0 ? sym : (h->sym ? 1 : 0);
   void* u = (it.what & 1) ? (void*)h->field.write(SG_FIELD_U) : nullptr;
   void* s = (it.what & 2) ? (void*)h->field.write(SG_FIELD_S) : nullptr;
   if (launch_inject(u, s, a, h->f32, stream) != 0) return fail(h, SG_ERR_DEVICE, "injector launch failed");

@@ -3,10 +3,9 @@
 // two-slot pipeline for large downloads, and the symmetric-stress bookkeeping of uploads.
 #include "handle.hpp"
 
-// Leave symmetric-stress mode: make the (i > j) lines of both stress buffers valid again.
-int leave_sym_mode(sg_handle* h) {
-  h->epoch += 1;
-  if (!h->sym) return SG_OK;
+// The launches that make the (i > j) lines of both stress buffers, and of the stress spectra, valid again.  They change
+// nothing that symmetric storage reads: a caller that fails after them has left the handle as it was.
+int queue_sym_mirrors(sg_handle* h) {
   for (int f : {SG_FIELD_S, SG_FIELD_SH}) {
     if (launch_mirror(h->md, h->field.write(f), h->f32, h->stream) != 0) return fail(h, SG_ERR_DEVICE, "mirror kernel launch failed");
   }
@@ -16,8 +15,17 @@ int leave_sym_mode(sg_handle* h) {
     for (int k = 0; k < 2 * h->spc.nfreq; ++k)
       if (launch_mirror(h->md, h->spc.acc[1].get() + (size_t)k * n, 0, h->stream) != 0) return fail(h, SG_ERR_DEVICE, "mirror kernel launch failed");
   }
-  HIPCHECK(h, sync_all(h));
-  h->sym = false;
+  return SG_OK;
+}
+
+// Leave symmetric-stress mode.  The storage mode and the epoch of the captured graphs change last, once nothing can fail.
+int leave_sym_mode(sg_handle* h) {
+  if (h->sym) {
+    if (int rc = queue_sym_mirrors(h)) return rc;
+    HIPCHECK(h, sync_all(h));
+    h->sym = false;
+  }
+  h->epoch += 1;
   return SG_OK;
 }
 
@@ -90,7 +98,7 @@ static int download_pipelined(sg_handle* h, int field, double* dev, int64_t cell
 
 // Copy `ncells` cells from `cell0` between a host array in the reference layout and the device
 // field.  gw == 1: the layouts coincide; otherwise go through a staging buffer + layout kernel.
-static int transfer(sg_handle* h, int field, int64_t cell0, int64_t ncells, double* host, bool to_device) {
+static int transfer_staged(sg_handle* h, int field, int64_t cell0, int64_t ncells, double* host, bool to_device) {
   HIPCHECK(h, hipSetDevice(h->cfg.device));
   if (int rc = join_second(h)) return rc;
   HIPCHECK(h, sync_all(h));
@@ -148,16 +156,32 @@ static int transfer(sg_handle* h, int field, int64_t cell0, int64_t ncells, doub
       // are stale wherever kernels ran in symmetric mode), then repeat this upload in full mode
       int rc = leave_sym_mode(h);
       if (rc != SG_OK) return rc;
-      return transfer(h, field, cell0, ncells, host, true);
+      return transfer_staged(h, field, cell0, ncells, host, true);
     }
   }
   return SG_OK;
 }
 
+// The staging buffer is allocated by the first transfer and kept - by the first that succeeds: a failed call leaves the
+// handle as it was, without a buffer it did not have.
+template <typename F>
+static int keep_staging_on_success(sg_handle* h, F&& call) {
+  const bool had = h->staging.get() != nullptr;
+  const int rc = call();
+  if (rc != SG_OK && !had) {
+    h->staging.reset();
+    h->staging_len = 0;
+  }
+  return rc;
+}
+static int transfer(sg_handle* h, int field, int64_t cell0, int64_t ncells, double* host, bool to_device) {
+  return keep_staging_on_success(h, [&]() { return transfer_staged(h, field, cell0, ncells, host, to_device); });
+}
+
 // One buffer in the device layout of field `field`, in double whatever the block's dtype (an accumulator of the spectra), ->
 // host[cell][node][comp] through the staging buffer and the layout kernel of the fields' own downloads; a stress buffer of a
 // block in symmetric storage takes its (i > j) entries from their mirrors.
-int download_layout(sg_handle* h, int field, const double* dev, double* host) {
+static int download_layout_staged(sg_handle* h, int field, const double* dev, double* host) {
   if (int rc = join_second(h)) return rc;
   HIPCHECK(h, sync_all(h));
   const size_t per_cell = h->field_len[field] / (size_t)h->ncells;
@@ -184,6 +208,10 @@ int download_layout(sg_handle* h, int field, const double* dev, double* host) {
     HIPCHECK(h, hipMemcpy(host + (size_t)done * per_cell, h->staging.get(), (size_t)n * per_cell * sizeof(double), hipMemcpyDeviceToHost));
   }
   return SG_OK;
+}
+
+int download_layout(sg_handle* h, int field, const double* dev, double* host) {
+  return keep_staging_on_success(h, [&]() { return download_layout_staged(h, field, dev, host); });
 }
 
 extern "C" {
