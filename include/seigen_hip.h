@@ -117,12 +117,15 @@ typedef struct sg_config {
                         library's own (sg_get_second_stream), ordered against this one by events in both directions.
                         Calls that return with the launches only QUEUED, ordered on the stream against whatever the
                         caller puts there before and after, and never waiting on the host: sg_run_stage, sg_end_step,
-                        sg_halo_pack, sg_halo_pack_sides, sg_apply_F, sg_apply_G, sg_correlate and sg_reset_correlation
-                        (release = 0).  Calls that make the host wait for the stream: sg_create (the whole device),
-                        sg_step and the native exchange's stepping (to the end of what they queued), every setter
-                        (sg_set_*, sg_leave_sym), sg_inject, sg_measure, every transfer and read-out (sg_set_field*,
-                        sg_get_field*, sg_get_receivers, sg_get_monitor, sg_get_correlation, sg_get_counters with timing
-                        on), sg_sync and sg_destroy.  The set-up paths also use the legacy stream (hipMemset, hipMemcpy)
+                        sg_halo_pack, sg_halo_pack_sides, sg_apply_F, sg_apply_G, sg_correlate, sg_reset_correlation
+                        (release = 0), sg_get_field_dev, sg_get_spectrum_dev and sg_set_field_dev (but for a stress
+                        handed to a block in symmetric storage).  Calls that make the host wait for the stream:
+                        sg_create (the whole device), sg_step and the native exchange's stepping (to the end of what
+                        they queued), every setter (sg_set_* but sg_set_field_dev, sg_leave_sym), sg_inject, sg_measure,
+                        every transfer and read-out through host memory (sg_set_field, sg_get_field, their _range
+                        forms, sg_get_spectrum, sg_get_receivers, sg_get_monitor, sg_get_correlation, sg_get_counters
+                        with timing on), sg_set_field_dev of a stress handed to a block in symmetric storage, sg_sync
+                        and sg_destroy.  The set-up paths also use the legacy stream (hipMemset, hipMemcpy)
                         after that wait and return when those have completed (a fill is followed by a blocking copy); a
                         non-blocking stream is not ordered against the legacy stream, so a fill that no host wait follows
                         (sg_correlate's accumulator, sg_comm_selftest's buffers) goes on the handle's stream. */
@@ -207,6 +210,34 @@ int sg_get_field(sg_handle* h, int field, double* host, size_t nbytes);
 /* the same for `ncells` consecutive cells starting at `cell0` (chunked transfer of large fields) */
 int sg_set_field_range(sg_handle* h, int field, int64_t cell0, int64_t ncells, const double* host, size_t nbytes);
 int sg_get_field_range(sg_handle* h, int field, int64_t cell0, int64_t ncells, double* host, size_t nbytes);
+
+/* ---- device transfers: the same between the field and a DEVICE buffer of the caller's, on the handle's stream -------
+ * The caller's buffer is memory of the handle's device in the host layout [cell][node][comp] of sg_get_field_range, for
+ * `ncells` cells from `cell0`, of the type `dtype` (0 = double, 1 = float: the CALLER's buffer, independent of
+ * sg_config::dtype); nbytes is exactly its size.  A double block into a float buffer, and doubles into a float block,
+ * round once, (float)v - bitwise what sg_set_field gives for the same doubles; float into double is exact.  The library
+ * does not test that the pointer is device memory: that is the caller's contract.  The buffer stays alive until the
+ * stream has passed the launch.  SG_ERR_ARG: a null pointer, a dtype outside 0 .. 1, a field, range or nbytes that
+ * sg_get_field_range refuses.  A call that fails leaves fields, storage mode, write counts and epoch as they were.
+ * sg_get_field_dev returns with its launch only QUEUED on the handle's stream, ordered against whatever the caller puts
+ *   there before and after, and never waits on the host; in symmetric-stress storage the (i > j) entries are delivered
+ *   from their mirrors, as sg_get_field does.
+ * sg_set_field_dev is queued only as well, EXCEPT for a stress field handed to a block in symmetric storage: that
+ *   upload tests the caller's data for symmetry, the call waits for the stream and reads the answer, and an asymmetric
+ *   stress makes the block leave symmetric storage (sg_leave_sym) and the upload run again in full storage - the rule
+ *   of sg_set_field.  Cells outside the range and the padding lanes of the layout are not written.
+ * sg_get_spectrum_dev delivers one accumulator of sg_set_spectra (always double on the device; errors and mirror rule
+ *   of sg_get_spectrum), queued only. */
+int sg_get_field_dev(sg_handle* h, int field, int64_t cell0, int64_t ncells, void* dev_out, int dtype, size_t nbytes);
+int sg_set_field_dev(sg_handle* h, int field, int64_t cell0, int64_t ncells, const void* dev_in, int dtype, size_t nbytes);
+int sg_get_spectrum_dev(sg_handle* h, int field, int freq, int part, void* dev_out, int dtype, size_t nbytes);
+/* The launch plan of one such transfer (device-free): a block whose layout puts gw cubes of ncls cells side by side
+ * (1: host layout, 16, 64), nd nodes of ncomp components, dev_bytes per word on the device and caller_bytes in the
+ * caller's buffer (4 or 8 each).  out = first item (cube group * ncls + class; gw = 1: cell), number of items, rows
+ * (node * ncomp + comp) per slice, slices per item, blocks of the grid (at most SG_XFER_GRID_CAP: the grid strides over
+ * the (item, slice) units beyond it), bytes of LDS per block. */
+#define SG_XFER_GRID_CAP 1048576
+int sg_xfer_plan(int gw, int ncls, int nd, int ncomp, int dev_bytes, int caller_bytes, int64_t cell0, int64_t ncells, int64_t out[6]);
 
 /* ---- absorption (elastic.py:136-141, :207-208) ------------------------------------ */
 /* sigma_nodes: [cell][nd(sigma_degree)] nodal values of the DG_q sponge field, or NULL to disable. */

@@ -62,6 +62,10 @@ SYMBOLS = {
     "sg_get_field": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),
     "sg_set_field_range": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, _P, C.c_size_t]),
     "sg_get_field_range": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, _P, C.c_size_t]),
+    "sg_get_field_dev": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, _P, C.c_int, C.c_size_t]),
+    "sg_set_field_dev": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, _P, C.c_int, C.c_size_t]),
+    "sg_get_spectrum_dev": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_size_t]),
+    "sg_xfer_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P]),
     "sg_set_absorption": (C.c_int, [_P, _P, C.c_int]),
     "sg_set_source": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P]),
     "sg_set_source_separable": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P]),

@@ -83,6 +83,7 @@ class HipBlock(object):
         self.u_dofs, self.s_dofs = int(info.u_dofs), int(info.s_dofs)
         self.halo_faces = [int(x) for x in info.halo_faces]
         self.nbr_mask = int(nbr_mask)
+        self._device = int(device)
         self._inj = None                # (what, entries, the library's step count at the arming call) of set_injectors
 
     def stream_ptr(self):
@@ -149,6 +150,77 @@ class HipBlock(object):
             raise ValueError("out must be a C-contiguous float64 array of shape %r" % (shape,))
         check(self.lib.sg_get_field_range(self.h, field, int(cell0), int(ncells), out.ctypes.data, out.nbytes), self.h)
         return out
+
+    # ---- device transfers (sg_get_field_dev / sg_set_field_dev / sg_get_spectrum_dev) -------------------------
+    def _torch_device(self):
+        import torch
+        return torch.device("cuda", self._device)
+
+    def _on_stream(self, tensor, call):
+        """Run `call` - one queued-only library call that reads or writes `tensor` - ordered against torch's current stream in
+        both directions, without a host wait: the handle's stream first waits for torch's current stream, torch's current
+        stream then waits for the handle's.  The caching allocator is told that the CURRENT stream uses the tensor, not the
+        handle's: the current stream has just been put behind the handle's launch, so memory freed and handed out again is
+        behind it too - and the allocator records an event on every stream it was told of when the tensor is freed, which
+        may be after sg_destroy has destroyed a stream the handle owned."""
+        import torch
+        with torch.cuda.device(self._device):
+            mine = torch.cuda.ExternalStream(self.stream_ptr(), device=self._device)
+            cur = torch.cuda.current_stream(self._device)
+            if mine.cuda_stream != cur.cuda_stream:
+                mine.wait_stream(cur)
+            call()
+            if mine.cuda_stream != cur.cuda_stream:
+                cur.wait_stream(mine)
+            tensor.record_stream(cur)
+
+    def _dev_tensor(self, t, shape, who):
+        import torch
+        if not isinstance(t, torch.Tensor) or t.device != self._torch_device() or t.dtype not in (torch.float64, torch.float32) \
+                or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+            raise ValueError("%s takes a contiguous float64 or float32 tensor of shape %r on %s" % (who, tuple(shape), self._torch_device()))
+        return 1 if t.dtype == torch.float32 else 0
+
+    def get_field_dev(self, field, out=None, dtype=None, cell0=0, ncells=None):
+        """Cells cell0 .. cell0 + ncells - 1 (default: to the last) of a field as a torch tensor [ncells, nd, comps...] on the
+        block's device, float64 or float32 (`dtype`, default float64, or that of `out`), moved on the device: the launch is
+        queued on the block's stream between torch's current stream before and after, and nothing waits on the host."""
+        import torch
+        ncells = self.ncells - int(cell0) if ncells is None else int(ncells)
+        shape = (ncells,) + self.field_shape(field)[1:]
+        if out is None:
+            out = torch.empty(shape, dtype=dtype or torch.float64, device=self._torch_device())
+        elif dtype is not None and out.dtype != dtype:
+            raise ValueError("out is %s, dtype asks for %s" % (out.dtype, dtype))
+        code = self._dev_tensor(out, shape, "get_field_dev")
+        nbytes = out.numel() * out.element_size()
+        self._on_stream(out, lambda: check(self.lib.sg_get_field_dev(self.h, int(field), int(cell0), ncells, C.c_void_p(out.data_ptr()),
+                                                                     code, nbytes), self.h))
+        return out
+
+    def set_field_dev(self, field, tensor, cell0=0):
+        """The cells from `cell0` of a field from a contiguous float64 or float32 tensor [ncells, nd, comps...] of the block's
+        device, moved on the device.  Queued like get_field_dev - but a stress handed to a block in symmetric storage makes
+        the host wait once for the answer whether it is symmetric (include/seigen_hip.h sg_set_field_dev)."""
+        import torch
+        if not isinstance(tensor, torch.Tensor) or tensor.dim() < 1:
+            raise ValueError("set_field_dev takes a torch tensor [ncells, nd, comps...]")
+        shape = (int(tensor.shape[0]),) + self.field_shape(field)[1:]
+        code = self._dev_tensor(tensor, shape, "set_field_dev")
+        nbytes = tensor.numel() * tensor.element_size()
+        self._on_stream(tensor, lambda: check(self.lib.sg_set_field_dev(self.h, int(field), int(cell0), shape[0], C.c_void_p(tensor.data_ptr()),
+                                                                        code, nbytes), self.h))
+
+    def get_spectrum_dev(self, field, freq):
+        """get_spectrum as a complex128 torch tensor on the block's device, moved on the device (sg_get_spectrum_dev)."""
+        import torch
+        k = {0: 0, 1: 1, _lib.FIELD_S: 1}[int(field)]
+        shape = self.field_shape(_lib.FIELD_S if k else _lib.FIELD_U)
+        parts = [torch.empty(shape, dtype=torch.float64, device=self._torch_device()) for _ in range(2)]
+        for part, t in enumerate(parts):
+            self._on_stream(t, lambda: check(self.lib.sg_get_spectrum_dev(self.h, k, int(freq), part, C.c_void_p(t.data_ptr()), 0,
+                                                                          t.numel() * 8), self.h))
+        return torch.complex(parts[0], parts[1])
 
     def set_params(self, density, dt, lam, mu):
         lam_a, mu_a = _f64(np.atleast_1d(lam)).ravel(), _f64(np.atleast_1d(mu)).ravel()

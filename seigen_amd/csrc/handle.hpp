@@ -1,6 +1,7 @@
 // The handle behind the C-ABI (include/seigen_hip.h) and what its translation units share:
 //   api.cpp      create / destroy, parameters, sponge, source, receivers, injectors, monitor, correlation, spectra: device checks, uploads, the move into the handle
 //   transfer.cpp host <-> device field transfers (layout conversion, pinned pipeline)
+//   devxfer.cpp  device <-> device field and spectrum transfers into the caller's buffers, queued on the stream
 //   stages.cpp   regions, stage launches, the LF4 step, graphs, halo packs, timing
 // and, without a device or a HIP header (the CPU sanitizer build, `make host-asan`):
 //   hostapi.cpp (hostlogic.hpp)  family choice, field layout, stage table, region boxes / items, point location, receiver and injector plans;

@@ -355,6 +355,19 @@ int sg_spectra_clock(int64_t every, int64_t nsamples, int64_t steps, int64_t mor
   return SG_OK;
 }
 
+int sg_xfer_plan(int gw, int ncls, int nd, int ncomp, int dev_bytes, int caller_bytes, int64_t cell0, int64_t ncells, int64_t out[6]) {
+  if (!out || (gw != 1 && gw != 16 && gw != 64) || ncls < 1 || nd < 1 || ncomp < 1 || cell0 < 0 || ncells < 0) return SG_ERR_ARG;
+  if ((dev_bytes != 4 && dev_bytes != 8) || (caller_bytes != 4 && caller_bytes != 8)) return SG_ERR_ARG;
+  const XferPlan p = xfer_plan(gw, ncls, nd, ncomp, dev_bytes, cell0, ncells);   // (the LDS image is in the block's type)
+  out[0] = p.item0;
+  out[1] = p.nitems;
+  out[2] = p.rows_per_slice;
+  out[3] = p.slices;
+  out[4] = p.grid;
+  out[5] = p.lds_bytes;
+  return SG_OK;
+}
+
 int sg_spectra_lines(int dim, int sym, int32_t* lines, int max_lines) {
   if (dim < 1 || dim > 3 || !lines) return SG_ERR_ARG;
   const std::vector<int32_t> r = spectra_lines(dim, sym != 0);

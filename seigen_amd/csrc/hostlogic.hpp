@@ -382,3 +382,49 @@ inline std::vector<int32_t> spectra_lines(int dim, bool sym) {
     if (spectra_line_kept(dim, sym, c)) r.push_back(c);
   return r;
 }
+
+// Device-to-device field transfers (seigen_hip.h sg_get_field_dev / sg_set_field_dev / sg_get_spectrum_dev; kernels_xfer.hip):
+// the launch plan of one transfer of `ncells` cells from `cell0`, for the launch wrapper (devxfer.cpp) and sg_xfer_plan alike.
+// For one item (cube group, class) the device side is one block [row = node * ncomp + comp][lane < gw], the caller's side gw
+// runs of rows = nd * ncomp words, one per cube: a [rows][gw] <-> [gw][rows] transpose per item, which a workgroup does for a
+// SLICE of rows_per_slice rows at a time through an LDS image [row][pitch = gw + 1] in the block's word size.  The items are
+// all classes of the groups that hold the first and the last cell of the range; a lane whose cell is outside the range (or
+// is layout padding) moves nothing.  gw = 1: the layouts coincide, an item is a cell, no LDS - a flat pass of 256-word
+// chunks.  The grid strides over the units (item, slice), or the chunks, beyond its cap.
+static constexpr int64_t XFER_GRID_CAP = SG_XFER_GRID_CAP;
+static constexpr int64_t XFER_LDS_BUDGET = 32768;   // of the 64 KB a block gets without an attribute: two slices of a P4 stress item, four blocks a CU
+static constexpr int XFER_THREADS = 256;
+struct XferPlan {
+  int64_t item0 = 0, nitems = 0;   // items item0 .. item0 + nitems - 1
+  int64_t rows = 0;                // nd * ncomp
+  int64_t rows_per_slice = 0, slices = 0;   // slice s of an item: rows s * rows_per_slice .. min(rows, (s + 1) * rows_per_slice) - 1
+  int64_t pitch = 0;               // words of an LDS row
+  int64_t units = 0;               // nitems * slices; gw = 1: chunks of XFER_THREADS words
+  int64_t grid = 0;                // blocks of XFER_THREADS threads, 0: nothing to move
+  int64_t lds_bytes = 0;
+};
+inline XferPlan xfer_plan(int gw, int ncls, int nd, int ncomp, int dev_bytes, int64_t cell0, int64_t ncells) {
+  XferPlan p;
+  p.rows = (int64_t)nd * ncomp;
+  if (ncells <= 0) return p;
+  if (gw == 1) {
+    p.item0 = cell0;
+    p.nitems = ncells;
+    p.rows_per_slice = p.rows;
+    p.slices = 1;
+    p.units = (ncells * p.rows + XFER_THREADS - 1) / XFER_THREADS;
+  } else {
+    const int64_t g0 = cell0 / ncls / gw, g1 = (cell0 + ncells - 1) / ncls / gw;
+    p.item0 = g0 * ncls;
+    p.nitems = (g1 - g0 + 1) * ncls;
+    p.pitch = gw + 1;
+    const int64_t fit = std::max<int64_t>(1, XFER_LDS_BUDGET / (p.pitch * dev_bytes));
+    p.slices = (p.rows + fit - 1) / fit;
+    p.rows_per_slice = (p.rows + p.slices - 1) / p.slices;
+    p.slices = (p.rows + p.rows_per_slice - 1) / p.rows_per_slice;
+    p.units = p.nitems * p.slices;
+    p.lds_bytes = p.rows_per_slice * p.pitch * dev_bytes;
+  }
+  p.grid = std::min(p.units, XFER_GRID_CAP);
+  return p;
+}

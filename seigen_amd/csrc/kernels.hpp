@@ -426,4 +426,12 @@ struct Args {
 }  // namespace spectra
 int launch_spectra(const void* field, const spectra::Args& a, int f32, int grid, void* stream);
 
+// Device transfers (kernels_xfer.hip; seigen_hip.h sg_get_field_dev / sg_set_field_dev / sg_get_spectrum_dev): `ncells` cells
+// from `cell0` between a buffer in the layout of the fields (`field`: float where f32) and the caller's device buffer
+// [cell][node][comp] (`buf`: float where c32), by the plan of hostlogic.hpp xfer_plan (item0, units, slices, rows_per_slice,
+// pitch, grid, lds_bytes).  dir = 0: buf -> field, 1: field -> buf.  sym and flag as launch_layout's.
+int launch_xfer(int gw, int ncls, int nd, int ncomp, int dim, int dir, void* field, void* buf, int64_t cell0, int64_t ncells,
+                int sym, int* flag, int f32, int c32, int64_t item0, int64_t units, int slices, int rows_per_slice, int pitch,
+                int grid, size_t lds_bytes, void* stream);
+
 }  // namespace sg

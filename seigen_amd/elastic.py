@@ -739,6 +739,14 @@ class ElasticLF4(object):
         out = self._block.get_spectrum(0 if field == "velocity" else 1, self._spectrum_index(f))
         return out.reshape((-1, d) if field == "velocity" else (-1, d, d))
 
+    def spectrum_torch(self, field, f):
+        """`spectrum` as a complex128 torch tensor on the block's device, moved on the device (no host copy)."""
+        if field not in ("velocity", "stress"):
+            raise ValueError("spectra fields are 'velocity' and 'stress', not %r" % (field,))
+        d = self.dimension
+        out = self._block.get_spectrum_dev(0 if field == "velocity" else 1, self._spectrum_index(f))
+        return out.reshape((-1, d) if field == "velocity" else (-1, d, d))
+
     def correlate_spectra(self, other, f, f_other=None, weights=(1.0, 1.0, 1.0), z=1 + 0j):
         """Add weights * Re(z conj(a^(f)) . b^(f_other)) in the forms (uu, ss, tt) of `correlate` - a^ this solver's spectra,
         b^ `other`'s (f_other = None: the same frequency) - to this block's per-cell accumulator (correlation,

@@ -236,6 +236,26 @@ class Function(object):
             self._set(np.asarray(other, dtype=np.float64))
         return self
 
+    # ---- device-resident transfers of a bound Function (HipBlock.get_field_dev / set_field_dev) -------------
+    def _bound(self, who):
+        if self._binding is None:
+            raise ValueError("%s needs a Function bound to a solver's device field; this one is host-resident" % who)
+        return self._binding
+
+    def to_torch(self, out=None, dtype=None):
+        """The values as a torch tensor [cells, nodes] + value_shape on the solver's device (float64, or `dtype` / that of
+        `out`), moved on the device on the block's stream between torch's current stream before and after: no host copy,
+        no host wait."""
+        block, field = self._bound("to_torch")
+        return block.get_field_dev(field, out=out, dtype=dtype)
+
+    def from_torch(self, t):
+        """Set the values from a contiguous float64 or float32 tensor [cells, nodes] + value_shape of the solver's device,
+        moved on the device (a stress handed to a block in symmetric storage makes the host wait once)."""
+        block, field = self._bound("from_torch")
+        block.set_field_dev(field, t)
+        return self
+
     def interpolate(self, expression):
         """Nodal interpolation [upstream]: evaluate at the node coordinates."""
         is_expr = isinstance(expression, Expression) or not callable(expression)
