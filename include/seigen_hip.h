@@ -239,6 +239,48 @@ int sg_get_spectrum_dev(sg_handle* h, int field, int freq, int part, void* dev_o
 #define SG_XFER_GRID_CAP 1048576
 int sg_xfer_plan(int gw, int ncls, int nd, int ncomp, int dev_bytes, int caller_bytes, int64_t cell0, int64_t ncells, int64_t out[6]);
 
+/* ---- frames: a field rastered on a pixel lattice aligned with the block's cubes, on the device -----------------------
+ * Along a FREE axis a every cube holds m[a] pixels: pixel i * m[a] + j (0 <= j < m[a]) belongs to the block's cube i, lies
+ * at the cube fraction t = (j + 1/2) / m[a], physically at origin[a] + (cube0[a] + i + t) * h[a]; the extent is
+ * P[a] = n[a] * m[a].  A FIXED axis (fixed[a] = 1) is the single plane x_a = at[a] - a slice - of extent 1: the cube layer
+ * and t in [0, 1] come from (at[a] - origin[a]) / h[a] by the rule of sg_locate_points (on a grid plane the lower cube
+ * where the mesh has one); a block that does not hold that layer owns nothing of the frame: the call succeeds and
+ * launches nothing.  Limits: 1 <= m[a] <= 8, at most 64 in-cube pixels Q = prod m[a] over the free axes, at least one
+ * free axis; entries of axes beyond dim are ignored.  Every cube of a block has the same cell class k(q) and reference
+ * coordinates xi(q) for its in-cube pixel q = j0 + m0 * (j1 + m1 * j2): what sg_locate_points returns on the UNIT block
+ * (same dim, diagonal and cell kind, n = 1, h = 1, origin = 0, cube0 = 0) at the point t - the lowest class whose
+ * coordinates pass the 1e-12 tests - and the weights phi[q][a] are sg_tabulate_cell at xi(q), as for the receivers. */
+typedef struct sg_frame {
+  int32_t m[3];      /* pixels per cube along axis a (>= 1); ignored where fixed[a] */
+  int32_t fixed[3];  /* 1: the frame is the single plane x_a = at[a] (a slice); extent 1 along a */
+  double  at[3];
+} sg_frame;
+/* sg_get_frame_dev writes out[comp][P2][P1][P0] (axes beyond dim have extent 1) of field `field` (any of
+ * sg_get_field_dev's) into DEVICE memory of the caller's, of type dtype (0 = double, 1 = float); the components in the
+ * host layout's order - dim of a velocity, dim^2 row-major of a stress, in symmetric storage the (i > j) entries from
+ * their mirrors.  stride = { comp, axis 2, axis 1, axis 0 } in elements (non-negative), NULL: contiguous; nbytes must
+ * cover the largest index touched, else SG_ERR_ARG and nothing is queued.  Strides let the blocks of a mesh write into
+ * views of one image.  The value is the receivers':
+ *   out[c][pixel] = sum_a phi[q][a] * (double)field[cell(cube, k(q))][a][c]
+ * over a ascending with fma from zero in double, rounded once where dtype is float - the same bits on every kernel
+ * family, storage mode and stream.  The launch is only QUEUED on the handle's stream under the ordering rules of
+ * sg_get_field_dev.  The tables of a frame specification (classes, weights, listed cube groups) live on the device with
+ * the handle, which keeps those of the last specification: a call with another specification builds them first (an
+ * allocation and blocking copies, as a setter does), a repeated one does not.  A call that fails leaves the handle as it
+ * was.  SG_ERR_ARG: a null pointer, a field or dtype outside its range, a frame beyond the limits, a negative stride,
+ * nbytes too small. */
+int sg_get_frame_dev(sg_handle* h, int field, const sg_frame* fr, void* dev_out, int dtype, const int64_t stride[4], size_t nbytes);
+/* The plan of a frame on a block (device-free; the kernel family, hence the group width gw of the layout, as sg_create
+ * chooses it): out = { P0, P1, P2, Q, owns (0 / 1), layer of axis 0, 1, 2 (block-local cube index of a fixed axis the
+ * block holds, else -1), listed groups of gw cubes, units (waves' (64 cubes, class) units; gw = 1: (cube, in-cube pixel)
+ * threads), blocks of 256 threads along x (at most SG_FRAME_GRID_CAP: the grid strides over the units beyond it; the
+ * output component is the grid's y), gw }.  groups (or NULL) receives the listed groups, ascending, at most max_groups. */
+#define SG_FRAME_GRID_CAP 65536
+int sg_frame_plan(const sg_config* cfg, const sg_frame* fr, int64_t out[12]);
+int64_t sg_frame_groups(const sg_config* cfg, const sg_frame* fr, int32_t* groups, int64_t max_groups);
+/* cls[Q], xi[Q][dim] and phi[Q][nd] of the in-cube pixels (device-free; degree <= 8 as sg_locate_points) */
+int sg_frame_weights(const sg_config* cfg, int degree, const sg_frame* fr, int32_t* cls, double* xi, double* phi);
+
 /* ---- absorption (elastic.py:136-141, :207-208) ------------------------------------ */
 /* sigma_nodes: [cell][nd(sigma_degree)] nodal values of the DG_q sponge field, or NULL to disable. */
 int sg_set_absorption(sg_handle* h, const double* sigma_nodes, int sigma_degree);

@@ -42,6 +42,10 @@ class SgCounters(C.Structure):
                 ("halo_pack_ms", C.c_double), ("halo_pack_launches", C.c_int64), ("halo_bytes_packed", C.c_int64)]
 
 
+class SgFrame(C.Structure):
+    _fields_ = [("m", C.c_int32 * 3), ("fixed", C.c_int32 * 3), ("at", C.c_double * 3)]
+
+
 # every symbol include/seigen_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _DP = C.POINTER(C.c_double)
@@ -66,6 +70,10 @@ SYMBOLS = {
     "sg_set_field_dev": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, _P, C.c_int, C.c_size_t]),
     "sg_get_spectrum_dev": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_size_t]),
     "sg_xfer_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P]),
+    "sg_get_frame_dev": (C.c_int, [_P, C.c_int, C.POINTER(SgFrame), _P, C.c_int, _P, C.c_size_t]),
+    "sg_frame_plan": (C.c_int, [C.POINTER(SgConfig), C.POINTER(SgFrame), _P]),
+    "sg_frame_groups": (C.c_int64, [C.POINTER(SgConfig), C.POINTER(SgFrame), _P, C.c_int64]),
+    "sg_frame_weights": (C.c_int, [C.POINTER(SgConfig), C.c_int, C.POINTER(SgFrame), _P, _P, _P]),
     "sg_set_absorption": (C.c_int, [_P, _P, C.c_int]),
     "sg_set_source": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P]),
     "sg_set_source_separable": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P]),

@@ -3,7 +3,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import SgConfig, SgInfo, SgCounters, check
+from ._lib import SgConfig, SgFrame, SgInfo, SgCounters, check
 
 
 def _f64(a):
@@ -48,6 +48,51 @@ def injector_weights(cfg, points, nd):
     return cell, psi
 
 
+def make_frame(dim, m=1, slice=None):
+    """The sg_frame of `m` pixels per cube (an int or a per-axis tuple) and `slice` = {axis: coordinate} (the plane
+    x_axis = coordinate; m is ignored along a sliced axis)."""
+    fr = SgFrame()
+    ms = [int(m)] * dim if np.isscalar(m) else [int(x) for x in m]
+    if len(ms) != dim:
+        raise ValueError("m: an int or one value per axis (%d)" % dim)
+    slice = dict(slice or {})
+    if any(not (0 <= int(a) < dim) for a in slice):
+        raise ValueError("slice: axes 0 .. %d" % (dim - 1))
+    for a in range(3):
+        fr.m[a] = ms[a] if a < dim else 1
+        fr.fixed[a] = 0
+        fr.at[a] = 0.0
+    for a, x in slice.items():
+        fr.fixed[int(a)] = 1
+        fr.at[int(a)] = float(x)
+    return fr
+
+
+def frame_plan(cfg, fr):
+    """sg_frame_plan of the frame `fr` (make_frame) on the block `cfg` (an SgConfig) describes, as a dict (device-free);
+    `groups`: the listed cube groups"""
+    out = np.zeros(12, dtype=np.int64)
+    check(_lib.load().sg_frame_plan(C.byref(cfg), C.byref(fr), out.ctypes.data))
+    p = {"P": tuple(int(x) for x in out[:3]), "Q": int(out[3]), "owns": bool(out[4]), "layer": tuple(int(x) for x in out[5:8]),
+         "ngroups": int(out[8]), "units": int(out[9]), "grid": int(out[10]), "gw": int(out[11])}
+    groups = np.zeros(max(1, p["ngroups"]), dtype=np.int32)
+    n = _lib.load().sg_frame_groups(C.byref(cfg), C.byref(fr), groups.ctypes.data, len(groups))
+    if n != p["ngroups"]:
+        raise _lib.SeigenHipError("sg_frame_groups returned %d, the plan has %d groups" % (n, p["ngroups"]))
+    p["groups"] = groups[:n]
+    return p
+
+
+def frame_weights(cfg, degree, fr, nd):
+    """(cls [Q], xi [Q, dim], phi [Q, nd]) of the in-cube pixels of the frame (sg_frame_weights; device-free)"""
+    Q = frame_plan(cfg, fr)["Q"]
+    cls = np.zeros(Q, dtype=np.int32)
+    xi = np.zeros((Q, cfg.dim))
+    phi = np.zeros((Q, int(nd)))
+    check(_lib.load().sg_frame_weights(C.byref(cfg), int(degree), C.byref(fr), cls.ctypes.data, xi.ctypes.data, phi.ctypes.data))
+    return cls, xi, phi
+
+
 class HipBlock(object):
     def __init__(self, dim, degree, n, h, origin, diagonal="left", nbr_mask=0, device=0, stream=None, dtype="f64",
                  cube0=None):
@@ -78,6 +123,7 @@ class HipBlock(object):
         info = SgInfo()
         check(self.lib.sg_get_info(self.h, C.byref(info)), self.h)
         self.dim, self.degree = dim, degree
+        self.n = tuple(int(n[a]) for a in range(dim))
         self.nd, self.nf, self.nfaces, self.ncls = info.nd, info.nf, info.nfaces, info.nclasses
         self.ncells = int(info.ncells)
         self.u_dofs, self.s_dofs = int(info.u_dofs), int(info.s_dofs)
@@ -221,6 +267,48 @@ class HipBlock(object):
             self._on_stream(t, lambda: check(self.lib.sg_get_spectrum_dev(self.h, k, int(freq), part, C.c_void_p(t.data_ptr()), 0,
                                                                           t.numel() * 8), self.h))
         return torch.complex(parts[0], parts[1])
+
+    # ---- frames (sg_get_frame_dev) ---------------------------------------------------------------------------
+    def frame_shape(self, field, m=1, slice=None):
+        """value shape + (P_{d-1}, ..., P_0) of get_frame_dev, the sliced axes dropped"""
+        fr = make_frame(self.dim, m, slice)
+        value = (self.dim, self.dim) if field in (_lib.FIELD_S, _lib.FIELD_SH) else (self.dim,)
+        return value + tuple(self.n[a] * fr.m[a] for a in reversed(range(self.dim)) if not fr.fixed[a])
+
+    def get_frame_dev(self, field, m=1, slice=None, out=None, dtype=None):
+        """A field rastered on a pixel lattice aligned with the block's cubes, as a torch tensor on the block's device: `m`
+        pixels per cube along every axis (an int or a per-axis tuple), `slice` = {axis: coordinate} for the plane x_axis =
+        coordinate.  Shape: value shape + (P_{d-1}, ..., P_0), P_a = n_a * m_a, the sliced axes dropped; float64 or float32
+        (`dtype`, default float64, or that of `out`).  `out` may be a strided view - several blocks write into views of
+        one image - whose value axes of a stress are laid out row-major (stride of i = dim * stride of j).  Queued like
+        get_field_dev: on the block's stream between torch's current stream before and after, no host wait (a frame
+        specification the block has not just used builds its tables first).  A block that does not hold a slice's layer
+        leaves `out` as it is."""
+        import torch
+        fr = make_frame(self.dim, m, slice)
+        shape = self.frame_shape(field, m, slice)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype or torch.float64, device=self._torch_device())
+        elif dtype is not None and out.dtype != dtype:
+            raise ValueError("out is %s, dtype asks for %s" % (out.dtype, dtype))
+        if not isinstance(out, torch.Tensor) or out.device != self._torch_device() or out.dtype not in (torch.float64, torch.float32) \
+                or tuple(out.shape) != tuple(shape):
+            raise ValueError("get_frame_dev takes a float64 or float32 tensor of shape %r on %s" % (tuple(shape), self._torch_device()))
+        st = [int(s) for s in out.stride()]
+        nv = len(shape) - sum(1 for a in range(self.dim) if not fr.fixed[a])
+        if nv == 2 and self.dim > 1 and st[0] != self.dim * st[1]:
+            raise ValueError("get_frame_dev: the value axes of `out` must be row-major (stride of i = dim * stride of j)")
+        if any(s < 0 for s in st):
+            raise ValueError("get_frame_dev: negative strides")
+        axis = {}
+        for k, a in enumerate(a for a in reversed(range(self.dim)) if not fr.fixed[a]):
+            axis[a] = st[nv + k]
+        stride = (C.c_int64 * 4)(st[nv - 1], axis.get(2, 0), axis.get(1, 0), axis.get(0, 0))
+        nbytes = out.untyped_storage().nbytes() - out.storage_offset() * out.element_size()
+        code = 1 if out.dtype == torch.float32 else 0
+        self._on_stream(out, lambda: check(self.lib.sg_get_frame_dev(self.h, int(field), C.byref(fr), C.c_void_p(out.data_ptr()), code,
+                                                                     stride, nbytes), self.h))
+        return out
 
     def set_params(self, density, dt, lam, mu):
         lam_a, mu_a = _f64(np.atleast_1d(lam)).ravel(), _f64(np.atleast_1d(mu)).ravel()

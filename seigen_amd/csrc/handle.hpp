@@ -2,6 +2,7 @@
 //   api.cpp      create / destroy, parameters, sponge, source, receivers, injectors, monitor, correlation, spectra: device checks, uploads, the move into the handle
 //   transfer.cpp host <-> device field transfers (layout conversion, pinned pipeline)
 //   devxfer.cpp  device <-> device field and spectrum transfers into the caller's buffers, queued on the stream
+//   frame.cpp    a field rastered on a cube-aligned pixel lattice into the caller's device buffer, queued on the stream
 //   stages.cpp   regions, stage launches, the LF4 step, graphs, halo packs, timing
 // and, without a device or a HIP header (the CPU sanitizer build, `make host-asan`):
 //   hostapi.cpp (hostlogic.hpp)  family choice, field layout, stage table, region boxes / items, point location, receiver and injector plans;
@@ -210,6 +211,19 @@ struct CorrelationTables {
   bool ready = false;
 };
 
+// The frames of sg_get_frame_dev (frame.cpp, kernels_frame.hip): the tables of the last frame specification, on the device
+struct FrameTables {
+  bool ready = false;
+  sg_frame key = {};          // the specification (frame.cpp frame_key)
+  FramePlan plan;             // ... and its plan (hostlogic.hpp)
+  DevBuf<FrameSpec> spec;     // what the specification fixes for every launch (kernels.hpp)
+  DevBuf<int32_t> cls;        // [Q] class of in-cube pixel q
+  DevBuf<int32_t> order;      // [Q] the pixels sorted by class
+  DevBuf<int32_t> cstart;     // [ncls + 1]
+  DevBuf<double> phi;         // [Q][nd]
+  DevBuf<int32_t> groups;     // the listed groups of gw cubes (hostlogic.hpp FramePlan)
+};
+
 // The four fields of a block.  Whoever writes one asks for it with write(), which counts the write: what remembers a field
 // state (the sponge pre-pass, hostlogic.hpp PrePass) can then tell that the field has moved on - from a stage, a source
 // launch, an upload or the mirror launch alike.  Readers take the const pointer.
@@ -280,6 +294,7 @@ struct sg_handle {
   MeasureScratch msr;
   InjectTables inj;
   SpectraTables spc;
+  FrameTables frm;
   // whose launches the captured graphs contain: bit 0 the source's, bit 1 + k those of end-of-step hook k (stages.cpp hooks)
   uint32_t in_graphs = 0;
   CorrelationTables cor;

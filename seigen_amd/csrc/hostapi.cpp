@@ -341,9 +341,167 @@ bool injector_symmetric(const InjectorPlan& pl, int dim, int what, int64_t nstep
   return true;
 }
 
+FramePlan frame_plan(const sg_config& cfg, int gw, int ncls, const sg_frame& fr) {
+  FramePlan p;
+  const int d = cfg.dim;
+  p.dim = d;
+  p.gw = gw;
+  p.ncls = ncls;
+  int nfree = 0;
+  p.owns = true;
+  for (int a = 0; a < d; ++a) {
+    if (fr.fixed[a] != 0 && fr.fixed[a] != 1) return p.err = "sg_frame: fixed[a] is 0 or 1", p;
+    p.fixed[a] = fr.fixed[a];
+    if (!fr.fixed[a]) {
+      if (fr.m[a] < 1 || fr.m[a] > FRAME_MAX_M) return p.err = "sg_frame: m[a] outside 1 .. 8", p;
+      p.m[a] = fr.m[a];
+      p.P[a] = (int64_t)cfg.n[a] * fr.m[a];
+      p.Q *= fr.m[a];
+      nfree += 1;
+      continue;
+    }
+    // the candidates of locate_point for this axis, in its order; the first whose fraction passes its tests wins
+    const double t = (fr.at[a] - cfg.origin[a]) / cfg.h[a];
+    if (!(std::fabs(t) < 1e15)) return p.err = "sg_frame: at[a] is not a coordinate", p;
+    const int64_t i = (int64_t)std::floor(t);
+    int64_t cand[2];
+    int nc = 0;
+    if (std::fabs(t - std::nearbyint(t)) < 1e-9 && i - 1 >= 0) cand[nc++] = i - 1;
+    if (i >= 0) cand[nc++] = i;
+    int64_t g = -1;
+    for (int k = 0; k < nc && g < 0; ++k) {
+      const double tf = t - (double)cand[k];
+      if (tf >= -1e-12 && tf <= 1.0 + 1e-12) g = cand[k];
+    }
+    if (g >= 0) p.t_fixed[a] = t - (double)g;   // (the fraction belongs to the mesh's layer, whichever block holds it)
+    const int64_t l = g - cfg.cube0[a];
+    if (g < 0 || l < 0 || l >= cfg.n[a]) {
+      p.owns = false;
+      continue;
+    }
+    p.layer[a] = (int32_t)l;
+  }
+  if (nfree == 0) return p.err = "sg_frame: no free axis", p;
+  if (p.Q > FRAME_MAX_Q) return p.err = "sg_frame: more than 64 pixels in a cube", p;
+  if (!p.owns) {
+    for (int a = 0; a < 3; ++a) p.layer[a] = -1;
+    return p;
+  }
+  // the groups that hold a cube of the layer: the cubes in ascending order, hence the groups too
+  int lo[3] = {0, 0, 0}, hi[3] = {1, 1, 1};
+  for (int a = 0; a < d; ++a) {
+    lo[a] = p.fixed[a] ? p.layer[a] : 0;
+    hi[a] = p.fixed[a] ? p.layer[a] + 1 : cfg.n[a];
+  }
+  const int64_t n0 = cfg.n[0], n1 = d > 1 ? cfg.n[1] : 1;
+  int64_t ncubes = 0;
+  for (int c2 = lo[2]; c2 < hi[2]; ++c2)
+    for (int c1 = lo[1]; c1 < hi[1]; ++c1)
+      for (int c0 = lo[0]; c0 < hi[0]; ++c0) {
+        const int64_t group = (c0 + n0 * (c1 + n1 * c2)) / gw;
+        if (p.groups.empty() || p.groups.back() != (int32_t)group) p.groups.push_back((int32_t)group);
+        ncubes += 1;
+      }
+  if (gw == 1) {
+    p.units = ncubes * p.Q;
+    p.grid = std::min((p.units + FRAME_THREADS - 1) / FRAME_THREADS, FRAME_GRID_CAP);
+  } else {
+    const int64_t per_wave = 64 / gw;
+    p.units = (((int64_t)p.groups.size() + per_wave - 1) / per_wave) * ncls;
+    p.grid = std::min((p.units + FRAME_THREADS / 64 - 1) / (FRAME_THREADS / 64), FRAME_GRID_CAP);
+  }
+  return p;
+}
+
+bool frame_weights(const sg_config& cfg, int degree, const FramePlan& p, int32_t* cls, double* xi, double* phi, std::string* err) {
+  sg_config unit;
+  std::memset(&unit, 0, sizeof(unit));
+  unit.dim = cfg.dim;
+  unit.degree = degree;
+  unit.diagonal = cfg.diagonal;
+  for (int a = 0; a < 3; ++a) {
+    unit.n[a] = 1;
+    unit.h[a] = 1.0;
+  }
+  NodeGeom G;
+  if (!G.init(&unit, degree)) return *err = "sg_frame: no such element", false;
+  const int d = cfg.dim;
+  const int kind = cfg.diagonal == SG_DIAGONAL_QUAD ? KIND_TENSOR : KIND_SIMPLEX;
+  const int nd = G.nq;
+  for (int q = 0; q < p.Q; ++q) {
+    double t[3] = {0, 0, 0}, x[3] = {0, 0, 0};
+    for (int a = 0; a < d; ++a) t[a] = p.fraction(q, a);
+    const int64_t cell = locate_point(G, t, x);
+    if (cell < 0) return *err = "sg_frame: a pixel lies in no cell of its cube", false;
+    cls[q] = (int32_t)cell;   // (one cube: the cell is the class)
+    for (int a = 0; a < d; ++a) xi[(size_t)q * d + a] = x[a];
+    tabulate(d, degree, 1, x, phi + (size_t)q * nd, kind);
+  }
+  return true;
+}
+
+// what the device-free frame exports check of a configuration, and the layout's group width and classes sg_create would choose
+static bool frame_config(const sg_config* cfg, const sg_frame* fr, int* gw, int* ncls) {
+  if (!cfg || !fr || cfg->dim < 1 || cfg->dim > 3) return false;
+  for (int a = 0; a < cfg->dim; ++a)
+    if (cfg->n[a] < 1 || !(cfg->h[a] > 0.0)) return false;
+  const bool quad = cfg->diagonal == SG_DIAGONAL_QUAD;
+  if (quad && cfg->dim == 1) return false;
+  *gw = family_gw(choose_kernel_path(*cfg));
+  *ncls = quad ? 1 : (cfg->dim == 1 ? 1 : (cfg->dim == 2 ? 2 : 6));
+  return true;
+}
+
 extern "C" {
 
 int sg_abi_version(void) { return SG_ABI_VERSION; }
+
+int sg_frame_plan(const sg_config* cfg, const sg_frame* fr, int64_t out[12]) {
+  int gw = 1, ncls = 1;
+  if (!out || !frame_config(cfg, fr, &gw, &ncls)) return SG_ERR_ARG;
+  const FramePlan p = frame_plan(*cfg, gw, ncls, *fr);
+  if (!p.err.empty()) {
+    g_create_err = p.err;
+    return SG_ERR_ARG;
+  }
+  for (int a = 0; a < 3; ++a) {
+    out[a] = p.P[a];
+    out[5 + a] = p.layer[a];
+  }
+  out[3] = p.Q;
+  out[4] = p.owns ? 1 : 0;
+  out[8] = (int64_t)p.groups.size();
+  out[9] = p.units;
+  out[10] = p.grid;
+  out[11] = gw;
+  return SG_OK;
+}
+
+int64_t sg_frame_groups(const sg_config* cfg, const sg_frame* fr, int32_t* groups, int64_t max_groups) {
+  int gw = 1, ncls = 1;
+  if (!frame_config(cfg, fr, &gw, &ncls)) return SG_ERR_ARG;
+  const FramePlan p = frame_plan(*cfg, gw, ncls, *fr);
+  if (!p.err.empty()) {
+    g_create_err = p.err;
+    return SG_ERR_ARG;
+  }
+  if (groups) {
+    if ((int64_t)p.groups.size() > max_groups) return SG_ERR_ARG;
+    std::copy(p.groups.begin(), p.groups.end(), groups);
+  }
+  return (int64_t)p.groups.size();
+}
+
+int sg_frame_weights(const sg_config* cfg, int degree, const sg_frame* fr, int32_t* cls, double* xi, double* phi) {
+  int gw = 1, ncls = 1;
+  if (!cls || !xi || !phi || degree < 1 || degree > 8 || !frame_config(cfg, fr, &gw, &ncls)) return SG_ERR_ARG;
+  const FramePlan p = frame_plan(*cfg, gw, ncls, *fr);
+  if (!p.err.empty() || !frame_weights(*cfg, degree, p, cls, xi, phi, &g_create_err)) {
+    if (!p.err.empty()) g_create_err = p.err;
+    return SG_ERR_ARG;
+  }
+  return SG_OK;
+}
 
 int sg_spectra_clock(int64_t every, int64_t nsamples, int64_t steps, int64_t more, int64_t out[4]) {
   if (!out || every < 1 || nsamples < 0 || steps < 0 || more < 0) return SG_ERR_ARG;

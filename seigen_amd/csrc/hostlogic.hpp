@@ -1,6 +1,6 @@
 // Host logic of libseigen_hip that needs no device and no HIP header: which kernel family runs a block, the layout of its
 // fields, the six stages of an LF4 step, the boxes and items of the regions of a split stage, node coordinates of a block,
-// point location, the receiver plan and the injector plan.  Defined in hostapi.cpp, which - with refelem.cpp, mesh_tables.cpp, mfma_tables.cpp,
+// point location, the receiver plan, the injector plan, the transfer plan and the frame plan.  Defined in hostapi.cpp, which - with refelem.cpp, mesh_tables.cpp, mfma_tables.cpp,
 // sponge_tables.cpp and source_tables.cpp - also builds on its own for the CPU sanitizer target (`make host-asan`).
 #pragma once
 #include <algorithm>
@@ -428,3 +428,37 @@ inline XferPlan xfer_plan(int gw, int ncls, int nd, int ncomp, int dev_bytes, in
   p.grid = std::min(p.units, XFER_GRID_CAP);
   return p;
 }
+
+// Frames (seigen_hip.h sg_get_frame_dev; frame.cpp, kernels_frame.hip): a field rastered on a pixel lattice commensurate with
+// the block's cubes.  Along a FREE axis a every cube holds m[a] pixels, pixel j of a cube at the cube fraction (j + 1/2) / m[a];
+// a FIXED axis is the single plane x_a = at[a]: one layer of cubes and one fraction in it.  The Q = prod m[a] (free axes)
+// in-cube pixels have the same cell class and reference coordinates in every cube, so the weights are one table [Q][nd].
+// frame_plan states, for the launch wrapper and sg_frame_plan alike, the extents, the fractions, whether this block holds the
+// layer of every fixed axis, the listed GROUPS of gw cubes (those with a cube in the layer; all of them without a fixed axis)
+// and the launch: a wave takes 64 cubes - 64 / gw listed groups - of one class and one output component at a time (gw = 1: a
+// thread per (listed cube, in-cube pixel)), the component is the grid's second dimension, the first strides over the rest
+// beyond its cap.
+static constexpr int FRAME_MAX_M = 8, FRAME_MAX_Q = 64, FRAME_THREADS = 256;
+static constexpr int64_t FRAME_GRID_CAP = SG_FRAME_GRID_CAP;
+struct FramePlan {
+  int dim = 0, gw = 1, ncls = 1;
+  int32_t m[3] = {1, 1, 1};       // in-cube pixels per axis (1 along a fixed axis and beyond dim)
+  int32_t fixed[3] = {0, 0, 0};
+  int32_t layer[3] = {-1, -1, -1};   // block-local cube layer of a fixed axis; -1: a free axis
+  double t_fixed[3] = {0, 0, 0};  // the cube fraction of a fixed axis
+  int64_t P[3] = {1, 1, 1};       // extents in pixels
+  int Q = 1;
+  bool owns = false;              // every fixed axis' layer lies in this block
+  std::vector<int32_t> groups;    // listed groups, ascending (empty where !owns)
+  int64_t units = 0;              // waves' (chunk of 64 cubes, class) units; gw = 1: (listed cube, in-cube pixel) threads
+  int64_t grid = 0;               // blocks of FRAME_THREADS threads along x (0: nothing to launch)
+  std::string err;                // why the frame is refused (then nothing else is valid)
+  // the cube fraction of in-cube pixel q along axis a, and q's digit there
+  int digit(int q, int a) const { return a == 0 ? q % m[0] : (a == 1 ? q / m[0] % m[1] : q / (m[0] * m[1])); }
+  double fraction(int q, int a) const { return fixed[a] ? t_fixed[a] : ((double)digit(q, a) + 0.5) / (double)m[a]; }
+};
+FramePlan frame_plan(const sg_config& cfg, int gw, int ncls, const sg_frame& fr);
+// cls[Q], xi[Q][dim], phi[Q][nd] of the plan's in-cube pixels: locate_point on the unit block of the configuration's cell kind
+// (n = 1, h = 1, origin = 0, cube0 = 0) at the pixel's cube fractions, and the receivers' tabulate at those coordinates.
+// False (with *err) where a pixel lies in no class.
+bool frame_weights(const sg_config& cfg, int degree, const FramePlan& p, int32_t* cls, double* xi, double* phi, std::string* err);

@@ -434,4 +434,31 @@ int launch_xfer(int gw, int ncls, int nd, int ncomp, int dim, int dir, void* fie
                 int sym, int* flag, int f32, int c32, int64_t item0, int64_t units, int slices, int rows_per_slice, int pitch,
                 int grid, size_t lds_bytes, void* stream);
 
+// Frames (kernels_frame.hip; seigen_hip.h sg_get_frame_dev): one field rastered on the pixel lattice of hostlogic.hpp FramePlan.
+// In-cube pixel q = j0 + m0 * (j1 + m1 * j2) of cube (c0, c1, c2) is output pixel p_a = fixed[a] ? 0 : c_a * m[a] + j_a and
+//   out[c * stride[0] + p2 * stride[1] + p1 * stride[2] + p0 * stride[3]] = sum_a phi[q][a] field[cell(cube, cls[q])][a][c']
+// over a ascending, in double with fma from zero (c' = c, or the mirror of an (i > j) stress entry where sym).
+// What a frame specification fixes for every launch lives on the device beside its tables (the kernels take plain pointers
+// and scalars: nothing by value but those):
+struct FrameSpec {
+  int64_t ngroups;         // the listed groups of gw cubes
+  int64_t units;           // gw > 1: (chunk of 64 / gw listed groups, class); gw = 1: (listed cube, in-cube pixel)
+  int64_t ncube;
+  int32_t n[3], m[3], fixed[3], layer[3];   // (n, m = 1 beyond dim)
+  int32_t Q, nd, ncls, gw, dim, pad_;
+};
+struct FrameTablePtrs {    // device pointers, gathered for the launch wrapper
+  const FrameSpec* spec;
+  const int32_t* cls;      // [Q] the class of in-cube pixel q
+  const int32_t* order;    // [Q] the in-cube pixels sorted by class (ascending q within a class)
+  const int32_t* cstart;   // [ncls + 1] the pixels of class k are order[cstart[k] .. cstart[k + 1] - 1]
+  const double* phi;       // [Q][nd]
+  const int32_t* groups;   // [ngroups] ascending
+};
+// field: the buffer of a field with ncomp components (float where f32), out: the caller's (float where c32), stride = comp,
+// axis 2, axis 1, axis 0 in elements; gw, units and grid (blocks of 256 threads along x; the grid's y is the component) are
+// the plan's
+int launch_frame(const void* field, void* out, const FrameTablePtrs& t, int gw, int64_t units, int ncomp, int sym,
+                 const int64_t stride[4], int f32, int c32, int grid, void* stream);
+
 }  // namespace sg

@@ -193,6 +193,8 @@ class ElasticLF4(object):
             self._monitor_times = []
             self._spectra = None            # (freqs, every, nsamples, what, window) of set_spectra
             self._spectra_freqs = None      # the frequencies armed by the last run
+            self._frames = None             # (function, m, slice, every, dtype) of set_frames
+            self._frame_stack = None        # the frames of the last run
             self._injected = []             # what inject / set_injectors have added, for rewind (see _position)
             self._armed = None              # the armed series' entries still to be logged
             self._rewound = 0               # steps re-wound so far
@@ -769,6 +771,47 @@ class ElasticLF4(object):
     def reset_correlation(self):
         self._block.reset_correlation()
 
+    # ---- frames: images of the wavefield taken inside the time loop (sg_get_frame_dev) ----------------
+    def set_frames(self, function="velocity", m=1, slice=None, every=1, dtype=None):
+        """Take a frame of `function` ("velocity" = VelocityNew or "stress" = StressNew; Function.frame has `m` and `slice`)
+        after every `every`-th step of the next runs: frame j after step (j + 1) * every, into one pre-allocated torch
+        tensor [nframes, ...] on the device (`dtype`: torch.float64, the default, or torch.float32), which frames() returns.
+        The run advances in chunks of `every` steps, a frame queued behind each; the remaining steps follow at the end.
+        function = None: no frames, and run takes the path it takes without this call.  Single-rank meshes only."""
+        if function is None:
+            self._frames = None
+            self._frame_stack = None
+            return
+        if function not in ("velocity", "stress"):
+            raise ValueError("frames are taken of 'velocity' or 'stress', not %r" % (function,))
+        if int(every) < 1:
+            raise ValueError("set_frames: every >= 1")
+        if self.output:
+            raise ValueError("set_frames: not with output=True, whose loop writes a file per step")
+        if self.mesh.partition.world > 1:
+            raise NotImplementedError("set_frames: single-rank meshes only (the blocks of a partitioned mesh hold parts of the image)")
+        self._frames = (function, m, None if slice is None else dict(slice), int(every), dtype)
+        self._frame_stack = None
+
+    def frames(self):
+        """The frames of the last run: a torch tensor [nframes] + Function.frame's shape on the device."""
+        if self._frame_stack is None:
+            raise RuntimeError("no frames: call set_frames before run")
+        return self._frame_stack
+
+    def _advance_with_frames(self, nsteps):
+        import torch
+        function, m, slice, every, dtype = self._frames
+        field = _lib.FIELD_U if function == "velocity" else _lib.FIELD_S
+        blk = self._block
+        nframes = nsteps // every
+        self._frame_stack = torch.empty((nframes,) + blk.frame_shape(field, m, slice), dtype=dtype or torch.float64, device=blk._torch_device())
+        for j in range(nframes):
+            self._advance(every)
+            blk.get_frame_dev(field, m=m, slice=slice, out=self._frame_stack[j])
+        if nsteps - nframes * every:
+            self._advance(nsteps - nframes * every)
+
     # ---- time loop (elastic.py:267-315) ----------------------------------------------------------
     def step_times(self, T):
         """The values of `t` visited by the reference loop ``t = dt; while t <= T + 1e-12``."""
@@ -819,6 +862,8 @@ class ElasticLF4(object):
                         log("t = %f" % t)
                         self._advance(1)
                         self.write(self.u1, self.s1)
+                elif self._frames is not None:
+                    self._advance_with_frames(len(times))
                 else:
                     # the eight solves + two assigns of every step, without returning to Python
                     self._advance(len(times))

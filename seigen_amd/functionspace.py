@@ -249,6 +249,14 @@ class Function(object):
         block, field = self._bound("to_torch")
         return block.get_field_dev(field, out=out, dtype=dtype)
 
+    def frame(self, m=1, slice=None, out=None, dtype=None):
+        """The values rastered on a pixel lattice aligned with the mesh's cubes, as a torch tensor value_shape + (P_{d-1},
+        ..., P_0) on the solver's device: `m` pixels per cube (an int or a per-axis tuple), `slice` = {axis: coordinate} for
+        a plane of a 3-D field (that axis is dropped).  Interpolated on the device in the element's own basis and queued
+        like to_torch: no host copy, no host wait (HipBlock.get_frame_dev)."""
+        block, field = self._bound("frame")
+        return block.get_frame_dev(field, m=m, slice=slice, out=out, dtype=dtype)
+
     def from_torch(self, t):
         """Set the values from a contiguous float64 or float32 tensor [cells, nodes] + value_shape of the solver's device,
         moved on the device (a stress handed to a block in symmetric storage makes the host wait once)."""
