@@ -14,8 +14,21 @@ with different summation orders, whose difference per checkpoint is the round-of
 The C port has no un-fused operator with a sponge, so the apply_F / apply_G operations are mirrored with numpy in both (they
 write the two work fields only, which every step overwrites: the state and the floor do not depend on them).
 
-Nothing here needs a GPU.  Point location and the basis at a receiver are the library's device-free entry points
-(sg_locate_points, sg_tabulate_cell), through tests/test_receivers_gpu.py _locate_on as in its host_samples."""
+A second script (make_hooks_script; tests/test_lifetime_hooks_gpu.py) reaches what the first stops short of: the other three
+end-of-step hooks - monitor, spectra, injectors - armed, re-armed and disarmed beside the receivers, the writers of the fields
+outside the stages (sg_inject, an injector series, sg_set_field_dev, sg_leave_sym) and the readers queued on the stream
+(sg_measure, sg_get_field_dev, sg_get_spectrum_dev, sg_get_frame_dev).  The mirror takes their meaning from the header as
+well: an injection adds amp * psi to the owning cells, summed per cell in the order listed; entry k of a series goes in at the
+END of step k + 1 counted from the arming call, behind that step's receiver, monitor and spectra samples; a monitor sample
+is { U2, S2, T2, EK, ES } as tests/test_monitor_gpu.py host_sample states it; the spectra add w[j][f] * field after step
+(j + 1) * every; every clock counts from its own arming call and no other call resets it; a frame is tests/frame_cases.py
+host_frame of the field.  Injections are applied in numpy between the steps of either engine.  Its round-off floor is
+tests/golden/lifetime_hooks_floor.json.
+
+Nothing here needs a GPU or torch (a device tensor is made only where the target is a HipBlock).  Point location, the basis
+at a receiver and the weights of an injector are the library's device-free entry points (sg_locate_points, sg_tabulate_cell,
+sg_injector_weights - checked on its own in tests/test_injectors_host.py), the first two through tests/test_receivers_gpu.py
+_locate_on as in its host_samples."""
 import collections
 import types
 
@@ -138,6 +151,20 @@ def receiver_basis(case, pts):
     return cell, phi
 
 
+def case_cfg(case):
+    """the sg_config of a case's block, for the library's device-free entry points (tests/frame_cases.py block_cfg)"""
+    from tests.frame_cases import block_cfg
+    return block_cfg(case.dim, case.degree, case.n, case.cell)
+
+
+def injector_points(case):
+    """three points: two inside one cell of the second cube along x, one on the grid line x = 2 h (the lower cell's)"""
+    d, n = case.dim, np.array(case.n, dtype=np.float64)
+    p0 = (np.array([1.0, 0.0, 0.0])[:d] + np.array([0.35, 0.2, 0.1])[:d]) / n
+    p2 = (np.array([2.0, 0.0, 0.0])[:d] + np.array([0.0, 0.45, 0.15])[:d]) / n
+    return np.stack([p0, p0 + 0.02 / n, p2])
+
+
 # ---- the script -----------------------------------------------------------------------------------------------------------
 
 def _stress(shape, rng, sym):
@@ -161,8 +188,8 @@ def _sponge(m, ncls, q, rng):
 
 
 class _Builder(object):
-    def __init__(self, case, rng, omit):
-        self.case, self.rng, self.omit = case, rng, omit
+    def __init__(self, case, rng, omit, tags=None):
+        self.case, self.rng, self.omit, self.tags = case, rng, omit, TAGS if tags is None else tags
         self.ops = []
         self.stretch = 0
         self.nc = int(np.prod(case.n)) * ncls_of(case)
@@ -172,11 +199,12 @@ class _Builder(object):
         self.symmetric = case.sym        # the data handed over so far is symmetric
 
     def add(self, op, tag, **args):
+        assert tag in self.tags, tag
         args["tag"] = tag
         self.ops.append((op, args))
 
     def wants(self, tag):
-        assert tag in TAGS, tag
+        assert tag in self.tags, tag
         return tag not in self.omit
 
     def step(self, n, tag):
@@ -351,20 +379,230 @@ def make_script(case, seed=0):
     return b.ops
 
 
+# ---- the second script: the other end-of-step hooks, the injections and the device transfers -------------------------------
+
+# The transitions of make_hooks_script by tag, with the rule of TAGS / OMITTED: nothing in it depends on the family.
+HOOK_TAGS = ("fresh", "arm.monitor", "arm.spectra", "arm.injectors", "order", "size.classes", "readers", "runout.spectra",
+             "rearm.spectra", "dev.upload", "runout.injectors", "rearm.injectors", "monitor.full", "rearm.monitor", "dev.range",
+             "inject.sponge", "sym.leave", "clock.source", "clock.params", "step.host", "sym.again", "inject.replay",
+             "step.timing", "disarm.monitor", "disarm.spectra", "disarm.injectors")
+HOOKS_OMITTED = {}
+HOOK_SETTERS = ("set_monitor", "set_spectra", "set_injectors", "inject", "set_field_dev", "leave_sym")
+# how a case leaves symmetric-stress storage in the second script, in turn over the cases
+SYM_LEAVERS = ("set_field_dev", "set_injectors", "leave_sym")
+LARGE_ENTRY = 10.0          # the factor of the injector entry that lands on the step all hooks sample ("order")
+
+
+def frames_of(case):
+    """(field, m, slice) of the frames read in mid-run: in 3-D a plane slice on a grid plane and one inside a cube, else the
+    raster of the mesh"""
+    if case.dim == 3:
+        return [(FIELD_U, (2, 2, 1), {2: 1.0 / case.n[2]}), (FIELD_S, (1, 2, 2), {0: 2.5 / case.n[0]})]
+    m = (2, 3) if case.dim == 2 else 4
+    return [(FIELD_U, m, None), (FIELD_S, m, None)]
+
+
+def make_hooks_script(case, seed=0):
+    """The second lifetime of a handle of `case`: monitor, spectra and injectors armed, re-armed and disarmed beside the
+    receivers on a handle that holds graphs, a pre-pass and running counters; fields written by sg_inject, an injector series
+    and sg_set_field_dev between stepping calls; readers queued on the stream in mid-run.  78 steps; the absolute step at which
+    each call is made stands in the comments (tests/test_lifetime_oracle.py walks them)."""
+    import zlib
+    from seigen_amd.backend import injector_weights
+    rng = np.random.default_rng([seed, zlib.crc32(case.name.encode()), 1])
+    b = _Builder(case, rng, HOOKS_OMITTED.get(case.name, {}), HOOK_TAGS)
+    m = case_mesh(case)
+    assert m.ncells == b.nc
+    d, P, nc, nd, ncls = case.dim, case.degree, b.nc, b.nd, ncls_of(case)
+    dt = 0.04 * min(1.0 / k for k in case.n) / P ** 2
+    lam_c, mu_c = rng.uniform(0.4, 0.8, nc), rng.uniform(0.2, 0.4, nc)
+    turn = CASES.index(case) % 3
+    pts, ipts = receiver_points(case), injector_points(case)
+    icell, psi = injector_weights(case_cfg(case), ipts, nd)
+    assert icell[0] == icell[1] >= 0 and icell[2] >= 0
+    unit = 0.1 / np.abs(psi).max()                        # an entry moves a nodal value by 0.1 at the most, the large one by 1
+    mid = (nc // 2) // ncls * ncls + (1 if ncls > 1 else 0)     # a cell in the middle of a cube's classes
+    triple = np.array([0.55, 1.0, -0.5 / (d * 0.5 + 0.5)])      # rho / 2, 1 / (4 mu), -lambda / (4 mu (d lambda + 2 mu))
+    rho_c = rng.uniform(0.5, 2.0, nc)
+    per_cell = np.stack([rho_c / 2.0, 1.0 / (4.0 * mu_c), -lam_c / (4.0 * mu_c * (d * lam_c + 2.0 * mu_c))], axis=-1)
+
+    def amps(entries, what):
+        parts = []
+        if what & 1:
+            parts.append(rng.uniform(-1, 1, (entries, 3, d)))
+        if what & 2:
+            parts.append(_stress((entries, 3, d, d), rng, b.symmetric).reshape(entries, 3, d * d))
+        return unit * np.concatenate(parts, axis=-1)
+
+    def weights(nsamples):
+        return rng.uniform(-1, 1, (nsamples, 2)) + 1j * rng.uniform(-1, 1, (nsamples, 2))
+
+    def read_hooks(tag):
+        b.add("get_receivers", tag)
+        b.add("get_monitor", tag)
+        b.add("spectra_samples", tag)
+        for field, freq in ((0, 0), (1, 1)):
+            b.add("get_spectrum", tag, field=field, freq=freq)
+
+    # 1. a fresh handle with no hook: every size class (eager, the first capture, graph8 + graph1, graph8)        steps 0 .. 20
+    b.add("set_params", "fresh", density=1.1, dt=dt, lam=0.5, mu=0.25)
+    b.add("kernels", "fresh")
+    b.upload_state("fresh")
+    for n in (1, 2, 9, 8):
+        b.step(n, "fresh")
+    b.upload_state("fresh")
+    # (the sponge for the rest of the script; the injectors' cells absorb - general nodal sigma - whatever kind their turn
+    # gives them: a velocity added there changes what the pre-pass holds)
+    sigma = _sponge(m, ncls, 4, rng)
+    own = np.unique(icell)
+    sigma[own] = rng.uniform(5.0, 30.0, size=(len(own), sigma.shape[1]))
+    b.add("set_absorption", "fresh", sigma=sigma, degree=4)
+
+    # 2. the hooks armed one call after the other on the handle that holds those graphs, a replay after each      20 .. 27
+    b.add("set_receivers", "arm.monitor", points=pts, what=3, every=2, capacity=40)
+    b.add("set_monitor", "arm.monitor", every=1, capacity=35, w=triple)                    # full after step 55
+    b.step(2, "arm.monitor")
+    b.add("set_spectra", "arm.spectra", wu=weights(18), ws=weights(18), every=1)             # armed at 22: the last sample at 40
+    b.step(2, "arm.spectra")
+    series = amps(25, 3)                                                                     # armed at 24: the last entry at 49
+    series[3] *= LARGE_ENTRY                                                                 # ... and entry 3 at the end of step 28
+    b.add("set_injectors", "arm.injectors", points=ipts, series=series, what=3)
+    b.step(3, "arm.injectors")
+
+    # 3. the order inside a step: step 28 is a sample step of the receivers (every 2 from 20), the monitor and the spectra,
+    # and the large entry lands at its end; then the size classes with every hook running                           27 .. 45
+    b.step(1, "order")
+    read_hooks("order")
+    b.step(8, "size.classes")
+    b.step(9, "size.classes")                      # the spectra's series runs out at step 40, inside this call
+
+    # 4. readers queued on the stream between two replays; the second replay must add nothing to the spectra      45 .. 47
+    b.add("measure", "readers", w=per_cell)
+    b.add("measure", "readers", w=None)
+    few = min(3, nc - mid)
+    for field in (FIELD_U, FIELD_S):
+        b.add("get_field_dev", "readers", field=field, cell0=mid, ncells=few)
+    for field, freq in ((0, 1), (1, 0)):
+        b.add("get_spectrum_dev", "readers", field=field, freq=freq)
+    for field, mm, sl in frames_of(case):
+        b.add("get_frame_dev", "readers", field=field, m=mm, slice=sl)
+    b.step(2, "runout.spectra")
+    read_hooks("runout.spectra")
+
+    # 5. the spectra armed again with another `every` beside the running monitor and injectors; both fields from device
+    # buffers between two replays (the sponge is set: a pre-pass of the old velocity must not be reused); the injectors'
+    # series runs out at step 49 inside the replay, the next adds nothing                                            47 .. 52
+    b.add("set_spectra", "rearm.spectra", wu=weights(20), ws=weights(20), every=2)         # samples after 49, 51, .. 85
+    b.add("set_field_dev", "dev.upload", field=FIELD_U, cell0=0, values=rng.uniform(-1, 1, b.ushape))
+    b.add("set_field_dev", "dev.upload", field=FIELD_S, cell0=0, values=_stress(b.sshape, rng, b.symmetric))
+    b.stretch = 0
+    b.step(3, "dev.upload")
+    b.step(2, "runout.injectors")
+
+    # 6. a stress series armed beside the running monitor and spectra; the monitor's trace exactly full at step 55, read,
+    # and armed again with another `every` and weights per cell                                                      52 .. 55
+    b.add("set_injectors", "rearm.injectors", points=ipts, series=amps(30, 2), what=2)
+    b.step(3, "rearm.injectors")
+    b.add("get_monitor", "monitor.full")
+    b.add("set_monitor", "rearm.monitor", every=3, capacity=12, w=per_cell)              # samples after 58, 61, .. 70
+
+    # 7. under the sponge, between eager single steps: a few velocity cells from a device buffer, then a velocity injection -
+    # the pre-pass the step before left is stale both times                                                          55 .. 58
+    b.step(1, "dev.range")
+    b.add("set_field_dev", "dev.range", field=FIELD_U, cell0=mid, values=rng.uniform(-1, 1, (few,) + b.ushape[1:]))
+    b.step(1, "dev.range")
+    b.add("inject", "inject.sponge", points=ipts, amp=amps(1, 1)[0], what=1)
+    b.step(1, "inject.sponge")
+
+    # 8. leaving symmetric-stress storage with stress spectra armed and graphs captured, in turn over the cases by a few
+    # stress cells from a device buffer, by a stress series that is not symmetric, by sg_leave_sym                   58 .. 60
+    b.add("get_spectrum", "sym.leave", field=1, freq=0)
+    b.add("kernels", "sym.leave")
+    b.symmetric = False
+    if SYM_LEAVERS[turn] == "set_field_dev":
+        b.add("set_field_dev", "sym.leave", field=FIELD_S, cell0=mid, values=_stress((min(2, nc - mid),) + b.sshape[1:], rng, False))
+    elif SYM_LEAVERS[turn] == "set_injectors":
+        b.add("set_injectors", "sym.leave", points=ipts, series=amps(24, 2), what=2)
+    else:
+        b.add("leave_sym", "sym.leave")
+    b.add("kernels", "sym.leave")
+    b.step(2, "sym.leave")
+    b.add("get_spectrum", "sym.leave", field=1, freq=0)
+
+    # 9. every clock keeps its own count: a source set while the injectors run, sg_set_params with another dt while all
+    # hooks run                                                                                                        60 .. 64
+    nodes = b.nodes(7)
+    b.add("set_source", "clock.source", nodes=nodes, values=_stress((5, len(nodes), d, d), rng, False), static=False)
+    b.step(2, "clock.source")
+    b.add("set_params", "clock.params", density=0.9, dt=0.8 * dt, lam=lam_c, mu=mu_c)
+    b.step(2, "clock.params")
+
+    # 10. the other ways of stepping among the replays, all hooks armed: two host-driven steps, a replay (sg_leave_sym on a
+    # block that has left, and an injection of both fields, in front of it), a timed eager call, a replay            64 .. 72
+    b.host_steps(2, "step.host")
+    b.add("leave_sym", "sym.again")
+    b.add("inject", "inject.replay", points=ipts, amp=amps(1, 3)[0], what=3)
+    b.step(2, "inject.replay")
+    b.add("enable_timing", "step.timing", on=True)
+    b.step(2, "step.timing")
+    b.add("enable_timing", "step.timing", on=False)
+    b.step(2, "step.timing")
+    read_hooks("step.timing")
+    b.upload_state("step.timing")
+
+    # 11. each hook disarmed while the others keep running, a replay behind it, and armed again                     72 .. 78
+    b.add("set_monitor", "disarm.monitor", every=0, capacity=0, w=None)
+    b.step(2, "disarm.monitor")
+    b.add("get_monitor", "disarm.monitor")
+    b.add("set_monitor", "disarm.monitor", every=2, capacity=4, w=None)
+    b.add("set_spectra", "disarm.spectra", wu=None, ws=None, every=1)
+    b.step(2, "disarm.spectra")
+    b.add("spectra_samples", "disarm.spectra")
+    b.add("set_spectra", "disarm.spectra", wu=weights(3), ws=None, every=1)
+    b.add("set_injectors", "disarm.injectors", points=np.zeros((0, d)), series=None, what=1)
+    b.step(2, "disarm.injectors")
+    b.add("get_receivers", "disarm.injectors")
+    b.add("get_monitor", "disarm.injectors")
+    b.add("get_spectrum", "disarm.injectors", field=0, freq=1)
+    return b.ops
+
+
 # ---- applying it ------------------------------------------------------------------------------------------------------------
 
 def _snapshot(target):
+    """what a checkpoint observes; a mirror is told that one has been taken (it logs its samples by checkpoint)"""
+    getattr(target, "checkpoint", lambda: None)()
     c = target.counters()
     return dict(u=target.get_field(FIELD_U), s=target.get_field(FIELD_S), uh=target.get_field(FIELD_UH),
                 sh=target.get_field(FIELD_SH), steps=c["steps"], launches=list(c["launches"]), sym=target.is_sym(),
                 stretch=getattr(target, "stretch", None))
 
 
+def _copy(x):
+    return None if x is None else list(x)
+
+
+def _host(x):
+    """a device tensor as a numpy array (the copy runs on torch's current stream, which HipBlock has put behind the
+    handle's launch)"""
+    return x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
+
+
+def _device(target, values):
+    """the values as a double tensor on the block's device where the target is a HipBlock - the only place a device tensor
+    is made - and as they are for a mirror"""
+    if not hasattr(target, "_torch_device"):
+        return values
+    import torch
+    return torch.as_tensor(np.ascontiguousarray(values, dtype=np.float64), device=target._torch_device())
+
+
 def run_script(target, script):
     """Apply the script to `target` - a HipBlock, or anything with its method names - and return what can be observed, one
     dict per observing operation: {"i": index in the script, "op", "tag"} and, after a stepping call (a checkpoint), the four
     fields, the counters and is_sym(); after apply_F / apply_G the field written; for get_receivers the samples; for
-    kernels the six stage kernel names."""
+    kernels the six stage kernel names; for the readers of the second script what they return, as numpy arrays (and, from a
+    mirror, what the bound of that observation is made from)."""
     seen = []
     for i, (op, a) in enumerate(script):
         obs = None
@@ -403,9 +641,40 @@ def run_script(target, script):
             obs = dict(sh=target.get_field(FIELD_SH))
         elif op == "get_receivers":
             obs = dict(traces=target.get_receivers(), scales=getattr(target, "rec_scales", None),
-                       lebesgue=getattr(target, "rec_lebesgue", None), what=getattr(target, "rec_what", None))
+                       lebesgue=getattr(target, "rec_lebesgue", None), what=getattr(target, "rec_what", None),
+                       log=_copy(getattr(target, "rec_log", None)))
         elif op == "kernels":
             obs = dict(names=[target.stage_kernel_name(st) for st in range(6)])
+        elif op == "leave_sym":
+            target.leave_sym()
+        elif op == "inject":
+            target.inject(a["points"], a["amp"], a["what"])
+        elif op == "set_injectors":
+            obs = dict(owned=np.asarray(target.set_injectors(a["points"], a["series"], a["what"])))
+        elif op == "set_field_dev":
+            target.set_field_dev(a["field"], _device(target, a["values"]), cell0=a["cell0"])
+        elif op == "set_monitor":
+            target.set_monitor(a["every"], a["capacity"], a["w"])
+        elif op == "get_monitor":
+            mon = getattr(target, "mon", None) or {}
+            obs = dict(samples=target.get_monitor(), abs=_copy(mon.get("abs")), log=_copy(mon.get("log")))
+        elif op == "measure":
+            obs = dict(sample=target.measure(a["w"]), abs=getattr(target, "measure_abs", None))
+        elif op == "set_spectra":
+            target.set_spectra(a["wu"], a["ws"], a["every"])
+        elif op in ("get_spectrum", "get_spectrum_dev"):
+            get = target.get_spectrum if op == "get_spectrum" else target.get_spectrum_dev
+            obs = dict(acc=_host(get(a["field"], a["freq"])))
+            if hasattr(target, "spectrum_terms"):
+                obs["terms"] = target.spectrum_terms(a["field"], a["freq"])
+        elif op == "spectra_samples":
+            obs = dict(taken=target.spectra_samples())
+        elif op == "get_field_dev":
+            obs = dict(dev=_host(target.get_field_dev(a["field"], cell0=a["cell0"], ncells=a["ncells"])),
+                       range=target.get_field_range(a["field"], a["cell0"], a["ncells"]), field=a["field"])
+        elif op == "get_frame_dev":
+            obs = dict(frame=_host(target.get_frame_dev(a["field"], a["m"], a["slice"])), field=a["field"],
+                       lebesgue=getattr(target, "frame_lebesgue", None), scale=getattr(target, "frame_scale", None))
         else:
             raise ValueError("unknown operation %r" % (op,))
         if obs is not None:
@@ -443,6 +712,14 @@ class Mirror(object):
         self.steps = 0
         self.stretch, self._fresh = 0, set()
         self._dirty = True
+        # the hooks of make_hooks_script: every sample is logged with (stepping calls completed before its own, steps of
+        # the stretch), what a bound of the fields at that sample is made from
+        self.ncheck = 0
+        self.rec_log = None
+        self.mon = self.spc = self.inj = None
+        self.measure_abs = None
+        self.frame_lebesgue = self.frame_scale = None
+        self._mass = None
 
     # ---- setters: include/seigen_hip.h --------------------------------------------------------------------------------
     def set_params(self, density, dt, lam, mu):
@@ -520,7 +797,7 @@ class Mirror(object):
             return np.zeros(0, dtype=bool)
         cell, phi = receiver_basis(self.case, pts)
         self.rec = dict(cell=cell, phi=phi, what=int(what), every=int(every), capacity=int(capacity), steps=0, samples=[])
-        self.rec_scales, self.rec_what = [], int(what)
+        self.rec_scales, self.rec_log, self.rec_what = [], [], int(what)
         self.rec_lebesgue = float(np.abs(phi[cell >= 0]).sum(axis=1).max()) if (cell >= 0).any() else 0.0
         return cell >= 0
 
@@ -536,6 +813,154 @@ class Mirror(object):
 
     def is_sym(self):
         return self.sym
+
+    def leave_sym(self):
+        self.sym = False
+
+    # ---- writers outside the stages ---------------------------------------------------------------------------------------
+    def set_field_dev(self, field, values, cell0=0):
+        """sg_set_field_dev: the cells from cell0 - the rule of sg_set_field for a stress that is not symmetric; the whole
+        field counts as an upload of it"""
+        values = np.asarray(values, dtype=np.float64)
+        if cell0 == 0 and len(values) == self.ncells:
+            self.set_field(field, values)
+        else:
+            self.set_field_range(field, cell0, values)
+
+    def _injectors(self, points, what):
+        from seigen_amd.backend import injector_weights
+        pts = np.asarray(points, dtype=np.float64).reshape(-1, self.dim)
+        return injector_weights(case_cfg(self.case), pts, self.nd)
+
+    def _amp_leaves_sym(self, cell, amp, what):
+        """"a stress table that is symmetric to the bit (the owned points', every entry) writes the i <= j lines only; one
+        that is not makes THIS block leave symmetric storage at the call"; amp [entries, npts, ncomp]"""
+        if not (what & 2 and self.sym):
+            return
+        d = self.dim
+        t = amp[:, cell >= 0, d if what & 1 else 0:].reshape(len(amp), -1, d, d)
+        if np.any(t != np.swapaxes(t, -1, -2)):
+            self.sym = False
+
+    def _add(self, cell, psi, amp, what):
+        """field[cell][a][c] += sum_r amp[r][c] psi_r[a] over the cell's points r in the order listed; amp [npts, ncomp]"""
+        d = self.dim
+        nu = d if what & 1 else 0
+        for field, lo, hi in ((FIELD_U, 0, nu), (FIELD_S, nu, amp.shape[1])):
+            if hi == lo:
+                continue
+            v = {}
+            for r, c in enumerate(cell):
+                if c >= 0:
+                    v[int(c)] = v.get(int(c), 0.0) + psi[r][:, None] * amp[r, lo:hi][None, :]
+            out = self.f[field].copy()
+            for c, add in v.items():
+                out[c] = out[c] + add.reshape(out[c].shape)
+            self.f[field] = out
+
+    def inject(self, points, amp, what=1):
+        cell, psi = self._injectors(points, what)
+        amp = np.asarray(amp, dtype=np.float64).reshape(len(cell), -1)
+        self._amp_leaves_sym(cell, amp[None], what)
+        self._add(cell, psi, amp, what)
+
+    def set_injectors(self, points, series, what=1):
+        """entry k at the END of step k + 1 counted from this call; re-arming restarts the count; no points or no entries:
+        disarmed"""
+        pts = np.asarray(points, dtype=np.float64).reshape(-1, self.dim)
+        if len(pts) == 0 or series is None or len(series) == 0:
+            self.inj = None
+            return np.zeros(len(pts), dtype=bool)
+        cell, psi = self._injectors(pts, what)
+        series = np.asarray(series, dtype=np.float64).reshape(len(series), len(pts), -1)
+        self._amp_leaves_sym(cell, series, what)
+        self.inj = dict(cell=cell, psi=psi, series=series, what=int(what), steps=0)
+        return cell >= 0
+
+    # ---- monitor ------------------------------------------------------------------------------------------------------------
+    def _sample(self, u, s, w):
+        """{ U2, S2, T2, EK, ES }: tests/test_monitor_gpu.py host_sample, with the forms v^T Mhat v taken cell by cell"""
+        if self._mass is None:
+            from oracle import refelem
+            kind = getattr(self.mesh, "kind", "simplex")
+            xq, wq = refelem.el_quadrature(self.dim, 2 * self.case.degree, kind)
+            phi, _ = refelem.el_tabulate(self.dim, self.case.degree, xq, kind)
+            self._mass = np.einsum('q,qa,qb->ab', wq, phi, phi)
+        M, dj = self._mass, np.abs(self.mesh.detJ)
+        t = np.einsum('cnii->cn', s)
+        s2 = s.reshape(s.shape[0], s.shape[1], -1)
+        Qu = np.einsum('cak,ab,cbk->c', u, M, u)
+        Qs = np.einsum('cak,ab,cbk->c', s2, M, s2)
+        Qt = np.einsum('ca,ab,cb->c', t, M, t)
+        out = [np.sum(dj * Qu), np.sum(dj * Qs), np.sum(dj * Qt), 0.0, 0.0]
+        if w is not None:
+            w = np.broadcast_to(np.asarray(w, dtype=np.float64), (self.ncells, 3))
+            out[3:] = [np.sum(dj * w[:, 0] * Qu), np.sum(dj * (w[:, 1] * Qs + w[:, 2] * Qt))]
+        return np.array(out)
+
+    def measure(self, w=None):
+        """one sample of u and s as they stand now; measure_abs: the same with |w|, the scale of its bound"""
+        self.measure_abs = self._sample(self.f[FIELD_U], self.f[FIELD_S], None if w is None else np.abs(w))
+        return self._sample(self.f[FIELD_U], self.f[FIELD_S], w)
+
+    def set_monitor(self, every, capacity, w=None):
+        """sample j after step (j + 1) * every counted from this call; every = 0 disarms; re-arming discards the samples"""
+        if int(every) == 0:
+            self.mon = None
+            return
+        self.mon = dict(every=int(every), capacity=int(capacity), w=None if w is None else np.array(w, dtype=np.float64), steps=0,
+                        samples=[], abs=[], log=[])
+
+    def get_monitor(self):
+        return np.array(self.mon["samples"]).reshape(-1, 5) if self.mon is not None else np.zeros((0, 5))
+
+    # ---- spectra ------------------------------------------------------------------------------------------------------------
+    def set_spectra(self, wu=None, ws=None, every=1):
+        """acc[f] += w[j][f] * field after step (j + 1) * every counted from this call, for the nsamples rows of the table;
+        arming zeroes the accumulators and restarts the count; no table: disarmed"""
+        if wu is None and ws is None:
+            self.spc = None
+            return
+        w = [None if x is None else np.asarray(x, dtype=np.complex128) for x in (wu, ws)]
+        nsamples, nfreq = next(x for x in w if x is not None).shape
+        shapes = (self.f[FIELD_U].shape, self.f[FIELD_S].shape)
+        self.spc = dict(w=w, every=int(every), nsamples=nsamples, steps=0, log=[],
+                        acc=[None if w[k] is None else np.zeros((nfreq,) + shapes[k], dtype=np.complex128) for k in range(2)])
+
+    def _spectrum_field(self, field):
+        return {0: 0, 1: 1, FIELD_S: 1}[int(field)]
+
+    def get_spectrum(self, field, freq):
+        return self.spc["acc"][self._spectrum_field(field)][freq].copy()
+
+    def get_spectrum_dev(self, field, freq):
+        return self.get_spectrum(field, freq)
+
+    def spectra_samples(self):
+        return len(self.spc["log"]) if self.spc is not None else 0
+
+    def spectrum_terms(self, field, freq):
+        """per sample taken (|w[j][freq]|, stepping calls completed, steps of the stretch, max |field|): the terms of the
+        bound of an accumulator"""
+        k = self._spectrum_field(field)
+        return [(abs(self.spc["w"][k][j][freq]), c, n, (su, ss)[k]) for j, (c, n, su, ss) in enumerate(self.spc["log"])]
+
+    # ---- readers ------------------------------------------------------------------------------------------------------------
+    def get_field_range(self, field, cell0, ncells):
+        return self.f[field][cell0:cell0 + ncells].copy()
+
+    def get_field_dev(self, field, out=None, dtype=None, cell0=0, ncells=None):
+        return self.get_field_range(field, cell0, self.ncells - cell0 if ncells is None else ncells)
+
+    def get_frame_dev(self, field, m=1, slice=None):
+        """tests/frame_cases.py host_frame of the field, the sliced axes dropped as HipBlock.get_frame_dev drops them;
+        frame_lebesgue: the largest sum_a |phi_a| over the pixels; frame_scale: max |field|"""
+        from tests.frame_cases import host_frame
+        img, px = host_frame(case_cfg(self.case), self.case.degree, self.case.cell == _Q, m, slice, self.f[field])
+        self.frame_lebesgue = float(np.abs(px["phi"]).sum(axis=1).max())
+        self.frame_scale = float(np.abs(self.f[field]).max())
+        free = [a for a in reversed(range(self.dim)) if not px["frame"].fixed[a]]
+        return img.reshape(self.f[field].shape[2:] + tuple(px["P"][a] for a in free))
 
     def stage_kernel_name(self, stage):
         return kernel_names(self.case, self.sym)[stage]
@@ -611,14 +1036,40 @@ class Mirror(object):
                     rows.append(np.concatenate(([uu] if r["what"] & 1 else []) + ([ss] if r["what"] & 2 else [])))
                 r["samples"].append(rows)
                 self.rec_scales.append((np.abs(u1).max(), np.abs(s1).max()))
+                self.rec_log.append((self.ncheck, self.stretch))
+        # the other hooks of the one clock, in its order: monitor, spectra, and last the injectors' entry, which belongs to
+        # the step that follows - no sample of this step contains it
+        where = (self.ncheck, self.stretch)
+        m = self.mon
+        if m is not None:
+            m["steps"] += 1
+            if m["steps"] % m["every"] == 0:
+                assert len(m["samples"]) < m["capacity"], "the script overfills the monitor's trace"
+                m["samples"].append(self._sample(u1, s1, m["w"]))
+                m["abs"].append(self._sample(u1, s1, None if m["w"] is None else np.abs(m["w"])))
+                m["log"].append(where)
+        p = self.spc
+        if p is not None:
+            p["steps"] += 1
+            j = p["steps"] // p["every"] - 1
+            if p["steps"] % p["every"] == 0 and j < p["nsamples"]:
+                for k, fld in enumerate((u1, s1)):
+                    if p["w"][k] is not None:
+                        p["acc"][k] = p["acc"][k] + p["w"][k][j].reshape((-1,) + (1,) * fld.ndim) * fld[None]
+                p["log"].append(where + (np.abs(u1).max(), np.abs(s1).max()))
+        q = self.inj
+        if q is not None:
+            k, q["steps"] = q["steps"], q["steps"] + 1
+            if k < len(q["series"]):
+                self._add(q["cell"], q["psi"], q["series"][k], q["what"])
 
     def _stepped(self, n):
         if {FIELD_U, FIELD_S} <= self._fresh:
             self.stretch = 0
         self._fresh = set()
         for _ in range(n):
+            self.stretch += 1
             self._one_step()
-        self.stretch += n
 
     def step(self, nsteps=1):
         self._stepped(int(nsteps))
@@ -630,10 +1081,19 @@ class Mirror(object):
     def end_step(self):
         self._stepped(1)
 
+    def checkpoint(self):
+        self.ncheck += 1
+
 
 def mirror_run(case, engine="numpy", seed=0):
     """(script, what the mirror observes)"""
     script = make_script(case, seed)
+    return script, run_script(Mirror(case, engine), script)
+
+
+def hooks_mirror_run(case, engine="numpy", seed=0):
+    """(the second script, what the mirror observes)"""
+    script = make_hooks_script(case, seed)
     return script, run_script(Mirror(case, engine), script)
 
 
