@@ -803,3 +803,71 @@ def test_every_environment_switch_is_documented():
     names -= {"SEIGEN_HIP_H"}      # the header's include guard
     missing = sorted(n for n in names if n not in doc)
     assert not missing, "not in INTEGRATION.md's table: %s" % missing
+
+
+def _faked_rank_file(single, n, part, cell):
+    """what tests/native_exchange_worker.py saves of a rank, cut out of the single block's fields"""
+    from tests.native_exchange_worker import block_cells
+    idx = block_cells(n, part.start, part.n, cell)
+    return dict({k: v[idx] for k, v in single.items()}, start=np.array(part.start), n=np.array(part.n))
+
+
+@pytest.mark.parametrize("n,grid,cell,nd", [((9,), (3,), "left", 4), ((6, 4), (2, 2), "right", 10), ((6, 4), (2, 2), "quadrilateral", 16),
+                                            ((4, 6, 2), (2, 2, 1), "left", 4), ((4, 6, 2), (2, 2, 1), "quadrilateral", 8)])
+def test_native_exchange_block_comparison_fails_on_a_wrong_block(n, grid, cell, nd):
+    """The bitwise comparison of tests/test_native_exchange_gpu.py (check_rank_fields over block_cells) on faked rank files:
+    it passes for each rank's own cells and fails for a block shifted by one cell, for the block of the transposed grid and
+    for the other cell class - the comparison would not pass by looking at the wrong cells."""
+    from tests.native_exchange_worker import block_cells, cells_per_cube, check_rank_fields
+    dim, world = len(n), int(np.prod(grid))
+    ncells = int(np.prod(n)) * cells_per_cube(dim, cell)
+    rng = np.random.default_rng(5)
+    single = {"u": rng.uniform(-1, 1, (ncells, nd, dim)), "s": rng.uniform(-1, 1, (ncells, nd, dim, dim)),
+              "uh": rng.uniform(-1, 1, (ncells, nd, dim))}
+    parts = [Partition(n, r, world, grid) for r in range(world)]
+    seen = np.concatenate([block_cells(n, p.start, p.n, cell) for p in parts])
+    assert sorted(seen) == list(range(ncells)), "the blocks' cells tile the mesh"
+    for r, p in enumerate(parts):
+        d = _faked_rank_file(single, n, p, cell)
+        check_rank_fields(d, single, n, cell, r)
+        for a in range(dim):      # the start shifted by one cell along an axis (where the block still fits the mesh)
+            start = list(p.start)
+            start[a] += 1 if p.start[a] + p.n[a] < n[a] else -1
+            with pytest.raises(AssertionError):
+                check_rank_fields(dict(d, start=np.array(start)), single, n, cell, r)
+        if dim > 1:
+            other = "left" if cell == "quadrilateral" else "quadrilateral"
+            with pytest.raises((AssertionError, IndexError)):
+                check_rank_fields(d, single, n, other, r)
+    if dim > 1:      # the transposed grid: the ranks counted along y first - rank r then sits at the swapped coordinates
+        tgrid = (grid[1], grid[0]) + tuple(grid[2:])
+        wrong = 0
+        for r in range(world):
+            c = Partition(n, r, world, tgrid).coords
+            q = parts[parts[0].coords_to_rank((c[1], c[0]) + tuple(c[2:]))]
+            d = _faked_rank_file(single, n, parts[r], cell)
+            if (q.start, q.n) == (parts[r].start, parts[r].n):
+                continue
+            wrong += 1
+            with pytest.raises(AssertionError):
+                check_rank_fields(dict(d, start=np.array(q.start), n=np.array(q.n)), single, n, cell, r)
+        assert wrong >= world - 2
+
+
+def test_native_exchange_family_pin_fails_on_another_family():
+    """The family assertion of tests/test_native_exchange_gpu.py on faked kernel names: names of the claimed family pass,
+    one stage of another family - or of the other number type - fails."""
+    from tests.native_exchange_worker import check_family
+    tile = ["sg::tile2d_stage<3, %d, %d, 1, 1, 0, double>" % km for km in ((0, 0), (1, 0), (0, 1), (1, 0), (0, 2), (1, 1))]
+    check_family(np.array(tile), "sg::tile2d_stage<", "double")
+    with pytest.raises(AssertionError):
+        check_family(np.array(tile), "sg::tile2d_stage<", "float")
+    with pytest.raises(AssertionError):
+        check_family(np.array(tile), "sg::lane_stage<")
+    with pytest.raises(AssertionError):
+        check_family(np.array(tile[:5] + ["sg::stage_kernel<2, 3, 1, 1, 1>"]), "sg::tile2d_stage<", "double")
+    with pytest.raises(AssertionError):
+        check_family(np.array(tile[:5]), "sg::tile2d_stage<")
+    # hex_stage and hexm_stage are told apart, as are lane_stage and stage_kernel
+    with pytest.raises(AssertionError):
+        check_family(np.array(["sg::hexm_stage<3, 0, 0, 1, 1>"] * 6), "sg::hex_stage<")

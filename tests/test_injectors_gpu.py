@@ -566,13 +566,13 @@ def fake():
     return build()
 
 
-def test_injectors_on_a_split_block(gpu, fake, tmp_path):
-    """Two ranks over the transport double, the exchange inside the library, ONE sg_step(n): injectors of velocity and stress
-    in a cell touching the cut, on the cut plane itself (the lower block's) and in the interior.  Every rank's fields equal
-    the single block's bit for bit, and every point has one owner."""
-    from injector_exchange_worker import POINTS, series_of
+def _injectors_on_a_split_block(fake, tmp_path, n, grid, degree, steps, cell="left"):
+    """The ranks of `grid` over the transport double (tests/injector_exchange_worker.py), the exchange inside the library,
+    ONE sg_step(n), against the single block here: every rank's fields equal the single block's bit for bit, and every point
+    has one owner.  Returns the ranks' files."""
+    from injector_exchange_worker import points_of, series_of
     from native_exchange_worker import setup_block
-    grid, n, degree, steps, world = (1, 1, 2), (16, 4, 4), 4, 6, 2
+    dim, world = len(n), int(np.prod(grid))
     env = dict(os.environ, SEIGEN_RCCL_LIB=fake, FAKE_RCCL_TIMEOUT_S="60", FAKE_RCCL_LOG=str(tmp_path / "fake"),
                HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2", FAKE_RCCL_ASYNC="1", FAKE_RCCL_SLOT_BYTES="1048576")
     env.pop("FAKE_RCCL_HOST", None)
@@ -580,7 +580,7 @@ def test_injectors_on_a_split_block(gpu, fake, tmp_path):
         env.pop(var, None)
     logs = [open(tmp_path / ("rank%d.log" % r), "w") for r in range(world)]
     procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "injector_exchange_worker.py"), str(tmp_path), str(world),
-                               str(r), ",".join(map(str, grid)), ",".join(map(str, n)), str(degree), str(steps)],
+                               str(r), ",".join(map(str, grid)), ",".join(map(str, n)), str(degree), str(steps), cell],
                               cwd=ROOT, env=env, stdout=logs[r], stderr=subprocess.STDOUT) for r in range(world)]
     deadline = time.time() + 300
     errs = []
@@ -594,19 +594,43 @@ def test_injectors_on_a_split_block(gpu, fake, tmp_path):
         if p.returncode != 0:
             errs.append("rank %d: exit %r\n%s" % (r, p.returncode, open(tmp_path / ("rank%d.log" % r)).read()[-3000:]))
     assert not errs, "\n-----\n".join(errs)
-    blk = HipBlock(3, degree, n, [1.0 / n[a] for a in range(3)], [0.0] * 3, "left", 0)
+    points = points_of(dim)
+    blk = HipBlock(dim, degree, n, [1.0 / n[a] for a in range(dim)], [0.0] * dim, cell, 0)
     setup_block(blk, n, degree, "source")
-    assert blk.set_injectors(POINTS, series_of(steps), 3).all()
+    assert blk.set_injectors(points, series_of(steps, dim), 3).all()
     blk.step(steps)
     u, s = blk.get_field(_lib.FIELD_U), blk.get_field(_lib.FIELD_S)
     blk.close()
-    owners = np.zeros(len(POINTS), dtype=int)
-    for r in range(world):
-        d = np.load(tmp_path / ("rank%d.npz" % r))
+    owners = np.zeros(len(points), dtype=int)
+    ranks = [np.load(tmp_path / ("rank%d.npz" % r)) for r in range(world)]
+    for r, d in enumerate(ranks):
         assert int(d["steps"]) == steps
         owners += d["owned"]
         assert np.array_equal(d["u"], u[d["cells"]]) and np.array_equal(d["s"], s[d["cells"]]), "rank %d" % r
     assert np.all(owners == 1), owners
+    return ranks
+
+
+def test_injectors_on_a_split_block(gpu, fake, tmp_path):
+    """Two ranks over the transport double, the exchange inside the library, ONE sg_step(n): injectors of velocity and stress
+    in a cell touching the cut, on the cut plane itself (the lower block's) and in the interior.  Every rank's fields equal
+    the single block's bit for bit, and every point has one owner."""
+    _injectors_on_a_split_block(fake, tmp_path, (16, 4, 4), (1, 1, 2), 4, 6)
+
+
+def test_injectors_on_a_split_block_2d(gpu, fake, tmp_path):
+    """The same on triangles: P3 on the mesh (9, 6), two ranks (1, 2) - the 2-D tile family, blocks of four sides.  A stress
+    entry makes comm_step exchange the first stage's input once more before the next step (csrc/comm.cpp: the traces of s1
+    that stage S1 sent are older than the entry); points in a cell touching the cut, on the cut line itself and in the
+    interior.  Bitwise the single block, one owner per point - and the extra exchanges really ran."""
+    steps = 6
+    ranks = _injectors_on_a_split_block(fake, tmp_path, (9, 6), (1, 2), 3, steps, "left")
+    for d in ranks:
+        assert all(str(k).startswith("sg::tile2d_stage<") for k in d["kernels"]), d["kernels"]
+        # the first stage's input at the start of the call, six stage outputs per step, and one more behind each of the
+        # series' steps - 2 stress entries (added at the end of steps 1 .. steps - 2, each followed by another step)
+        assert int(d["exchanges"]) == 1 + 6 * steps + (steps - 2)
+    assert ranks[0]["owned"][:2].all() and ranks[1]["owned"][2:].all()      # the point on the cut line is the lower block's
 
 
 def _free_port():
