@@ -273,7 +273,9 @@ def test_every_kernel_family(gpu, monkeypatch, path, dim, degree, n, L, diagonal
 ])
 def test_stages_utemp_and_s1_read_only_their_operands(gpu, monkeypatch, path, dim, degree, n, L, diagonal):
     """Stage UTEMP writes w = dt u1 + dt^3/24 Minv f(sh1) into UH (include/seigen_hip.h, enum sg_stage) and has no
-    self term: whatever UH held before - here NaN - must not reach the result, in any kernel family."""
+    self term: whatever UH held before - here NaN - must not reach the result, in any kernel family.
+    (tests/test_stage_alone_gpu.py does this for all six stages on every row of the family modules, with a sentinel in
+    every field that is no operand, and compares each stage's output with the oracle.)"""
     from seigen_amd import _lib
     if path:
         monkeypatch.setenv("SEIGEN_HIP_PATH", path)
