@@ -1,5 +1,6 @@
 // fake_hip.cpp - a double of the HIP runtime for the CPU sanitizer build of the library's device-facing host code
-// (api.cpp, stages.cpp, transfer.cpp, comm.cpp and the host halves of kernels*.hip; `make host-runtime-asan`).  It defines
+// (the Makefile's DEV_CPP - api.cpp, stages.cpp, transfer.cpp, comm.cpp, devxfer.cpp, frame.cpp - and the host halves of
+// kernels*.hip; `make host-runtime-asan`).  It defines
 // exactly the entry points those objects leave undefined.  "Device" memory is host heap, so the sanitizers see every copy
 // or fill that overruns a buffer, every use after hipFree and every double free; kernels are never run: a launch is logged
 // with its argument bytes, and every device pointer among them must be null or lie in a live allocation.  README.md says what

@@ -1,5 +1,6 @@
 /* fake_hip.h - the controls of the HIP runtime double (fake_hip.cpp, README.md): fault injection and the live counts as
- * plain C functions, the launch log and the registration table for C++ callers (tools/host_runtime_driver.cpp). */
+ * plain C functions, the launch log and the registration table for C++ callers (tools/host_runtime_common.hpp and the
+ * suites of host_runtime_driver over it). */
 #ifndef SEIGEN_FAKE_HIP_H
 #define SEIGEN_FAKE_HIP_H
 

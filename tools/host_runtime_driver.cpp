@@ -1,7 +1,9 @@
-// host_runtime_driver.cpp - the device-facing host code of libseigen_hip (api.cpp, stages.cpp, transfer.cpp, comm.cpp and the
-// host halves of kernels*.hip) on the CPU, under ASan and UBSan, over the HIP runtime double of tests/fake_hip
-// (`make -C seigen_amd/csrc host-runtime-asan`; tests/test_host_runtime.py).  Nothing runs on a device and no kernel runs at
-// all: the double logs every launch with its argument bytes and audits the device pointers among them.  Per block:
+// host_runtime_driver.cpp - the device-facing host code of libseigen_hip (api.cpp, stages.cpp, transfer.cpp, comm.cpp,
+// devxfer.cpp, frame.cpp and the host halves of kernels*.hip) on the CPU, under ASan and UBSan, over the HIP runtime double of
+// tests/fake_hip (`make -C seigen_amd/csrc host-runtime-asan`; tests/test_host_runtime.py).  Nothing runs on a device and no
+// kernel runs at all: the double logs every launch with its argument bytes and audits the device pointers among them.  One
+// program of three suites over host_runtime_common.hpp: this file's, per block (a) - (d) and once (e), and those of the
+// device transfers (host_runtime_xfer.cpp) and the frames (host_runtime_frame.cpp) on blocks of their own.  Per block:
 //   (a) a whole life of a handle - every setter twice, stepping by graph replay and eagerly, host-driven stages, transfers,
 //       destroy - with the audit and the sanitizers silent and nothing of the runtime left alive;
 //   (b) the launches of that life under graph replay equal to those with SEIGEN_HIP_GRAPH=0, but for the members of kMask;
@@ -9,38 +11,18 @@
 //       the handle as it was, and the next steps launching what a twin launches that never saw the failure;
 //   (d) sizes that cannot be met;
 //   (e) the kernel objects the program registered, printed for the wrapper to compare with the tests' lists.
-// usage: host_runtime_driver [block ...]   (no argument: every block; a name that is no block's, `kernels`: (e) alone)
-#include <functional>
+// usage: host_runtime_driver [block | xfer | frames | kernels | blocks ...]   (no argument: every block and both suites; (e)
+// comes first in every run, and alone with `kernels`; `blocks`: the names of kBlocks, one per line, and nothing else)
 #include <map>
 #include <set>
 #include <sstream>
 
-#include "fake_hip.h"
-#include "handle.hpp"
+#include "host_runtime_common.hpp"
 
 namespace {
 
-int g_errors = 0;
-std::string g_where;
-void error(const std::string& what) {
-  g_errors += 1;
-  std::printf("ERROR [%s] %s\n", g_where.c_str(), what.c_str());
-  std::fflush(stdout);
-}
-#define REQUIRE(cond, msg)              \
-  do {                                  \
-    if (!(cond)) error(std::string(msg) + "  (" #cond ")"); \
-  } while (0)
-
 // ---- the blocks: the smallest of each kernel family -----------------------------------------------------------------
 
-struct BlockDef {
-  const char* name;
-  const char* path;   // SEIGEN_HIP_PATH, or null
-  int dim, degree, n[3], diagonal, dtype, nbr_mask;
-  bool own_stream;    // false: a stream of the caller's (sg_config::stream)
-  Family family;
-};
 const BlockDef kBlocks[] = {
     {"mfma-P4-f64", nullptr, 3, 4, {3, 2, 2}, 0, 0, 0, true, Family::Mfma},
     {"mfma-P2-f32", nullptr, 3, 2, {17, 1, 2}, 0, 1, 0, true, Family::Mfma},
@@ -61,93 +43,6 @@ std::vector<double> rnds(size_t n, double scale = 1.0) {
   std::vector<double> v(n);
   for (double& x : v) x = scale * rnd();
   return v;
-}
-
-// a handle with everything the script hands it
-struct Ctx {
-  const BlockDef* b = nullptr;
-  sg_handle* h = nullptr;
-  hipStream_t user_stream = nullptr;
-  std::vector<void*> halo;       // the caller's device buffers: ghosts and send buffers
-  sg_info_t info = {};
-  int dim = 0, nd = 0;
-  int64_t ncells = 0;
-};
-
-sg_config config_of(const BlockDef& b, hipStream_t stream) {
-  sg_config c;
-  std::memset(&c, 0, sizeof(c));
-  c.dim = b.dim;
-  c.degree = b.degree;
-  for (int a = 0; a < 3; ++a) {
-    c.n[a] = b.n[a];
-    c.h[a] = 0.5;
-  }
-  c.diagonal = b.diagonal;
-  c.nbr_mask = b.nbr_mask;
-  c.dtype = b.dtype;
-  c.stream = (void*)stream;
-  return c;
-}
-
-void* dev_alloc(Ctx& c, size_t nbytes) {
-  void* p = nullptr;
-  if (hipMalloc(&p, nbytes) != hipSuccess) return nullptr;
-  std::memset(p, 0, nbytes);
-  c.halo.push_back(p);
-  return p;
-}
-
-// sg_create (rc returned)
-int create_block(const BlockDef& b, Ctx& c) {
-  c.b = &b;
-  if (b.path) setenv("SEIGEN_HIP_PATH", b.path, 1);
-  else unsetenv("SEIGEN_HIP_PATH");
-  if (!b.own_stream && !c.user_stream && hipStreamCreateWithPriority(&c.user_stream, hipStreamNonBlocking, 0) != hipSuccess) return SG_ERR_DEVICE;
-  const sg_config cfg = config_of(b, c.user_stream);
-  const int rc = sg_create(&cfg, &c.h);
-  if (rc != SG_OK) return rc;
-  sg_get_info(c.h, &c.info);
-  c.dim = c.info.dim;
-  c.nd = c.info.nd;
-  c.ncells = c.info.ncells;
-  return SG_OK;
-}
-// ... then the caller's halo buffers on the sides with a neighbour
-int open_block(const BlockDef& b, Ctx& c) {
-  if (int rc = create_block(b, c)) return rc;
-  for (int side = 0; side < 2 * b.dim; ++side)
-    if ((b.nbr_mask >> side) & 1)
-      for (int f = 0; f < 4; ++f) {
-        size_t nb = 0;
-        sg_halo_bytes(c.h, f, side, &nb);
-        if (sg_halo_attach(c.h, f, side, dev_alloc(c, nb)) != SG_OK) return SG_ERR_ARG;
-      }
-  return SG_OK;
-}
-
-// sg_destroy; last = false: another handle of the driver's is still alive, the counts are checked when that one goes
-void close_block(Ctx& c, bool last = true) {
-  if (c.h) sg_destroy(c.h);
-  c.h = nullptr;
-  for (void* p : c.halo) (void)hipFree(p);
-  c.halo.clear();
-  if (!last) {
-    if (c.user_stream) (void)hipStreamDestroy(c.user_stream);
-    c.user_stream = nullptr;
-    return;
-  }
-  fakehip_counts n;
-  fakehip_get_counts(&n);
-  // a stream handed in through sg_config::stream stays the caller's: alive after sg_destroy, destroyed here
-  REQUIRE(n.streams == (c.user_stream ? 1 : 0), "streams left after sg_destroy: " + std::to_string(n.streams));
-  if (c.user_stream) (void)hipStreamDestroy(c.user_stream);
-  c.user_stream = nullptr;
-  REQUIRE(n.allocs == 0 && n.bytes == 0, "device allocations left after sg_destroy: " + std::to_string(n.allocs));
-  REQUIRE(n.events == 0, "events left after sg_destroy: " + std::to_string(n.events));
-  REQUIRE(n.graphs == 0 && n.execs == 0, "graphs left after sg_destroy");
-  REQUIRE(n.pinned == 0, "pinned buffers left after sg_destroy");
-  REQUIRE(n.capturing == 0, "a stream left capturing");
 }
 
 // ---- what the script hands the setters (v = 0, 1: two sets of values) -----------------------------------------------
@@ -251,7 +146,6 @@ int inject_once(Ctx& c, bool symmetric) {
   const std::vector<double> p = points(c), amp = injector_amps(c, 1, symmetric);
   return sg_inject(c.h, 3, p.data(), 3, amp.data());
 }
-size_t field_doubles(const Ctx& c, int f) { return (size_t)c.ncells * c.nd * (field_is_stress(f) ? c.dim * c.dim : c.dim); }
 
 // n LF4 steps: sg_step, or - a block with neighbours and no communicator - the host's own FIRST / SECOND launches with the
 // packs between them and sg_end_step
@@ -388,11 +282,6 @@ void compare_logs(const std::vector<std::string>& a, const std::vector<std::stri
     }
 }
 
-void no_violations(const char* when) {
-  if (fakehip_violations() > 0) error(std::string("the runtime double objected ") + when + ": " + fakehip_violation(0));
-  fakehip_clear_violations();
-}
-
 // the audit's one extent: a field buffer holds the layout's field_alloc words of the block's type
 void check_field_extents(Ctx& c) {
   for (int f = 0; f < 4; ++f) {
@@ -439,7 +328,7 @@ std::vector<std::string> life(const BlockDef& b, bool graphs) {
   check_field_extents(c);
   auto ok = [&](int rc, const std::string& what) {
     if (rc != SG_OK) error(what + " returned " + std::to_string(rc) + ": " + sg_last_error(c.h));
-    no_violations(what.c_str());
+    no_violations(what);
   };
   ok(configure(c, 0), "the setters");
   ok(configure(twin, 0), "the twin's setters");
@@ -486,7 +375,7 @@ std::vector<std::string> life(const BlockDef& b, bool graphs) {
   ok(sg_reset_correlation(c.h, 1), "sg_reset_correlation, release");
   // transfers, whole and by range
   for (int f = 0; f < 4; ++f) {
-    const size_t len = field_doubles(c, f), per = len / (size_t)c.ncells;
+    const size_t len = c.words(f), per = len / (size_t)c.ncells;
     std::vector<double> host = field_is_stress(f) ? tensors(c, len / (c.dim * c.dim), true) : rnds(len);
     ok(sg_set_field(c.h, f, host.data(), len * sizeof(double)), "sg_set_field");
     ok(sg_get_field(c.h, f, host.data(), len * sizeof(double)), "sg_get_field");
@@ -494,7 +383,7 @@ std::vector<std::string> life(const BlockDef& b, bool graphs) {
     ok(sg_set_field_range(c.h, f, c0, nc, host.data(), (size_t)nc * per * sizeof(double)), "sg_set_field_range");
     ok(sg_get_field_range(c.h, f, c0, nc, host.data(), (size_t)nc * per * sizeof(double)), "sg_get_field_range");
   }
-  std::vector<double> spec(field_doubles(c, SG_FIELD_S));
+  std::vector<double> spec(c.words(SG_FIELD_S));
   ok(sg_get_spectrum(c.h, 1, 1, 1, spec.data(), spec.size() * sizeof(double)), "sg_get_spectrum");
   std::vector<double> rec((size_t)kRecCap * 3 * (c.dim + c.dim * c.dim)), mon((size_t)kMonCap * 5);
   int64_t ns = 0;
@@ -580,15 +469,6 @@ Observed observe(Ctx& c) {
   if (sg_get_monitor(c.h, mon.data(), mon.size() * sizeof(double), &o.monitor) != SG_OK) o.monitor = -2;
   return o;
 }
-bool same_counts(const fakehip_counts& a, const fakehip_counts& b) {
-  return a.allocs == b.allocs && a.bytes == b.bytes && a.streams == b.streams && a.events == b.events && a.graphs == b.graphs &&
-         a.execs == b.execs && a.pinned == b.pinned && a.capturing == b.capturing;
-}
-std::string show(const fakehip_counts& n) {
-  return std::to_string(n.allocs) + " allocations, " + std::to_string(n.bytes) + " bytes, " + std::to_string(n.streams) + " streams, " +
-         std::to_string(n.events) + " events, " + std::to_string(n.graphs) + "+" + std::to_string(n.execs) + " graphs, " +
-         std::to_string(n.pinned) + " pinned, " + std::to_string(n.capturing) + " capturing";
-}
 
 // The places where the library deliberately tolerates a failure of the runtime: the call returns SG_OK.  Told apart by the
 // entry point that returned the injected failure and by whether a stream was capturing then.
@@ -659,25 +539,25 @@ std::vector<Call> calls() {
   add("sg_reset_correlation", BASE_STEPPED, [](Ctx& c, Ctx&) { return sg_reset_correlation(c.h, 0); });
   v.back().prepare = [](Ctx& c, Ctx&) { return sg_correlate(c.h, c.h, nullptr); };   // (an accumulator to zero)
   add("sg_set_field", BASE_STEPPED, [](Ctx& c, Ctx&) {
-    const std::vector<double> host = tensors(c, field_doubles(c, SG_FIELD_S) / (c.dim * c.dim), true);
+    const std::vector<double> host = tensors(c, c.words(SG_FIELD_S) / (c.dim * c.dim), true);
     return sg_set_field(c.h, SG_FIELD_S, host.data(), host.size() * sizeof(double));
   });
   add("sg_get_field", BASE_STEPPED, [](Ctx& c, Ctx&) {
-    std::vector<double> host(field_doubles(c, SG_FIELD_U));
+    std::vector<double> host(c.words(SG_FIELD_U));
     return sg_get_field(c.h, SG_FIELD_U, host.data(), host.size() * sizeof(double));
   });
   add("sg_set_field_range", BASE_STEPPED, [](Ctx& c, Ctx&) {
-    const size_t per = field_doubles(c, SG_FIELD_U) / (size_t)c.ncells;
+    const size_t per = c.words(SG_FIELD_U) / (size_t)c.ncells;
     const std::vector<double> host = rnds(per * 2);
     return sg_set_field_range(c.h, SG_FIELD_U, 1, 2, host.data(), host.size() * sizeof(double));
   });
   add("sg_get_field_range", BASE_STEPPED, [](Ctx& c, Ctx&) {
-    const size_t per = field_doubles(c, SG_FIELD_S) / (size_t)c.ncells;
+    const size_t per = c.words(SG_FIELD_S) / (size_t)c.ncells;
     std::vector<double> host(per * 2);
     return sg_get_field_range(c.h, SG_FIELD_S, 1, 2, host.data(), host.size() * sizeof(double));
   });
   add("sg_get_spectrum", BASE_STEPPED, [](Ctx& c, Ctx&) {
-    std::vector<double> host(field_doubles(c, SG_FIELD_S));
+    std::vector<double> host(c.words(SG_FIELD_S));
     return sg_get_spectrum(c.h, 1, 1, 0, host.data(), host.size() * sizeof(double));
   });
   add("sg_halo_attach + sg_halo_pack_sides", BASE_STEPPED, [](Ctx& c, Ctx&) {
@@ -835,7 +715,7 @@ void sweep_block(const BlockDef& b) {
             g_where = std::string(b.name) + " " + call.name + " kind " + std::to_string(kind);
           }
         }
-        no_violations(("in or after the failed call, " + who).c_str());
+        no_violations("in or after the failed call, " + who);
         if (call.twin) close_block(t, false);
         close_block(c);   // destroyable, nothing left
         no_violations("in sg_destroy after a failed call");
@@ -877,7 +757,12 @@ void impossible_sizes(const BlockDef& b) {
 }  // namespace
 
 int main(int argc, char** argv) {
-  std::vector<std::string> only(argv + 1, argv + argc);
+  const std::vector<std::string> only(argv + 1, argv + argc);
+  const auto asked = [&](const char* what) { return only.empty() || std::find(only.begin(), only.end(), what) != only.end(); };
+  if (!only.empty() && asked("blocks")) {
+    for (const BlockDef& b : kBlocks) std::printf("%s\n", b.name);
+    return 0;
+  }
   // (e) every kernel object the program holds, as registered
   const std::vector<std::string> kernels = fakehip_kernels();
   for (const std::string& k : kernels) std::printf("kernel: %s\n", k.c_str());
@@ -887,7 +772,7 @@ int main(int argc, char** argv) {
     error("no kernel registered itself");
   }
   for (const BlockDef& b : kBlocks) {
-    if (!only.empty() && std::find(only.begin(), only.end(), b.name) == only.end()) continue;
+    if (!asked(b.name)) continue;
     const long injected = g_failures_injected;
     g_where = std::string(b.name) + " life, graph replay";
     const std::vector<std::string> replay = life(b, true);
@@ -902,6 +787,8 @@ int main(int argc, char** argv) {
                 replay.size(), g_failures_injected - injected, g_tolerated);
     std::fflush(stdout);
   }
+  if (asked("xfer")) run_suite("xfer", xfer_block);
+  if (asked("frames")) run_suite("frames", frame_block);
   if (g_errors) {
     std::printf("host_runtime_driver: %d errors\n", g_errors);
     return 1;
