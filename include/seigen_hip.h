@@ -118,12 +118,12 @@ typedef struct sg_config {
                         Calls that return with the launches only QUEUED, ordered on the stream against whatever the
                         caller puts there before and after, and never waiting on the host: sg_run_stage, sg_end_step,
                         sg_halo_pack, sg_halo_pack_sides, sg_apply_F, sg_apply_G, sg_correlate, sg_reset_correlation
-                        (release = 0), sg_get_field_dev, sg_get_spectrum_dev and sg_set_field_dev (but for a stress
+                        (release = 0), sg_get_field_dev, sg_get_spectrum_dev, sg_get_peaks_dev and sg_set_field_dev (but for a stress
                         handed to a block in symmetric storage).  Calls that make the host wait for the stream:
                         sg_create (the whole device), sg_step and the native exchange's stepping (to the end of what
                         they queued), every setter (sg_set_* but sg_set_field_dev, sg_leave_sym), sg_inject, sg_measure,
                         every transfer and read-out through host memory (sg_set_field, sg_get_field, their _range
-                        forms, sg_get_spectrum, sg_get_receivers, sg_get_monitor, sg_get_correlation, sg_get_counters
+                        forms, sg_get_spectrum, sg_get_peaks, sg_get_receivers, sg_get_monitor, sg_get_correlation, sg_get_counters
                         with timing on), sg_set_field_dev of a stress handed to a block in symmetric storage, sg_sync
                         and sg_destroy.  The set-up paths also use the legacy stream (hipMemset, hipMemcpy)
                         after that wait and return when those have completed (a fill is followed by a blocking copy); a
@@ -508,6 +508,47 @@ int sg_correlate_spectra(sg_handle* a, int fa, sg_handle* b, int fb, const doubl
 int sg_spectra_clock(int64_t every, int64_t nsamples, int64_t steps, int64_t more, int64_t out[4]);
 /* the stress lines c = i * dim + j accumulated in full (sym = 0) or symmetric storage, ascending; returns their number */
 int sg_spectra_lines(int dim, int sym, int32_t* lines, int max_lines);
+
+/* ---- peak maps: per node the maximum of |u|^2 and of s:s over the samples of a run and the sample that reached it, on the
+ * device inside the time loop (the peak-ground-velocity, peak-stress and time-of-peak maps of an elastic-wave run) -----------
+ * Armed with `what`, `every` and `nsamples`, the handle takes sample j (0-based) after completed step (j + 1) * every counted
+ * from the arming call - through sg_step (graph replay or eager, with or without a communicator) and through sg_end_step
+ * after host-driven stages alike.  The hook order at the end of a step is receivers, monitor, spectra, peak maps, injectors:
+ * the maps come behind the spectra and BEFORE the injectors, so the sample of step k + 1 never contains injector entry k.
+ * For every node of the block and every selected field - the velocity u = SG_FIELD_U (what bit 0, it lives at t), the stress
+ * s = SG_FIELD_S (bit 1, at t + dt / 2): the receivers' bits -
+ *   every nodal value is converted to double first;
+ *   m starts as x_0 * x_0, then m = m + (x_c * x_c) for c ascending, each product and each sum rounded to double on its own
+ *   (no fma);
+ *   velocity: c = 0 .. dim - 1;  stress in full storage: c = i * dim + j, ascending over all dim^2;  stress in symmetric
+ *   storage: the lines of sg_spectra_lines(dim, 1), ascending, an off-diagonal line entering as 2.0 * (x * x) - the doubling
+ *   is exact - and the i > j lines are not read;
+ *   then  if (m > val) { val = m; idx = j; }  - the comparison is strict, so the earliest sample wins a tie, a NaN never
+ *   enters, and a node that never moved keeps idx = -1.
+ * numpy restates this to the bit.  After nsamples samples nothing is recorded and nothing is refused.
+ * Storage: per selected field val (doubles) and idx (int32) in the field's own device layout with one component, word
+ * (item * nd + a) * gw + lane - double / int32 for FP32 blocks too: 12 bytes per node and selected field.  A word has one
+ * writer and there are no atomics: the bits depend only on the field contents - the same under graph replay and eager
+ * launches, for sg_step(n) and n calls of sg_step(1), for host-driven stages, with timing on or off, and on a split block
+ * (each block keeps its own cells).  When the block leaves symmetric storage mid-run val needs no fix-up: from that step on
+ * the full-storage formula runs.
+ * what: bit 0 velocity (|u|^2), bit 1 stress (s:s) - the receivers' bits; what = 0 disarms and frees.
+ * sample j (0-based) after completed step (j + 1) * every counted from the arming call; after nsamples samples nothing
+ * is recorded and nothing is refused.  SG_ERR_ARG: what outside 0..3, every < 1, nsamples < 1 or > 2^31 - 1.
+ * SG_ERR_NOMEM: all buffers are allocated or none.  Arming again zeroes the maps (val = 0.0, idx = -1) and restarts the
+ * count.  A failed call leaves the maps armed before it, their values and the count intact.  The host waits for the handle's
+ * stream, as in every setter. */
+int sg_set_peaks(sg_handle* h, int what, int64_t every, int64_t nsamples);
+/* field 0: velocity, 1: stress -> value[ncells][nd] (the maxima of the SQUARES) and sample[ncells][nd] (-1: never above 0),
+ * cells in the order of sg_get_field, the cubes of the layout's padding dropped; either pointer may be NULL; nvalues must be
+ * ncells * nd, else SG_ERR_ARG.  SG_ERR_STATE: nothing armed or the field not selected.  The host waits for the handle's
+ * stream. */
+int sg_get_peaks(sg_handle* h, int field, double* value, int32_t* sample, size_t nvalues);
+/* the same into the caller's device buffers on the handle's stream, queued only; dtype of the values as in sg_get_field_dev
+ * (0: double, 1: float, rounded once); the samples are int32 */
+int sg_get_peaks_dev(sg_handle* h, int field, void* dev_value, int dtype, int32_t* dev_sample, size_t nvalues);
+/* samples taken so far (0 when nothing is armed) */
+int sg_peaks_samples(sg_handle* h, int64_t* taken);
 
 /* un-fused operators for stage-level parity tests:
  *   out = Minv f(w; s_in, u_abs)   (elastic.py:204-209 + :358-367)

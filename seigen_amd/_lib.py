@@ -98,6 +98,10 @@ SYMBOLS = {
     "sg_correlate_spectra": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, _P]),
     "sg_spectra_clock": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, _P]),
     "sg_spectra_lines": (C.c_int, [C.c_int, C.c_int, _P, C.c_int]),
+    "sg_set_peaks": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64]),
+    "sg_get_peaks": (C.c_int, [_P, C.c_int, _P, _P, C.c_size_t]),
+    "sg_get_peaks_dev": (C.c_int, [_P, C.c_int, _P, C.c_int, _P, C.c_size_t]),
+    "sg_peaks_samples": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "sg_locate_points": (C.c_int, [C.POINTER(SgConfig), C.c_int64, _P, _P, _P]),
     "sg_apply_F": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),
     "sg_apply_G": (C.c_int, [_P, C.c_int, C.c_int, C.c_int]),

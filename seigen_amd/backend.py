@@ -560,6 +560,42 @@ class HipBlock(object):
         check(self.lib.sg_correlate_spectra(self.h, int(f), other.h, int(f if f_other is None else f_other),
                                             None if w is None else w.ctypes.data, zz.ctypes.data), self.h)
 
+    # ---- peak maps (sg_set_peaks / sg_get_peaks / sg_get_peaks_dev / sg_peaks_samples) -----------------------
+    def set_peaks(self, what, every=1, nsamples=1):
+        """Arm the peak maps: bit 0 of `what` the velocity (|u|^2), bit 1 the stress (s:s).  Sample j is taken after step
+        (j + 1) * every counted from this call, behind the spectra and before the injectors; every node keeps the largest
+        squared magnitude and the sample that reached it, `nsamples` samples long.  what = 0: disarm and free."""
+        check(self.lib.sg_set_peaks(self.h, int(what), int(every), int(nsamples)), self.h)
+
+    def get_peaks(self, field):
+        """(value, sample) of the velocity (field 0 / FIELD_U) or the stress (1 / FIELD_S): value[ncells, nd] the maxima of the
+        SQUARES (float64), sample[ncells, nd] the 0-based sample that reached them (int32; -1: never above zero)."""
+        k = {0: 0, 1: 1, _lib.FIELD_S: 1}[int(field)]
+        value = np.empty((self.ncells, self.nd))
+        sample = np.empty((self.ncells, self.nd), dtype=np.int32)
+        check(self.lib.sg_get_peaks(self.h, k, value.ctypes.data, sample.ctypes.data, value.size), self.h)
+        return value, sample
+
+    def get_peaks_dev(self, field, dtype=None):
+        """get_peaks as torch tensors on the block's device (value float64 or float32, sample int32), moved on the device:
+        queued on the block's stream between torch's current stream before and after, as get_field_dev."""
+        import torch
+        k = {0: 0, 1: 1, _lib.FIELD_S: 1}[int(field)]
+        shape = (self.ncells, self.nd)
+        value = torch.empty(shape, dtype=dtype or torch.float64, device=self._torch_device())
+        sample = torch.empty(shape, dtype=torch.int32, device=self._torch_device())
+        code = self._dev_tensor(value, shape, "get_peaks_dev")
+        self._on_stream(value, lambda: check(self.lib.sg_get_peaks_dev(self.h, k, C.c_void_p(value.data_ptr()), code,
+                                                                       C.c_void_p(sample.data_ptr()), value.numel()), self.h))
+        sample.record_stream(torch.cuda.current_stream(self._device))
+        return value, sample
+
+    def peaks_samples(self):
+        """Samples taken since the arming call (0: nothing armed)."""
+        n = C.c_int64()
+        check(self.lib.sg_peaks_samples(self.h, C.byref(n)), self.h)
+        return int(n.value)
+
     def apply_F(self, s_in, u_abs, u_out):
         check(self.lib.sg_apply_F(self.h, s_in, u_abs, u_out), self.h)
 

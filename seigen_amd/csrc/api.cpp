@@ -304,22 +304,6 @@ static int init_launch(sg_handle* h) {
   return SG_OK;
 }
 
-// The tail of every setter of an end-of-step hook (handle.hpp StepSeries), once nothing of its own can fail any more: armed
-// tables get their device-side step counter, a zero; the host waits for whatever still reads the old tables; a table that is
-// not symmetric makes the block leave symmetric storage - the last step that can fail, and it fails before the mode changes;
-// the new ones move into the handle; the captured graphs are out of date.
-template <typename Tables>
-static int arm_hook(sg_handle* h, Tables& slot, Tables& fresh, bool armed, bool leave_sym = false) {
-  const int64_t zero = 0;
-  if (armed) HIPCHECK(h, fresh.ctr.upload(&zero, 1));
-  HIPCHECK(h, sync_all(h));
-  if (leave_sym)
-    if (int rc = leave_sym_mode(h)) return rc;
-  slot = std::move(fresh);
-  h->epoch += 1;
-  return SG_OK;
-}
-
 extern "C" {
 
 const char* sg_last_error(const sg_handle* h) { return h ? h->err.c_str() : g_create_err.c_str(); }

@@ -3,6 +3,7 @@
 //   transfer.cpp host <-> device field transfers (layout conversion, pinned pipeline)
 //   devxfer.cpp  device <-> device field and spectrum transfers into the caller's buffers, queued on the stream
 //   frame.cpp    a field rastered on a cube-aligned pixel lattice into the caller's device buffer, queued on the stream
+//   peak.cpp     the peak maps: arming, the end-of-step launches, the read-outs through the host and on the stream
 //   stages.cpp   regions, stage launches, the LF4 step, graphs, halo packs, timing
 // and, without a device or a HIP header (the CPU sanitizer build, `make host-asan`):
 //   hostapi.cpp (hostlogic.hpp)  family choice, field layout, stage table, region boxes / items, point location, receiver and injector plans;
@@ -106,10 +107,10 @@ struct SourceTables {
   DevBuf<int32_t> slot, idx;
 };
 
-// What each of the four end-of-step hooks - receivers, monitor, spectra, injectors (stages.cpp hooks) - keeps besides its
+// What each of the five end-of-step hooks - receivers, monitor, spectra, peak maps, injectors (stages.cpp hooks) - keeps besides its
 // tables.  ctr serves graph replay: it is the step index of the hook's launches in a capture - they read it (the kernels'
 // Args::ctr), a one-thread launch bumps it behind them, and sg_step sets it to clock.steps before it replays: the role of
-// sg_handle::src_ctr_d for the source.  A setter puts a zero there when it arms (api.cpp arm_hook).
+// sg_handle::src_ctr_d for the source.  A setter puts a zero there when it arms (arm_hook below).
 struct StepSeries {
   StepClock clock;            // every, count, steps completed since arming (hostlogic.hpp)
   DevBuf<int64_t> ctr;
@@ -152,6 +153,18 @@ struct SpectraTables : StepSeries {   // clock.count: nsamples
   DevBuf<double> w[2];        // [nsamples][nfreq][2] of the velocity / of the stress
   DevBuf<double> acc[2];      // [nfreq][2][field_alloc] of the velocity / of the stress
   bool has(int k) const { return nfreq > 0 && (what & (1 << k)) != 0; }   // k = 0: velocity, 1: stress
+};
+
+// The peak maps of sg_set_peaks (kernels_peak.hip), on the device: per selected field the running maximum of the squared
+// magnitude and the sample that reached it, in the field's own layout with one component (12 bytes per node and field)
+struct PeakTables : StepSeries {      // clock.count: nsamples
+  int what = 0;               // bit 0: velocity, bit 1: stress (0: none armed)
+  DevBuf<double> val[2];      // [field_alloc / ncomp] of the velocity / of the stress
+  DevBuf<int32_t> idx[2];     // ... the 0-based sample of the maximum, -1: never above zero
+  // the hook's launches (peak.cpp queue_peaks), set by the arming call: stages.cpp reaches the feature through the armed
+  // tables alone, so a program that never arms the maps links without peak.cpp and kernels_peak.hip
+  int (*queue)(sg_handle* h, hipStream_t stream, const int64_t* ctr, int64_t step) = nullptr;
+  bool has(int k) const { return (what & (1 << k)) != 0; }   // k = 0: velocity, 1: stress
 };
 
 // The monitor of sg_set_monitor and the scratch of sg_measure (kernels_measure.hip), on the device
@@ -294,6 +307,7 @@ struct sg_handle {
   MeasureScratch msr;
   InjectTables inj;
   SpectraTables spc;
+  PeakTables pk;
   FrameTables frm;
   // whose launches the captured graphs contain: bit 0 the source's, bit 1 + k those of end-of-step hook k (stages.cpp hooks)
   uint32_t in_graphs = 0;
@@ -381,6 +395,22 @@ inline hipError_t sync_all(sg_handle* h) {
 // transfer.cpp: make the (i > j) lines of both stress buffers valid again and continue with the full-tensor kernels
 int leave_sym_mode(sg_handle* h);
 int queue_sym_mirrors(sg_handle* h);   // ... its launches alone: sg_inject changes the mode behind its own launch
+
+// The tail of every setter of an end-of-step hook (StepSeries), once nothing of its own can fail any more: armed tables get
+// their device-side step counter, a zero; the host waits for whatever still reads the old tables; a table that is not
+// symmetric makes the block leave symmetric storage - the last step that can fail, and it fails before the mode changes;
+// the new ones move into the handle; the captured graphs are out of date.
+template <typename Tables>
+int arm_hook(sg_handle* h, Tables& slot, Tables& fresh, bool armed, bool leave_sym = false) {
+  const int64_t zero = 0;
+  if (armed) HIPCHECK(h, fresh.ctr.upload(&zero, 1));
+  HIPCHECK(h, sync_all(h));
+  if (leave_sym)
+    if (int rc = leave_sym_mode(h)) return rc;
+  slot = std::move(fresh);
+  h->epoch += 1;
+  return SG_OK;
+}
 
 // hostlogic.hpp: the layout of the block's fields
 inline Layout layout(const sg_handle* h) { return Layout{h->md.gw, h->ncls, h->re.nd}; }

@@ -173,10 +173,10 @@ inline SourceSlice source_slice(const SourceFacts& s, int64_t step, bool capture
 
 // The clock of everything that runs at the end of a step (stages.cpp hooks): sample j (0-based) belongs to step (j + 1) * every
 // counted from the arming call, and there are `count` of them - the capacity of the receivers' and the monitor's trace, the
-// spectra's nsamples, the injectors' nsteps (every = 1: entry k is added at the end of step k + 1).  What happens when the
-// series is full is the hook's business, not the clock's: the receivers and the monitor refuse the step (fits, no_room_at;
-// their count of samples is the uncapped one, which the refusals keep within count), the spectra and the injectors run out
-// silently (due_at, active; their count of samples is the capped one).
+// spectra's and the peak maps' nsamples, the injectors' nsteps (every = 1: entry k is added at the end of step k + 1).  What
+// happens when the series is full is the hook's business, not the clock's: the receivers and the monitor refuse the step (fits,
+// no_room_at; their count of samples is the uncapped one, which the refusals keep within count), the spectra, the peak maps and
+// the injectors run out silently (due_at, active; their count of samples is the capped one).
 struct StepClock {
   int64_t every = 1, count = 0;
   int64_t steps = 0;   // completed since arming

@@ -426,6 +426,19 @@ struct Args {
 }  // namespace spectra
 int launch_spectra(const void* field, const spectra::Args& a, int f32, int grid, void* stream);
 
+// Peak maps (kernels_peak.hip; seigen_hip.h sg_set_peaks): at the end of step s (counted from the arming call; s from
+// *ctr + 1 under graph replay) with s % every == 0 and j = s / every - 1 < nsamples, every node word w = (item * nd + a) * gw +
+// lane of the n forms m = sum_c x_c x_c over the lines ((item * nd + a) * ncomp + c) * gw + lane of `field` in double, each
+// product and sum rounded on its own - in symmetric storage (sym, ncomp = dim^2) the i <= j lines, an off-diagonal one as
+// 2 (x x) - and if (m > val[w]) { val[w] = m; idx[w] = j; }.  One flat pass over the node words, of at most `grid` blocks.
+// The kernels take pointers and built-in scalars only.
+int launch_peak_update(const void* field, double* val, int32_t* idx, const int64_t* ctr, int64_t step, int64_t every, int64_t nsamples,
+                       int64_t n, int gw, int ncomp, int dim, int sym, int f32, int grid, void* stream);
+// val / idx in that layout -> out_val (float where c32) / out_idx [cell][node], cell = cube * ncls + cls, the cubes of the
+// layout's padding (cube >= ncube) dropped; either output may be null
+int launch_peak_gather(const double* val, const int32_t* idx, void* out_val, int c32, int32_t* out_idx, int64_t n, int gw, int nd, int ncls,
+                       int64_t ncube, int grid, void* stream);
+
 // Device transfers (kernels_xfer.hip; seigen_hip.h sg_get_field_dev / sg_set_field_dev / sg_get_spectrum_dev): `ncells` cells
 // from `cell0` between a buffer in the layout of the fields (`field`: float where f32) and the caller's device buffer
 // [cell][node][comp] (`buf`: float where c32), by the plan of hostlogic.hpp xfer_plan (item0, units, slices, rows_per_slice,

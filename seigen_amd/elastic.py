@@ -193,6 +193,8 @@ class ElasticLF4(object):
             self._monitor_times = []
             self._spectra = None            # (freqs, every, nsamples, what, window) of set_spectra
             self._spectra_freqs = None      # the frequencies armed by the last run
+            self._peaks = None              # (what, every, nsamples) of set_peaks
+            self._peaks_armed = None        # (what, every) armed by the last run
             self._frames = None             # (function, m, slice, every, dtype) of set_frames
             self._frame_stack = None        # the frames of the last run
             self._injected = []             # what inject / set_injectors have added, for rewind (see _position)
@@ -756,6 +758,65 @@ class ElasticLF4(object):
         fo = f if f_other is None else f_other
         self._block.correlate_spectra(other._block, self._spectrum_index(f), other._spectrum_index(fo), weights, z)
 
+    # ---- peak maps: per-node maxima of |u|^2 and s:s inside the time loop (sg_set_peaks) ---------------
+    def set_peaks(self, fields=("velocity",), every=1, nsamples=None):
+        """Keep, over the next runs, per node the largest |u| ("velocity" = VelocityNew at t) and / or the largest
+        sqrt(s:s) ("stress" = StressNew at t + dt/2) and the time it was reached, on the device inside the time loop: sample
+        j after step (j + 1) * every, `nsamples` of them (None: all the run has).  No fields: none.  It works with a source
+        and a sponge, and keeps 12 bytes per node and field."""
+        what = 0
+        for f in fields or ():
+            if f not in ("velocity", "stress"):
+                raise ValueError("peak fields are 'velocity' and 'stress', not %r" % (f,))
+            what |= 1 if f == "velocity" else 2
+        if what == 0:
+            self._peaks = None
+            return
+        if int(every) < 1:
+            raise ValueError("set_peaks needs every >= 1")
+        self._peaks = (what, int(every), None if nsamples is None else int(nsamples))
+
+    def _arm_peaks(self, times):
+        if self._peaks is None:
+            if self._peaks_armed is not None:
+                self._block.set_peaks(0)
+                self._peaks_armed = None
+            return
+        what, every, nsamples = self._peaks
+        n = len(times) // every if nsamples is None else nsamples
+        if n < 1:
+            raise ValueError("set_peaks: the run has no sample step (every = %d, %d steps)" % (every, len(times)))
+        self._block.set_peaks(what, every, n)
+        self._peaks_armed = (what, every)
+
+    def _peak_field(self, field):
+        if field not in ("velocity", "stress"):
+            raise ValueError("peak fields are 'velocity' and 'stress', not %r" % (field,))
+        if self._peaks_armed is None or not self._peaks_armed[0] & (1 if field == "velocity" else 2):
+            raise RuntimeError("no peak map of the %s: call set_peaks before run" % field)
+        return (0 if field == "velocity" else 1), self._peaks_armed[1], (0.0 if field == "velocity" else 0.5 * self.dt)
+
+    def peak_map(self, field):
+        """The peak map of `field` ("velocity" or "stress") as recorded so far, of this rank's block, per node in the order
+        of the Function's data: {"amplitude": the largest |u| or sqrt(s:s), "time": when it was reached - (sample + 1) *
+        every * dt from the start of the run, + dt / 2 for the stress; NaN where the node never moved -, "sample": the
+        0-based sample, -1 there}."""
+        k, every, stagger = self._peak_field(field)
+        value, sample = self._block.get_peaks(k)
+        value, sample = value.ravel(), sample.ravel()
+        time = np.where(sample >= 0, (sample.astype(np.float64) + 1.0) * every * self.dt + stagger, np.nan)
+        return {"amplitude": np.sqrt(value), "time": time, "sample": sample}
+
+    def peak_map_torch(self, field):
+        """`peak_map` as torch tensors on the block's device, moved on the device (no host copy)."""
+        import torch
+        k, every, stagger = self._peak_field(field)
+        value, sample = self._block.get_peaks_dev(k)
+        value, sample = value.reshape(-1), sample.reshape(-1)
+        time = torch.where(sample >= 0, (sample.to(torch.float64) + 1.0) * every * self.dt + stagger,
+                           torch.full_like(value, float("nan")))
+        return {"amplitude": torch.sqrt(value), "time": time, "sample": sample}
+
     # ---- correlation with another solver's fields, cell by cell (sg_correlate) ------------------------
     def correlate(self, other, weights=(1.0, 1.0, 1.0)):
         """Add weights * (uu, ss, tt) of this solver's (u1, s1) against `other`'s - an ElasticLF4 on the same mesh and
@@ -856,6 +917,7 @@ class ElasticLF4(object):
             self._arm_receivers(times)
             self._arm_monitor(times)
             self._arm_spectra(times)
+            self._arm_peaks(times)
             with self.loop_context():
                 if self.output:
                     for t in times:

@@ -200,7 +200,7 @@ const MaskEntry kMask[] = {
     {"void sg::source_kernel<", nullptr, 5, 0, 0, "stages.cpp:251 sn.values + off: the host's slice against slice 0"},
     {"void sg::source_kernel<", nullptr, 7, 0, 0, "stages.cpp:251 sn.at.scale: the host's weight against SrcStep::weights"},
     {"void sg::source_kernel<", nullptr, 8, 0, 0, "stages.cpp:252 sn.stepper: null under eager launches"},
-    // the end-of-step hooks: the step by value against the hook's device counter (stages.cpp:549 hook_step)
+    // the end-of-step hooks: the step by value against the hook's device counter (stages.cpp:550 hook_step)
     {"", "sg::RecvArgs", -1, MEMBER(RecvArgs, ctr), "stages.cpp:418 a.ctr"},
     {"", "sg::RecvArgs", -1, MEMBER(RecvArgs, step), "stages.cpp:419 a.step"},
     {"", "sg::measure::Args", -1, MEMBER(measure::Args, ctr), "stages.cpp:445 a.ctr"},
@@ -210,7 +210,7 @@ const MaskEntry kMask[] = {
     {"", "sg::inject::Args", -1, MEMBER(inject::Args, ctr), "stages.cpp:327 a.ctr"},
     {"", "sg::inject::Args", -1, MEMBER(inject::Args, step), "stages.cpp:328 a.step"},
 };
-// ... and the one-thread launches that set and bump those counters exist under replay only (stages.cpp:550, :608, :674, :678)
+// ... and the one-thread launches that set and bump those counters exist under replay only (stages.cpp:551, :609, :675, :679)
 const char* const kReplayOnlyKernel = "sg::step_counter_kernel(";
 
 bool masked(const FakeHipLaunch& e, size_t byte) {
@@ -480,10 +480,10 @@ struct Tolerated {
 const Tolerated kTolerated[] = {
     {"hipOccupancyMaxActiveBlocksPerMultiprocessor", "stages.cpp:166 tile_resident; kernels_mfma.hip:1477 prepare_sponge_affine_mfma",
      "the resident blocks of a persistent grid fall back to 2 per CU"},
-    {"hipStreamBeginCapture", "stages.cpp:623 capture_steps", "a capture that fails switches graph replay off for the handle (stages.cpp:667): the steps run eagerly"},
-    {"hipStreamEndCapture", "stages.cpp:629 capture_steps", "the same"},
-    {"hipGraphInstantiate", "stages.cpp:631 capture_steps", "the same"},
-    {nullptr, "stages.cpp:627 capture_steps", "the same: a launch that fails inside the capture fails the capture, not the call"},
+    {"hipStreamBeginCapture", "stages.cpp:624 capture_steps", "a capture that fails switches graph replay off for the handle (stages.cpp:668): the steps run eagerly"},
+    {"hipStreamEndCapture", "stages.cpp:630 capture_steps", "the same"},
+    {"hipGraphInstantiate", "stages.cpp:632 capture_steps", "the same"},
+    {nullptr, "stages.cpp:628 capture_steps", "the same: a launch that fails inside the capture fails the capture, not the call"},
 };
 // 0: not tolerated; 1: tolerated; 2: tolerated, and the handle steps eagerly from here on (a failed capture)
 int tolerated(const char* call) {
