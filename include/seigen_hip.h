@@ -118,12 +118,13 @@ typedef struct sg_config {
                         Calls that return with the launches only QUEUED, ordered on the stream against whatever the
                         caller puts there before and after, and never waiting on the host: sg_run_stage, sg_end_step,
                         sg_halo_pack, sg_halo_pack_sides, sg_apply_F, sg_apply_G, sg_correlate, sg_reset_correlation
-                        (release = 0), sg_get_field_dev, sg_get_spectrum_dev, sg_get_peaks_dev and sg_set_field_dev (but for a stress
+                        (release = 0), sg_get_field_dev, sg_get_spectrum_dev, sg_get_peaks_dev, sg_get_frame_dev and sg_get_gradient_dev (their
+                        tables in place) and sg_set_field_dev (but for a stress
                         handed to a block in symmetric storage).  Calls that make the host wait for the stream:
                         sg_create (the whole device), sg_step and the native exchange's stepping (to the end of what
                         they queued), every setter (sg_set_* but sg_set_field_dev, sg_leave_sym), sg_inject, sg_measure,
                         every transfer and read-out through host memory (sg_set_field, sg_get_field, their _range
-                        forms, sg_get_spectrum, sg_get_peaks, sg_get_receivers, sg_get_monitor, sg_get_correlation, sg_get_counters
+                        forms, sg_get_spectrum, sg_get_peaks, sg_get_gradient, sg_get_receivers, sg_get_monitor, sg_get_correlation, sg_get_counters
                         with timing on), sg_set_field_dev of a stress handed to a block in symmetric storage, sg_sync
                         and sg_destroy.  The set-up paths also use the legacy stream (hipMemset, hipMemcpy)
                         after that wait and return when those have completed (a fill is followed by a blocking copy); a
@@ -280,6 +281,45 @@ int sg_frame_plan(const sg_config* cfg, const sg_frame* fr, int64_t out[12]);
 int64_t sg_frame_groups(const sg_config* cfg, const sg_frame* fr, int32_t* groups, int64_t max_groups);
 /* cls[Q], xi[Q][dim] and phi[Q][nd] of the in-cube pixels (device-free; degree <= 8 as sg_locate_points) */
 int sg_frame_weights(const sg_config* cfg, int degree, const sg_frame* fr, int32_t* cls, double* xi, double* phi);
+
+/* ---- gradient: strain rate, divergence and curl of a velocity field at the nodes, on the device -----------------------
+ * The broken (cell-local) gradient of field `field` (SG_FIELD_U or SG_FIELD_UH; a stress field: SG_ERR_ARG): the gradient of
+ * every cell's own polynomial at the cell's nodes, no facet terms - exact for every member of the element's space.  For the
+ * cell of class k, node a, velocity component i:
+ *   t_r[a][i] = sum_b C_r[a][b] * (double)u[b][i]      C_r[a][b] = d(phi_b)/d(xi_r) at the reference point of node a
+ *   G_ij[a]   = sum_r J[k][r][j] * t_r[a][i]           J[k][r][j] = d(xi_r)/d(x_j) (sg_mesh_tables' jinv)
+ * kind 0: the gradient, ncomp = dim^2, component c = i * dim + j holds d(u_i)/d(x_j);
+ * kind 1: the divergence, ncomp = 1;
+ * kind 2: the curl: 3-D ncomp = 3, (G21 - G12, G02 - G20, G10 - G01); 2-D ncomp = 1, G10 - G01; 1-D: SG_ERR_ARG;
+ * kind 3: the symmetric strain rate, ncomp = dim^2, 0.5 * (G_ij + G_ji), the diagonal entries G_ii themselves.
+ * Arithmetic: nodal values are converted to double first; t_r is formed with fma from zero over b ascending - simplices over
+ * the dense row, tensor-product cells over the P + 1 nodes of the line through a along axis r (the 1-D derivative matrix,
+ * what sum factorisation gives); G_ij with fma from zero over r ascending; the combinations of kinds 1 to 3 are single
+ * additions, subtractions and one multiplication by 0.5, each rounded on its own in the order written, the divergence as
+ * (G00 + G11) + G22.  The bits therefore depend on the cell's nodal values, the cell type, the degree, the class and h[]
+ * alone - not on the kernel family, the layout of the fields, the stream, the range or the caller's dtype.
+ * sg_get_gradient_dev writes dev_out[cell][node][ncomp] for `ncells` cells from `cell0` into DEVICE memory of the caller's of
+ * type dtype (0 = double, 1 = float, rounded once); nbytes is exactly its size; cell order, range rule and padding rule are
+ * sg_get_field_dev's, and so are the ordering rules: the launch is only QUEUED on the handle's stream, never waits on the
+ * host, and may be called between graph replays.  It writes no field and changes neither the storage mode nor a counter.
+ * The tables (C_r, J) live on the device with the handle from the first call to sg_destroy: that call builds them first (two
+ * allocations and blocking copies, as a setter does), no later one does.  A call that fails leaves the handle as it was.
+ * SG_ERR_ARG: a null pointer, a field, kind or dtype outside its range, a range or nbytes that sg_get_field_range would
+ * refuse for a field of ncomp components.
+ * sg_get_gradient is the same into HOST memory, doubles: a temporary device buffer, one blocking copy; it waits for the
+ * stream like every host read-out. */
+int sg_get_gradient_dev(sg_handle* h, int field, int kind, int64_t cell0, int64_t ncells, void* dev_out, int dtype, size_t nbytes);
+int sg_get_gradient(sg_handle* h, int field, int kind, int64_t cell0, int64_t ncells, double* host_out, size_t nbytes);
+/* The tables of a block (device-free): C[r][a][b], dim * nd * nd doubles, dense for both cell types - bitwise
+ * sg_tabulate_grad_cell at the nodes' reference points (lattice / degree) - and J[cls][3][3], the block's jinv.  Either may
+ * be NULL; returns the number of doubles of C (NULL, NULL: a size query), or SG_ERR_ARG. */
+int64_t sg_gradient_tables(const sg_config* cfg, double* C, double* J);
+/* The launch plan of one call (device-free), the counterpart of sg_xfer_plan: out = first item, number of items, output nodes
+ * per slice, slices per item, blocks of the grid (at most SG_XFER_GRID_CAP: the grid strides over the (item, slice) units
+ * beyond it), bytes of LDS per block (at most 64 KiB: the item's velocity block and a slice's values as doubles, pitch
+ * gw + 1).  gw = 1: items are cells, a thread per (cell, node), no LDS. */
+int sg_gradient_plan(int gw, int ncls, int nd, int dim, int ncomp, int dev_bytes, int caller_bytes, int64_t cell0, int64_t ncells,
+                     int64_t out[6]);
 
 /* ---- absorption (elastic.py:136-141, :207-208) ------------------------------------ */
 /* sigma_nodes: [cell][nd(sigma_degree)] nodal values of the DG_q sponge field, or NULL to disable. */
@@ -648,6 +688,9 @@ int sg_tabulate(int dim, int degree, int64_t npts, const double* xi, double* phi
  * the element of sg_config::diagonal = 2. */
 int64_t sg_reference_operator_cell(int cell_type, int dim, int degree, int which, int q, double* out, size_t nbytes);
 int sg_tabulate_cell(int cell_type, int dim, int degree, int64_t npts, const double* xi, double* phi);
+/* dphi[p][a][r] = d(phi_a)/d(xi_r) at xi[p][dim] (degree <= 8): the derivative of the interpolant's basis, the tables of
+ * sg_get_gradient_dev - not which = 0 of sg_reference_operator, the weak operator with the derivative on the test function. */
+int sg_tabulate_grad_cell(int cell_type, int dim, int degree, int64_t npts, const double* xi, double* dphi);
 /* Point location (device-free; cfg->device / stream ignored, like sg_block_node_coords): cell[k] = the block-local cell
  * owning pts[k][dim], or -1 (another block's, or outside the mesh); xi[k][dim] its reference coordinates (0 where -1).
  * The rule (seigen_amd/functionspace.py locate, the stand-in for the point location behind vtktools.vtu.ProbeData that

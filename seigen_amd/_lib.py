@@ -74,6 +74,11 @@ SYMBOLS = {
     "sg_frame_plan": (C.c_int, [C.POINTER(SgConfig), C.POINTER(SgFrame), _P]),
     "sg_frame_groups": (C.c_int64, [C.POINTER(SgConfig), C.POINTER(SgFrame), _P, C.c_int64]),
     "sg_frame_weights": (C.c_int, [C.POINTER(SgConfig), C.c_int, C.POINTER(SgFrame), _P, _P, _P]),
+    "sg_get_gradient_dev": (C.c_int, [_P, C.c_int, C.c_int, C.c_int64, C.c_int64, _P, C.c_int, C.c_size_t]),
+    "sg_get_gradient": (C.c_int, [_P, C.c_int, C.c_int, C.c_int64, C.c_int64, _P, C.c_size_t]),
+    "sg_gradient_tables": (C.c_int64, [C.POINTER(SgConfig), _P, _P]),
+    "sg_gradient_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P]),
+    "sg_tabulate_grad_cell": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P]),
     "sg_set_absorption": (C.c_int, [_P, _P, C.c_int]),
     "sg_set_source": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P]),
     "sg_set_source_separable": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P]),

@@ -93,6 +93,40 @@ def frame_weights(cfg, degree, fr, nd):
     return cls, xi, phi
 
 
+GRADIENT_KINDS = {"grad": 0, "div": 1, "curl": 2, "strain": 3}
+
+
+def gradient_kind(kind):
+    """the `kind` of sg_get_gradient_dev from its name or number"""
+    k = GRADIENT_KINDS.get(kind, kind)
+    if k not in (0, 1, 2, 3):
+        raise ValueError("kind: %s or 0 .. 3" % ", ".join(repr(n) for n in GRADIENT_KINDS))
+    return int(k)
+
+
+def gradient_tables(cfg):
+    """(C [dim, nd, nd], J [ncls, 3, 3]) of the block `cfg` (an SgConfig) describes: C[r, a, b] = d(phi_b)/d(xi_r) at node a,
+    J[k, r, j] = d(xi_r)/d(x_j) of class k - the tables of sg_get_gradient_dev (sg_gradient_tables; device-free)"""
+    L = _lib.load()
+    size = L.sg_gradient_tables(C.byref(cfg), None, None)
+    if size < 0:
+        raise _lib.SeigenHipError("sg_gradient_tables refuses the configuration")
+    d = cfg.dim
+    nd = int(round((size // d) ** 0.5))
+    ncls = 1 if cfg.diagonal == 2 else {1: 1, 2: 2, 3: 6}[d]
+    Ct, J = np.zeros((d, nd, nd)), np.zeros((ncls, 3, 3))
+    if L.sg_gradient_tables(C.byref(cfg), Ct.ctypes.data, J.ctypes.data) != size:
+        raise _lib.SeigenHipError("sg_gradient_tables failed")
+    return Ct, J
+
+
+def gradient_plan(gw, ncls, nd, dim, ncomp, dev_bytes=8, caller_bytes=8, cell0=0, ncells=0):
+    """sg_gradient_plan as a dict (device-free)"""
+    out = np.zeros(6, dtype=np.int64)
+    check(_lib.load().sg_gradient_plan(gw, ncls, nd, dim, ncomp, dev_bytes, caller_bytes, cell0, ncells, out.ctypes.data))
+    return dict(zip(("item0", "nitems", "nodes_per_slice", "slices", "grid", "lds_bytes"), (int(x) for x in out)))
+
+
 class HipBlock(object):
     def __init__(self, dim, degree, n, h, origin, diagonal="left", nbr_mask=0, device=0, stream=None, dtype="f64",
                  cube0=None):
@@ -308,6 +342,43 @@ class HipBlock(object):
         code = 1 if out.dtype == torch.float32 else 0
         self._on_stream(out, lambda: check(self.lib.sg_get_frame_dev(self.h, int(field), C.byref(fr), C.c_void_p(out.data_ptr()), code,
                                                                      stride, nbytes), self.h))
+        return out
+
+    # ---- gradient (sg_get_gradient_dev / sg_get_gradient) ------------------------------------------------------
+    def gradient_shape(self, kind, ncells=None):
+        """[ncells, nd] + the value shape of a kind: (dim, dim) of "grad" and "strain", () of "div", (3,) / () of "curl"""
+        k = gradient_kind(kind)
+        d = self.dim
+        if k == 2 and d == 1:
+            raise ValueError("no curl in one dimension")
+        value = {0: (d, d), 1: (), 2: (3,) if d == 3 else (), 3: (d, d)}[k]
+        return (self.ncells if ncells is None else int(ncells), self.nd) + value
+
+    def get_gradient_dev(self, field, kind, out=None, dtype=None, cell0=0, ncells=None):
+        """The broken gradient of a velocity field (FIELD_U, FIELD_UH) at the nodes of cells cell0 .. cell0 + ncells - 1, or
+        its divergence, curl or symmetric part (`kind`: 0 / "grad", 1 / "div", 2 / "curl", 3 / "strain"), as a torch tensor of
+        gradient_shape(kind, ncells) on the block's device, float64 or float32.  Queued like get_field_dev: on the block's
+        stream between torch's current stream before and after, no host wait."""
+        import torch
+        k = gradient_kind(kind)
+        ncells = self.ncells - int(cell0) if ncells is None else int(ncells)
+        shape = self.gradient_shape(k, ncells)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype or torch.float64, device=self._torch_device())
+        elif dtype is not None and out.dtype != dtype:
+            raise ValueError("out is %s, dtype asks for %s" % (out.dtype, dtype))
+        code = self._dev_tensor(out, shape, "get_gradient_dev")
+        nbytes = out.numel() * out.element_size()
+        self._on_stream(out, lambda: check(self.lib.sg_get_gradient_dev(self.h, int(field), k, int(cell0), ncells,
+                                                                        C.c_void_p(out.data_ptr()), code, nbytes), self.h))
+        return out
+
+    def get_gradient(self, field, kind, cell0=0, ncells=None):
+        """get_gradient_dev as a float64 numpy array, through a temporary device buffer and one blocking copy"""
+        k = gradient_kind(kind)
+        ncells = self.ncells - int(cell0) if ncells is None else int(ncells)
+        out = np.empty(self.gradient_shape(k, ncells))
+        check(self.lib.sg_get_gradient(self.h, int(field), k, int(cell0), ncells, out.ctypes.data, out.nbytes), self.h)
         return out
 
     def set_params(self, density, dt, lam, mu):

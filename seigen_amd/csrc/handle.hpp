@@ -3,6 +3,7 @@
 //   transfer.cpp host <-> device field transfers (layout conversion, pinned pipeline)
 //   devxfer.cpp  device <-> device field and spectrum transfers into the caller's buffers, queued on the stream
 //   frame.cpp    a field rastered on a cube-aligned pixel lattice into the caller's device buffer, queued on the stream
+//   grad.cpp     the broken gradient of a velocity field at the nodes into the caller's device buffer, queued on the stream
 //   peak.cpp     the peak maps: arming, the end-of-step launches, the read-outs through the host and on the stream
 //   stages.cpp   regions, stage launches, the LF4 step, graphs, halo packs, timing
 // and, without a device or a HIP header (the CPU sanitizer build, `make host-asan`):
@@ -237,6 +238,14 @@ struct FrameTables {
   DevBuf<int32_t> groups;     // the listed groups of gw cubes (hostlogic.hpp FramePlan)
 };
 
+// The gradient of sg_get_gradient_dev (grad.cpp, kernels_grad.hip): its tables on the device, built by the handle's first call
+struct GradTables {
+  bool ready = false;
+  DevBuf<double> C;           // simplices: [dim][nd][nd] dense; tensor-product cells: the 1-D matrix [n1][n1]
+  DevBuf<double> J;           // [ncls][3][3] = MeshDev::Jinv
+  int n1 = 0;                 // P + 1 on tensor-product cells, else 0 (kernels.hpp GradArgs::n1)
+};
+
 // The four fields of a block.  Whoever writes one asks for it with write(), which counts the write: what remembers a field
 // state (the sponge pre-pass, hostlogic.hpp PrePass) can then tell that the field has moved on - from a stage, a source
 // launch, an upload or the mirror launch alike.  Readers take the const pointer.
@@ -309,6 +318,7 @@ struct sg_handle {
   SpectraTables spc;
   PeakTables pk;
   FrameTables frm;
+  GradTables grd;
   // whose launches the captured graphs contain: bit 0 the source's, bit 1 + k those of end-of-step hook k (stages.cpp hooks)
   uint32_t in_graphs = 0;
   CorrelationTables cor;

@@ -526,6 +526,63 @@ int sg_xfer_plan(int gw, int ncls, int nd, int ncomp, int dev_bytes, int caller_
   return SG_OK;
 }
 
+int sg_gradient_plan(int gw, int ncls, int nd, int dim, int ncomp, int dev_bytes, int caller_bytes, int64_t cell0, int64_t ncells,
+                     int64_t out[6]) {
+  if (!out || (gw != 1 && gw != 16 && gw != 64) || ncls < 1 || nd < 1 || dim < 1 || dim > 3 || ncomp < 1 || ncomp > dim * dim) return SG_ERR_ARG;
+  if (cell0 < 0 || ncells < 0 || (dev_bytes != 4 && dev_bytes != 8) || (caller_bytes != 4 && caller_bytes != 8)) return SG_ERR_ARG;
+  const GradPlan p = grad_plan(gw, ncls, nd, dim, ncomp, cell0, ncells);
+  if (!p.ok) {
+    g_create_err = "sg_gradient_plan: the item's velocity block leaves no room for a node's values in the LDS budget";
+    return SG_ERR_ARG;
+  }
+  out[0] = p.item0;
+  out[1] = p.nitems;
+  out[2] = p.nodes_per_slice;
+  out[3] = p.slices;
+  out[4] = p.grid;
+  out[5] = p.lds_bytes;
+  return SG_OK;
+}
+
+int sg_tabulate_grad_cell(int cell_type, int dim, int degree, int64_t npts, const double* xi, double* dphi) {
+  if (dim < 1 || dim > 3 || degree < 1 || degree > 8 || npts < 0 || !xi || !dphi) return SG_ERR_ARG;
+  if (cell_type != KIND_SIMPLEX && cell_type != KIND_TENSOR) return SG_ERR_ARG;
+  tabulate_grad(dim, degree, (int)npts, xi, dphi, cell_type);
+  return SG_OK;
+}
+
+int64_t sg_gradient_tables(const sg_config* cfg, double* C, double* J) {
+  if (!cfg || cfg->dim < 1 || cfg->dim > 3 || cfg->degree < 1 || cfg->degree > 4) return SG_ERR_ARG;
+  const bool quad = cfg->diagonal == SG_DIAGONAL_QUAD;
+  if (quad && cfg->dim == 1) return SG_ERR_ARG;
+  for (int a = 0; a < cfg->dim; ++a)
+    if (!(cfg->h[a] > 0.0)) return SG_ERR_ARG;
+  try {
+    const RefElem re = make_refelem(cfg->dim, cfg->degree, quad ? KIND_TENSOR : KIND_SIMPLEX);
+    const int64_t size = (int64_t)cfg->dim * re.nd * re.nd;
+    if (C) {
+      const std::vector<double> c = grad_dense_tables(re.kind, cfg->dim, cfg->degree, re.lattice);
+      std::memcpy(C, c.data(), c.size() * sizeof(double));
+    }
+    if (J) {
+      MeshDev md;
+      std::memset(&md, 0, sizeof(md));
+      md.nd = re.nd;
+      md.nf = re.nf;
+      double hh[3] = {1, 1, 1};
+      for (int a = 0; a < cfg->dim; ++a) hh[a] = cfg->h[a];
+      build_mesh_tables(cfg->dim, cfg->degree, cfg->diagonal, hh, re.fnode.data(), re.lattice.data(), md);
+      for (int c = 0; c < md.ncls; ++c)
+        for (int r = 0; r < 3; ++r)
+          for (int j = 0; j < 3; ++j) J[((size_t)c * 3 + r) * 3 + j] = md.Jinv[c][r][j];
+    }
+    return size;
+  } catch (const std::exception& e) {
+    g_create_err = e.what();
+    return SG_ERR_ARG;
+  }
+}
+
 int sg_spectra_lines(int dim, int sym, int32_t* lines, int max_lines) {
   if (dim < 1 || dim > 3 || !lines) return SG_ERR_ARG;
   const std::vector<int32_t> r = spectra_lines(dim, sym != 0);

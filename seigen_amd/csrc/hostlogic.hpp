@@ -429,6 +429,75 @@ inline XferPlan xfer_plan(int gw, int ncls, int nd, int ncomp, int dev_bytes, in
   return p;
 }
 
+// The gradient (seigen_hip.h sg_get_gradient_dev; grad.cpp, kernels_grad.hip): the broken gradient of a velocity field at the
+// nodes.  Components of a kind (0 gradient, 1 divergence, 2 curl, 3 symmetric strain rate), 0: the kind does not exist there.
+inline int grad_ncomp(int dim, int kind) {
+  if (dim < 1 || dim > 3) return 0;
+  if (kind == 0 || kind == 3) return dim * dim;
+  if (kind == 1) return 1;
+  if (kind == 2) return dim == 3 ? 3 : (dim == 2 ? 1 : 0);
+  return 0;
+}
+// C[r][a][b] = d(phi_b)/d(xi_r) at the reference point of node a, dense for both cell kinds: refelem.hpp tabulate_grad at the
+// lattice points a / P.  On a tensor-product cell the entries of the line through a along axis r are the 1-D derivative
+// matrix C1[a_r][b_r] (the other 1-D factors are 1 at their own node), which is rows 0 .. P of C[0]: C1[al][be] = C[0][al][be].
+inline std::vector<double> grad_dense_tables(int kind, int dim, int P, const std::vector<int>& lattice) {
+  const int nd = (int)lattice.size() / dim;
+  std::vector<double> xi((size_t)nd * dim), dphi((size_t)nd * nd * dim), C((size_t)dim * nd * nd);
+  for (size_t k = 0; k < xi.size(); ++k) xi[k] = (double)lattice[k] / (double)P;
+  sg::tabulate_grad(dim, P, nd, xi.data(), dphi.data(), kind);
+  for (int r = 0; r < dim; ++r)
+    for (int a = 0; a < nd; ++a)
+      for (int b = 0; b < nd; ++b) C[((size_t)r * nd + a) * nd + b] = dphi[((size_t)a * nd + b) * dim + r];
+  return C;
+}
+// The launch plan of one call, for the launch wrapper (grad.cpp) and sg_gradient_plan alike.  The items and the lanes that
+// move nothing are those of xfer_plan.  A workgroup takes a UNIT (item, slice of nodes_per_slice output nodes): the item's whole
+// velocity block [nd * dim rows][gw] as an LDS image of doubles, pitch gw + 1, and behind it (from the next multiple of 16
+// bytes) the image of the slice's values [nodes_per_slice * ncomp rows][pitch]; both within GRAD_LDS_BUDGET, so that two
+// workgroups fit a CU.  gw = 1: a thread per (cell, node), no LDS, chunks of GRAD_THREADS threads.  The grid strides over the
+// units, or chunks, beyond its cap.  (The images are doubles whatever the block's and the caller's word sizes.)
+static constexpr int64_t GRAD_LDS_BUDGET = 65536;
+static constexpr int GRAD_THREADS = 256;
+struct GradPlan {
+  int64_t item0 = 0, nitems = 0;
+  int64_t nodes_per_slice = 0, slices = 0;   // slice s: nodes s * nodes_per_slice .. min(nd, (s + 1) * nodes_per_slice) - 1
+  int64_t pitch = 0;
+  int64_t out_offset = 0;                    // bytes from the LDS base to the image of the values
+  int64_t units = 0, grid = 0, lds_bytes = 0;
+  bool ok = true;                            // false: not even one node's values fit beside the input image
+};
+inline GradPlan grad_plan(int gw, int ncls, int nd, int dim, int ncomp, int64_t cell0, int64_t ncells) {
+  GradPlan p;
+  if (ncells <= 0) return p;
+  if (gw == 1) {
+    p.item0 = cell0;
+    p.nitems = ncells;
+    p.nodes_per_slice = nd;
+    p.slices = 1;
+    p.units = (ncells * nd + GRAD_THREADS - 1) / GRAD_THREADS;
+  } else {
+    const int64_t g0 = cell0 / ncls / gw, g1 = (cell0 + ncells - 1) / ncls / gw;
+    p.item0 = g0 * ncls;
+    p.nitems = (g1 - g0 + 1) * ncls;
+    p.pitch = gw + 1;
+    const int64_t row = p.pitch * (int64_t)sizeof(double);
+    p.out_offset = ((int64_t)nd * dim * row + 15) / 16 * 16;
+    const int64_t fit = (GRAD_LDS_BUDGET - p.out_offset) / (ncomp * row);
+    if (fit < 1) {
+      p.ok = false;
+      return p;
+    }
+    p.slices = (nd + fit - 1) / fit;
+    p.nodes_per_slice = (nd + p.slices - 1) / p.slices;
+    p.slices = (nd + p.nodes_per_slice - 1) / p.nodes_per_slice;
+    p.units = p.nitems * p.slices;
+    p.lds_bytes = p.out_offset + p.nodes_per_slice * ncomp * row;
+  }
+  p.grid = std::min(p.units, XFER_GRID_CAP);
+  return p;
+}
+
 // Frames (seigen_hip.h sg_get_frame_dev; frame.cpp, kernels_frame.hip): a field rastered on a pixel lattice commensurate with
 // the block's cubes.  Along a FREE axis a every cube holds m[a] pixels, pixel j of a cube at the cube fraction (j + 1/2) / m[a];
 // a FIXED axis is the single plane x_a = at[a]: one layer of cubes and one fraction in it.  The Q = prod m[a] (free axes)

@@ -474,4 +474,19 @@ struct FrameTablePtrs {    // device pointers, gathered for the launch wrapper
 int launch_frame(const void* field, void* out, const FrameTablePtrs& t, int gw, int64_t units, int ncomp, int sym,
                  const int64_t stride[4], int f32, int c32, int grid, void* stream);
 
+// The gradient (kernels_grad.hip; seigen_hip.h sg_get_gradient_dev): the kind's ncomp values of the broken gradient of the
+// velocity buffer `field` (float where f32) at every node of `ncells` cells from `cell0`, into the caller's
+// out[cell][node][ncomp] (float where c32), by the plan of hostlogic.hpp grad_plan.  What a launch hands its kernel, scalar by scalar:
+struct GradArgs {
+  int64_t item0, units;        // gw > 1: (item, slice) units from item0; gw = 1: chunks of 256 (cell, node) threads
+  int64_t cell0, ncells;
+  int32_t slices, nodes_per_slice, pitch, out_offset;   // out_offset: bytes from the LDS base to the image of the values
+  int32_t gw, ncls, nd, dim, ncomp, kind;
+  int32_t n1;                  // tensor-product cells: P + 1, and C is the 1-D matrix [n1][n1]; simplices: 0, C dense [dim][nd][nd]
+  int32_t pad_;
+};
+// C and J (J[cls][3][3]) are device tables of the handle (handle.hpp GradTables)
+int launch_grad(const void* field, void* out, const double* C, const double* J, const GradArgs& a, int f32, int c32, int grid,
+                size_t lds_bytes, void* stream);
+
 }  // namespace sg

@@ -385,6 +385,55 @@ void tabulate(int dim, int P, int npts, const double* xi, double* phi, int kind)
   }
 }
 
+void tabulate_grad(int dim, int P, int npts, const double* xi, double* dphi, int kind) {
+  if (kind == KIND_TENSOR && dim >= 2) {
+    // the product rule on the 1-D factors: the derivative along axis r, the values along the others
+    const int n1 = P + 1;
+    int nd = 1;
+    for (int i = 0; i < dim; ++i) nd *= n1;
+    std::vector<double> x(npts);
+    std::vector<std::vector<double>> p1((size_t)dim, std::vector<double>((size_t)npts * n1)), d1 = p1;
+    for (int i = 0; i < dim; ++i) {
+      for (int p = 0; p < npts; ++p) x[p] = xi[(size_t)dim * p + i];
+      tabulate(1, P, npts, x.data(), p1[(size_t)i].data(), KIND_SIMPLEX);
+      tabulate_grad(1, P, npts, x.data(), d1[(size_t)i].data(), KIND_SIMPLEX);
+    }
+    for (int p = 0; p < npts; ++p)
+      for (int a = 0; a < nd; ++a)
+        for (int r = 0; r < dim; ++r) {
+          double v = 1.0;
+          int rest = a;
+          for (int i = 0; i < dim; ++i) {
+            v *= (i == r ? d1 : p1)[(size_t)i][(size_t)p * n1 + rest % n1];
+            rest /= n1;
+          }
+          dphi[((size_t)p * nd + a) * dim + r] = v;
+        }
+    return;
+  }
+  int nd = num_nodes(dim, P, kind);
+  std::vector<int> lat;
+  lattice_points(dim, P, lat, kind);
+  std::vector<real> C = lagrange_coeffs(dim, P, lat);
+  std::vector<real> mono(nd);
+  for (int p = 0; p < npts; ++p)
+    for (int r = 0; r < dim; ++r) {
+      // d(xi^gamma_m) / d(xi_r) = gamma_mr xi^(gamma_m - e_r)
+      for (int m = 0; m < nd; ++m) {
+        const int gr = lat[m * dim + r];
+        real v = (real)gr;
+        for (int i = 0; i < dim; ++i)
+          for (int e = 0; e < lat[m * dim + i] - (i == r ? 1 : 0); ++e) v *= (real)xi[p * dim + i];
+        mono[m] = v;
+      }
+      for (int a = 0; a < nd; ++a) {
+        real s = 0;
+        for (int m = 0; m < nd; ++m) s += C[m * nd + a] * mono[m];
+        dphi[((size_t)p * nd + a) * dim + r] = (double)s;
+      }
+    }
+}
+
 std::vector<double> sponge_tensor(int dim, int P, int q, int kind) {
   if (kind == KIND_TENSOR && dim >= 2) {   // A[a][c][b] = prod over the axes of A1[a_i][c_i][b_i]
     const std::vector<double> A1 = sponge_tensor(1, P, q, KIND_SIMPLEX);

@@ -35,6 +35,10 @@ RefElem make_refelem(int dim, int P, int kind = KIND_SIMPLEX);
 
 // phi[p][a] = Lagrange basis a of P_k at reference point xi[p][:]  (degree up to 8)
 void tabulate(int dim, int P, int npts, const double* xi, double* phi, int kind = KIND_SIMPLEX);
+// dphi[p][a][r] = d(phi_a)/d(xi_r) at xi[p][:]: the derivative of the interpolant's basis (D_r above is the weak operator, with
+// the derivative on the test function).  The same monomial expansion, differentiated term by term; tensor-product cells: the
+// 1-D derivative along axis r times the 1-D values along the others.
+void tabulate_grad(int dim, int P, int npts, const double* xi, double* dphi, int kind = KIND_SIMPLEX);
 
 // A[a][c][b] = sum_a' Minv[a][a'] int phi_a' psi_c phi_b, psi in P_q.  Size nd*nq*nd.
 // (absorption term -inner(w, sigma*u0)*dx, elastic.py:207-208, with sigma in DG_q)

@@ -832,6 +832,20 @@ class ElasticLF4(object):
     def reset_correlation(self):
         self._block.reset_correlation()
 
+    # ---- derivatives of the velocity at the nodes, on the device (sg_get_gradient_dev) ------------------
+    def strain_rate(self, out=None, dtype=None):
+        """The symmetric strain rate 1/2 (grad u + grad u^T) of u1 at the nodes of this rank's block - what a fibre or a
+        strainmeter records - as a torch tensor [cells, nodes, dim, dim] on the device (Function.gradient)."""
+        return self._block.get_gradient_dev(_lib.FIELD_U, "strain", out=out, dtype=dtype)
+
+    def dilatation(self, out=None, dtype=None):
+        """The dilatation rate div u1 [cells, nodes]: the P wave alone."""
+        return self._block.get_gradient_dev(_lib.FIELD_U, "div", out=out, dtype=dtype)
+
+    def rotation(self, out=None, dtype=None):
+        """The rotation rate curl u1, [cells, nodes, 3] in 3-D and [cells, nodes] in 2-D: the S wave alone."""
+        return self._block.get_gradient_dev(_lib.FIELD_U, "curl", out=out, dtype=dtype)
+
     # ---- frames: images of the wavefield taken inside the time loop (sg_get_frame_dev) ----------------
     def set_frames(self, function="velocity", m=1, slice=None, every=1, dtype=None):
         """Take a frame of `function` ("velocity" = VelocityNew or "stress" = StressNew; Function.frame has `m` and `slice`)

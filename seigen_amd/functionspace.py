@@ -257,6 +257,16 @@ class Function(object):
         block, field = self._bound("frame")
         return block.get_frame_dev(field, m=m, slice=slice, out=out, dtype=dtype)
 
+    def gradient(self, kind="grad", out=None, dtype=None):
+        """The cell-local gradient of a velocity Function at the nodes, on the device: a torch tensor [cells, nodes] + the
+        kind's value shape - "grad": (dim, dim) with [i, j] = d u_i / d x_j; "div": (); "curl": (3,) in 3-D, () in 2-D;
+        "strain": (dim, dim), the symmetric part.  The derivative of each cell's own polynomial, no facet terms; queued like
+        to_torch: no host copy, no host wait (HipBlock.get_gradient_dev)."""
+        block, field = self._bound("gradient")
+        if field not in (_lib.FIELD_U, _lib.FIELD_UH):
+            raise ValueError("gradient is taken of a velocity Function that has a device field (u0 / u1, uh1 / utemp), not of a stress")
+        return block.get_gradient_dev(field, kind, out=out, dtype=dtype)
+
     def from_torch(self, t):
         """Set the values from a contiguous float64 or float32 tensor [cells, nodes] + value_shape of the solver's device,
         moved on the device (a stress handed to a block in symmetric storage makes the host wait once)."""

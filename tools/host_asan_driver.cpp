@@ -1,6 +1,6 @@
 // CPU sanitizer driver (SURVEY 5 "sanitizers"; `make -C seigen_amd/csrc host-asan`): everything of libseigen_hip that
 // needs no device - reference elements, mesh tables, MFMA fragment tables, the sponge, source, receiver and injector plans, the items
-// of split-stage regions, the stage table, what stepping remembers between calls, the correlation's plan, the device-free C-ABI entry points - built with
+// of split-stage regions, the stage table, what stepping remembers between calls, the correlation's plan, the gradient's tables and plan, the device-free C-ABI entry points - built with
 // -fsanitize=address,undefined and walked over every (dim, degree, cell type, diagonal) the library accepts, plus the
 // argument errors the entry points must refuse.  Exit code 0 and no sanitizer report = clean.
 #include <algorithm>
@@ -1529,6 +1529,115 @@ static void spectra_clock_and_lines() {
   EXPECT(sg_spectra_lines(4, 0, nullptr, 16) == SG_ERR_ARG);
 }
 
+// The gradient's device-free half (sg_tabulate_grad_cell, sg_gradient_tables, sg_gradient_plan; hostlogic.hpp grad_dense_tables,
+// grad_plan): the derivative of the basis sums to zero and reproduces the coordinate functions at every degree up to 8; the
+// tables are the tabulation at the nodes and the mesh tables' Jinv, a tensor-product cell's line entries the 1-D matrix; the
+// plan's slices cover the nodes once within the LDS budget for every layout, element and kind.
+static void gradient_tables_and_plan(int cell_type, int dim) {
+  for (int P = 1; P <= 8; ++P) {
+    std::vector<int> lat;
+    lattice_points(dim, P, lat, cell_type);
+    const int nd = num_nodes(dim, P, cell_type);
+    const double pts[3][3] = {{0.25, 0.125, 0.5}, {0.0, 0.0, 0.0}, {1.0 / 3, 1.0 / 7, 1.0 / 5}};
+    std::vector<double> xi, dphi((size_t)3 * nd * dim);
+    for (const auto& p : pts) xi.insert(xi.end(), p, p + dim);
+    EXPECT(sg_tabulate_grad_cell(cell_type, dim, P, 3, xi.data(), dphi.data()) == SG_OK);
+    double worst = 0;
+    for (int p = 0; p < 3; ++p)
+      for (int r = 0; r < dim; ++r) {
+        double sum = 0, x[3] = {0, 0, 0};
+        for (int a = 0; a < nd; ++a) {
+          const double d = dphi[((size_t)p * nd + a) * dim + r];
+          sum += d;
+          for (int i = 0; i < dim; ++i) x[i] += d * lat[(size_t)a * dim + i] / P;   // the gradient of the coordinate x_i
+        }
+        worst = std::fmax(worst, std::fabs(sum));
+        for (int i = 0; i < dim; ++i) worst = std::fmax(worst, std::fabs(x[i] - (i == r ? 1.0 : 0.0)));
+      }
+    EXPECT(worst < (P <= 4 ? 1e-12 : 1e-8));
+    if (P > 4) continue;
+    sg_config cfg;
+    std::memset(&cfg, 0, sizeof(cfg));
+    cfg.dim = dim;
+    cfg.degree = P;
+    for (int a = 0; a < 3; ++a) {
+      cfg.n[a] = a < dim ? 3 : 1;
+      cfg.h[a] = 0.5 / (a + 1);
+    }
+    for (int diagonal : {0, 1}) {
+      cfg.diagonal = cell_type == KIND_TENSOR ? SG_DIAGONAL_QUAD : diagonal;
+      const int64_t n = sg_gradient_tables(&cfg, nullptr, nullptr);
+      EXPECT(n == (int64_t)dim * nd * nd);
+      if (n <= 0) continue;
+      const int ncls = classes_of(dim, cell_type);
+      std::vector<double> C((size_t)n), J((size_t)ncls * 9, -1.0);
+      EXPECT(sg_gradient_tables(&cfg, C.data(), J.data()) == n && sg_gradient_tables(&cfg, C.data(), nullptr) == n);
+      EXPECT(C == grad_dense_tables(cell_type, dim, P, lat));
+      std::vector<double> at((size_t)nd * dim), tab((size_t)nd * nd * dim);
+      for (size_t k = 0; k < at.size(); ++k) at[k] = (double)lat[k] / (double)P;
+      EXPECT(sg_tabulate_grad_cell(cell_type, dim, P, nd, at.data(), tab.data()) == SG_OK);
+      bool same = true, line = true;
+      const int n1 = P + 1;
+      for (int r = 0; r < dim; ++r)
+        for (int a = 0; a < nd; ++a)
+          for (int b = 0; b < nd; ++b) {
+            const double c = C[((size_t)r * nd + a) * nd + b];
+            same = same && c == tab[((size_t)a * nd + b) * dim + r];
+            if (cell_type != KIND_TENSOR) continue;
+            bool on = true;
+            for (int i = 0; i < dim; ++i) on = on && (i == r || lat[(size_t)a * dim + i] == lat[(size_t)b * dim + i]);
+            if (on) line = line && c == C[(size_t)lat[(size_t)a * dim + r] * nd + lat[(size_t)b * dim + r]];   // C1 = C[0][:n1][:n1]
+            else line = line && std::fabs(c) < 1e-14;
+          }
+      EXPECT(same && line && n1 <= nd);
+      for (int k = 0; k < ncls; ++k)
+        for (int r = 0; r < 3; ++r)
+          for (int j = 0; j < 3; ++j) {
+            const double v = J[((size_t)k * 3 + r) * 3 + j];
+            if (r >= dim || j >= dim) EXPECT(v == 0.0);
+            else if (cell_type == KIND_TENSOR) EXPECT(v == (r == j ? 1.0 / cfg.h[r] : 0.0));
+            else EXPECT(std::isfinite(v));
+          }
+      if (cell_type == KIND_TENSOR) break;
+    }
+    // the plan
+    const int ncls = classes_of(dim, cell_type);
+    for (int gw : {1, 16, 64})
+      for (int kind = 0; kind < 4; ++kind) {
+        const int ncomp = grad_ncomp(dim, kind);
+        if (ncomp == 0) {
+          EXPECT(kind == 2 && dim == 1);
+          continue;
+        }
+        for (int64_t ncube : {1, 17, 130}) {
+          const int64_t ncells = ncube * ncls;
+          for (const auto& rg : {std::pair<int64_t, int64_t>{0, ncells}, {ncells / 2, ncells - ncells / 2}, {ncells - 1, 1}, {0, 0}}) {
+            int64_t out[6] = {-1, -1, -1, -1, -1, -1}, xf[6];
+            const int rc = sg_gradient_plan(gw, ncls, nd, dim, ncomp, 8, 4, rg.first, rg.second, out);
+            const GradPlan p = grad_plan(gw, ncls, nd, dim, ncomp, rg.first, rg.second);
+            EXPECT((rc == SG_OK) == p.ok);
+            if (rc != SG_OK) continue;   // (an element whose velocity block alone is beyond the budget on that layout: refused, not planned)
+            EXPECT(sg_xfer_plan(gw, ncls, nd, ncomp, 8, 4, rg.first, rg.second, xf) == SG_OK && out[0] == xf[0] && out[1] == xf[1]);
+            EXPECT(out[5] <= GRAD_LDS_BUDGET && out[4] <= XFER_GRID_CAP);
+            if (rg.second == 0) {
+              EXPECT(out[4] == 0);
+              continue;
+            }
+            EXPECT(out[4] >= 1 && out[2] >= 1 && out[3] >= 1 && out[2] * out[3] >= nd && out[2] * (out[3] - 1) < nd);
+            if (gw > 1) EXPECT(p.out_offset % 16 == 0 && p.out_offset >= (int64_t)nd * dim * (gw + 1) * 8 && out[5] == p.out_offset + out[2] * ncomp * (gw + 1) * 8);
+          }
+        }
+      }
+  }
+  int64_t out[6];
+  double x = 0, d[8];
+  EXPECT(sg_gradient_plan(8, 1, 3, 1, 1, 8, 8, 0, 1, out) == SG_ERR_ARG && sg_gradient_plan(16, 1, 3, 1, 2, 8, 8, 0, 1, out) == SG_ERR_ARG);
+  EXPECT(sg_gradient_plan(16, 1, 3, 1, 1, 8, 8, 0, 1, nullptr) == SG_ERR_ARG);
+  EXPECT(sg_tabulate_grad_cell(0, 1, 9, 1, &x, d) == SG_ERR_ARG && sg_tabulate_grad_cell(2, 1, 2, 1, &x, d) == SG_ERR_ARG);
+  EXPECT(sg_tabulate_grad_cell(0, 1, 2, 1, nullptr, d) == SG_ERR_ARG && sg_tabulate_grad_cell(0, 1, 2, 1, &x, nullptr) == SG_ERR_ARG);
+  EXPECT(sg_gradient_tables(nullptr, nullptr, nullptr) == SG_ERR_ARG);
+}
+
 int main() {
   spectra_clock_and_lines();
   for (int cell_type : {0, 1})
@@ -1557,6 +1666,9 @@ int main() {
     tile_tables_2d(degree, KIND_SIMPLEX);
     tile_tables_2d(degree, KIND_TENSOR);
   }
+  for (int cell_type : {0, 1})
+    for (int dim = 1; dim <= 3; ++dim)
+      if (!(cell_type == 1 && dim == 1)) gradient_tables_and_plan(cell_type, dim);
   regions_and_coords();
   point_location();
   kernel_family_table();
