@@ -314,6 +314,16 @@ int sg_get_gradient(sg_handle* h, int field, int kind, int64_t cell0, int64_t nc
  * sg_tabulate_grad_cell at the nodes' reference points (lattice / degree) - and J[cls][3][3], the block's jinv.  Either may
  * be NULL; returns the number of doubles of C (NULL, NULL: a size query), or SG_ERR_ARG. */
 int64_t sg_gradient_tables(const sg_config* cfg, double* C, double* J);
+/* The class frame of the 3-D matrix-pipe F stages (device-free): tetrahedra of a 3-D block, class k = the reference simplex
+ * with the axes permuted by p[k].  Per class k = 0 .. 5: p[k][3]; s[k][3] = 1 / h[p[k][m]]; cn[k][4][2], the scaled normal of
+ * facet f at its non-zero columns {0} {0,1} {1,2} {2} of the permuted order (second entry 0 on facets 0 and 3);
+ * lines[k][2][36], per storage (0: full tensor, 1: symmetric) the line offsets in values of the field type: own[9] (slot
+ * 3 a + b: the line of T(p[a], p[b])), trace[4][6] (the neighbour lines facet f reads, in the order of kernels.hpp
+ * MfmaClassConst::cf_tr) and vel[3] (the line of velocity component p[i]).
+ * E and Ed, [3][nd][nd] each: the dense volume operators E_r (own-trace half of the flux folded in) and their differences
+ * E'_m = E_m - E_(m-1) as the F stages' tiles hold them (before the sign).  Any output may be NULL; returns nd, or SG_ERR_ARG
+ * (also when the block's tables do not have the shape the kernels are written to). */
+int64_t sg_mfma_class_frame(const sg_config* cfg, int32_t* p, double* s, double* cn, int32_t* lines, double* E, double* Ed);
 /* The launch plan of one call (device-free), the counterpart of sg_xfer_plan: out = first item, number of items, output nodes
  * per slice, slices per item, blocks of the grid (at most SG_XFER_GRID_CAP: the grid strides over the (item, slice) units
  * beyond it), bytes of LDS per block (at most 64 KiB: the item's velocity block and a slice's values as doubles, pitch

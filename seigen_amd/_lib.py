@@ -77,6 +77,7 @@ SYMBOLS = {
     "sg_get_gradient_dev": (C.c_int, [_P, C.c_int, C.c_int, C.c_int64, C.c_int64, _P, C.c_int, C.c_size_t]),
     "sg_get_gradient": (C.c_int, [_P, C.c_int, C.c_int, C.c_int64, C.c_int64, _P, C.c_size_t]),
     "sg_gradient_tables": (C.c_int64, [C.POINTER(SgConfig), _P, _P]),
+    "sg_mfma_class_frame": (C.c_int64, [C.POINTER(SgConfig), _P, _P, _P, _P, _P, _P]),
     "sg_gradient_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P]),
     "sg_tabulate_grad_cell": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, _P, _P]),
     "sg_set_absorption": (C.c_int, [_P, _P, C.c_int]),

@@ -120,6 +120,27 @@ def gradient_tables(cfg):
     return Ct, J
 
 
+def mfma_class_frame(cfg, operators=False):
+    """the class frame of the 3-D matrix-pipe F stages for the block `cfg` (an SgConfig) describes (sg_mfma_class_frame;
+    device-free): p [6, 3], s [6, 3], cn [6, 4, 2], own [6, 2, 9], trace [6, 2, 4, 6], vel [6, 3] - line offsets in values of
+    the field type, storage 0 = full tensor, 1 = symmetric - and, with operators, E and Ed [3, nd, nd]"""
+    L = _lib.load()
+    nd = L.sg_mfma_class_frame(C.byref(cfg), None, None, None, None, None, None)
+    if nd < 0:
+        raise _lib.SeigenHipError("sg_mfma_class_frame refuses the configuration")
+    p, s, cn = np.zeros((6, 3), dtype=np.int32), np.zeros((6, 3)), np.zeros((6, 4, 2))
+    lines = np.zeros((6, 2, 36), dtype=np.int32)
+    E, Ed = np.zeros((3, nd, nd)), np.zeros((3, nd, nd))
+    if L.sg_mfma_class_frame(C.byref(cfg), p.ctypes.data, s.ctypes.data, cn.ctypes.data, lines.ctypes.data,
+                             E.ctypes.data if operators else None, Ed.ctypes.data if operators else None) != nd:
+        raise _lib.SeigenHipError("sg_mfma_class_frame failed")
+    out = {"p": p, "s": s, "cn": cn, "own": lines[:, :, :9].copy(), "trace": lines[:, :, 9:33].reshape(6, 2, 4, 6).copy(),
+           "vel": lines[:, 0, 33:].copy()}
+    if operators:
+        out.update(E=E, Ed=Ed)
+    return out
+
+
 def gradient_plan(gw, ncls, nd, dim, ncomp, dev_bytes=8, caller_bytes=8, cell0=0, ncells=0):
     """sg_gradient_plan as a dict (device-free)"""
     out = np.zeros(6, dtype=np.int64)

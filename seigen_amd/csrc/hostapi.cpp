@@ -9,6 +9,8 @@
 #include <stdexcept>
 
 #include "hostlogic.hpp"
+#include "kernels.hpp"
+#include "mfma_tables.hpp"
 
 using namespace sg;
 
@@ -577,6 +579,49 @@ int64_t sg_gradient_tables(const sg_config* cfg, double* C, double* J) {
           for (int j = 0; j < 3; ++j) J[((size_t)c * 3 + r) * 3 + j] = md.Jinv[c][r][j];
     }
     return size;
+  } catch (const std::exception& e) {
+    g_create_err = e.what();
+    return SG_ERR_ARG;
+  }
+}
+
+int64_t sg_mfma_class_frame(const sg_config* cfg, int32_t* p, double* s, double* cn, int32_t* lines, double* E, double* Ed) {
+  if (!cfg || cfg->dim != 3 || cfg->degree < 1 || cfg->degree > 4 || cfg->diagonal == SG_DIAGONAL_QUAD) return SG_ERR_ARG;
+  for (int a = 0; a < 3; ++a)
+    if (!(cfg->h[a] > 0.0)) return SG_ERR_ARG;
+  try {
+    const RefElem re = make_refelem(3, cfg->degree, KIND_SIMPLEX);
+    MeshDev md;
+    std::memset(&md, 0, sizeof(md));
+    md.nd = re.nd;
+    md.nf = re.nf;
+    build_mesh_tables(3, cfg->degree, cfg->diagonal, cfg->h, re.fnode.data(), re.lattice.data(), md);
+    for (int k = 0; k < 6; ++k) {
+      MfmaClassConst kc;
+      std::memset(&kc, 0, sizeof(kc));
+      mfma_trace_lines(md, k, kc);
+      mfma_class_frame(md, k, kc);
+      for (int m = 0; m < 3; ++m) {
+        if (p) p[k * 3 + m] = kc.cf_p[m];
+        if (s) s[k * 3 + m] = kc.cf_s[m];
+      }
+      for (int f = 0; f < 4 && cn; ++f)
+        for (int c = 0; c < 2; ++c) cn[(k * 4 + f) * 2 + c] = kc.cf_cn[f][c];
+      for (int sym = 0; sym < 2 && lines; ++sym) {
+        int32_t* l = lines + (size_t)(k * 2 + sym) * 36;
+        for (int c = 0; c < 9; ++c) l[c] = kc.cf_own[sym][c];
+        for (int f = 0; f < 4; ++f)
+          for (int c = 0; c < 6; ++c) l[9 + f * 6 + c] = kc.cf_tr[sym][f][c];
+        for (int m = 0; m < 3; ++m) l[33 + m] = kc.cf_vel[m];
+      }
+    }
+    for (int r = 0; r < 3; ++r)
+      for (int a = 0; a < re.nd; ++a)
+        for (int b = 0; b < re.nd; ++b) {
+          if (E) E[((size_t)r * re.nd + a) * re.nd + b] = mfma_E(re, r, a, b);
+          if (Ed) Ed[((size_t)r * re.nd + a) * re.nd + b] = mfma_Ediff(re, r, a, b);
+        }
+    return re.nd;
   } catch (const std::exception& e) {
     g_create_err = e.what();
     return SG_ERR_ARG;

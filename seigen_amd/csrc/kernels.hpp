@@ -42,14 +42,43 @@ struct MfmaClassConst {
   uint32_t nbw[4][MK_KSF];    // [f][ks] byte q: neighbour ELEMENT node matching my facet node 4 ks + q (MeshDev::nb_node)
   uint32_t nfw[4][MK_KSF];    // same, as position in the neighbour's facet list (MeshDev::nb_fnode)
   int32_t nb_face[4];         // neighbour's local facet (MeshDev::nb_face)
-  // F stages: the stress lines facet f's scaled normal can see (mfma_trace_lines): the columns j with (c n)_j != 0 in
+  // What mfma_trace_lines found, in the FIXED axis order (no kernel reads these any more - the F stages read cf_tr / cf_cn
+  // below; they stay as the record of the check mfma_class_frame builds on, walked by tools/host_asan_driver.cpp, and cost
+  // 288 bytes of a table that is read by scalar loads of the used words only):
+  // the stress lines facet f's scaled normal can see: the columns j with (c n)_j != 0 in
   // ascending order ([1] = -1 on a cube-face facet, which has one), offset of the line of T(i, tr_col[c]) in values of the
   // field type [storage 0: full tensor, 1: symmetric][f][3 c + i] (c = 1 repeats c = 0 where there is no second column),
   // and (c n) at those columns (0 for the missing one)
   int32_t tr_col[4][2];
   int32_t tr_line[2][4][6];
   double tr_cn[4][2];
+  // F stages: the class in its own axis order (mfma_class_frame).  p: the class's permutation of the axes; register i' of a
+  // vector holds component p[i'], register slot (a, b) of a tensor holds T(p[a], p[b]).  Line offsets in values of the field
+  // type (slot * 16):
+  //   cf_vel[i']: component p[i'] of a velocity node;
+  //   cf_own[storage][3 a + b]: T(p[a], p[b]) of a stress node (symmetric storage: the same line for (a, b) and (b, a));
+  //   cf_tr[storage][f][c]: the neighbour lines of facet f in the order load_trace_face / load_trace_inner read them -
+  //     cube face (f = 0: column p[0], f = 3: column p[2]): c = i' < 3, T(p[i'], column);
+  //     inner facet, symmetric storage: the five lines its two columns see, T'(0,0) T'(0,1) T'(1,1) T'(2,0) T'(2,1) on facet 1
+  //       (columns 0, 1 of the frame) and the mirror set T'(2,2) T'(2,1) T'(1,1) T'(0,2) T'(0,1) on facet 2 (columns 2, 1);
+  //     inner facet, full storage: c = i': T(p[i'], lower column), c = 3 + i': T(p[i'], upper column);
+  //     (entries the kernels do not read repeat entry 0).
+  // cf_s[m] = 1 / h[p[m]]: J^-1 is the bidiagonal s_r e_p[r] - s_{r+1} e_p[r+1] in this order.
+  // cf_cn[f]: (c n)_f at its non-zero columns of the frame, {0} {0, 1} {1, 2} {2} for f = 0 .. 3 (second entry 0 on a cube face).
+  int32_t cf_p[3];
+  int32_t cf_vel[3];
+  int32_t cf_own[2][9];
+  int32_t cf_tr[2][4][6];
+  double cf_s[3];
+  double cf_cn[4][2];
 };
+// The second rule the F stage kernels are written to (kernels_mfma.hip do_volume, do_lifts), stated once: class k is the
+// reference simplex with the axes permuted by p (mesh_tables.cpp class_vertices), so with s_m = 1 / h[p[m]]
+//   row r of J^-1 = s_r e_p[r] - s_{r+1} e_p[r+1] (r = 0, 1), s_2 e_p[2] (r = 2), every other entry exactly zero, and
+//   (c n)_f = -1/2 grad lambda_f = (s_0 e_p[0]) / 2, -(row f - 1) / 2: non-zero at the frame's columns {0} {0,1} {1,2} {2}.
+// Fills cf_* of `kc` for class k from MeshDev::Jinv and MeshDev::cn (after mfma_trace_lines, whose nb_axis rule it relies
+// on); throws std::runtime_error if the tables do not have exactly this shape (sg_create then fails).
+void mfma_class_frame(const MeshDev& md_host, int k, MfmaClassConst& kc);
 // The rule the F stage kernels are written to (kernels_mfma.hip do_lifts), stated once: facets 0 and 3 of every class lie on
 // a cube face (nb_axis >= 0) and (c n) has ONE non-zero entry, at nb_axis; facets 1 and 2 are inside the cube (nb_axis < 0)
 // and (c n) has TWO; every other entry is exactly zero.  Fills tr_col / tr_line / tr_cn of `kc` for class k; throws

@@ -186,21 +186,35 @@ constexpr int SG_PRIO_F0 = 0x120, SG_PRIO_F1 = 0x320, SG_PRIO_F2 = 0x320, SG_PRI
 // a symmetric tensor, elastic.py:211-219; transfer.cpp checks what the user uploads), so only the six
 // lines (i <= j) of each node are read and written; the other three keep their slots but are
 // never touched.  Same results, 1/3 less stress traffic.
+// F reads a node's tensor in its class's own axis order (kernels.hpp mfma_class_frame): T[3 a + b] = T(p[a], p[b]), the
+// line of slot (a, b) at the wave-uniform offset ol[3 a + b] from the wave-uniform base pu, the lane `lane_off` of it.
+// (lane_at: a 64-bit scalar base and the lane's offset in BYTES as an unsigned 32-bit value is the one address form that
+// costs no vector instruction - global_load v, v_off, s[base:base+1]; an element index would be widened and shifted per load)
+template <typename R>
+__device__ __forceinline__ const R* lane_at(const R* pu, unsigned lane_off) {
+  return reinterpret_cast<const R*>(reinterpret_cast<const char*>(pu) + lane_off * (unsigned)sizeof(R));
+}
+// (a base that went through an opaque scalar is typed as global memory explicitly: the optimiser can no longer infer it)
+template <typename R>
+__device__ __forceinline__ __attribute__((address_space(1))) R* lane_at_g(__attribute__((address_space(1))) R* pu, unsigned lane_off) {
+  typedef __attribute__((address_space(1))) char gchar;
+  return (__attribute__((address_space(1))) R*)((gchar*)pu + lane_off * (unsigned)sizeof(R));
+}
 template <int SYM, typename R>
-__device__ __forceinline__ void load_tensor(const R* p, int stride, R (&T)[9]) {
+__device__ __forceinline__ void load_tensor(const R* pu, unsigned lane_off, const int (&ol)[9], R (&T)[9]) {
   if (SYM) {
-    T[0] = p[0];
-    T[1] = p[1 * stride];
-    T[2] = p[2 * stride];
-    T[4] = p[4 * stride];
-    T[5] = p[5 * stride];
-    T[8] = p[8 * stride];
+    T[0] = *lane_at(pu + ol[0], lane_off);
+    T[1] = *lane_at(pu + ol[1], lane_off);
+    T[2] = *lane_at(pu + ol[2], lane_off);
+    T[4] = *lane_at(pu + ol[4], lane_off);
+    T[5] = *lane_at(pu + ol[5], lane_off);
+    T[8] = *lane_at(pu + ol[8], lane_off);
     T[3] = T[1];
     T[6] = T[2];
     T[7] = T[5];
   } else {
 #pragma unroll
-    for (int c = 0; c < 9; ++c) T[c] = p[c * stride];
+    for (int c = 0; c < 9; ++c) T[c] = *lane_at(pu + ol[c], lane_off);
   }
 }
 __device__ __forceinline__ constexpr bool upper(int ij) { return (ij / 3) <= (ij % 3); }
@@ -210,43 +224,31 @@ __device__ __forceinline__ constexpr bool upper(int ij) { return (ij / 3) <= (ij
 // and two on the facets inside the cube (1 and 2); which ones is a property of (class, facet), tabulated on the host
 // and checked at create (mfma_tables.cpp mfma_trace_lines, MfmaClassConst::tr_*).  A line that only ever meets an exact
 // zero is not loaded.
-//   cube face: three loads, T[i] = T(i, a).  tl[i] = offset of that line, uniform over the wave.  GHOST = 1: a lane whose
-//     neighbour lives in another block reads the packed remote trace instead, whose record IS g_i = T(i, a) (kernels.hip
-//     pack_one): offset i.  Remote records exist on these facets only.
-//   else, symmetric storage: the six lines at their compile-time offsets, T[] = T00 T01 T02 T11 T12 T22.  Five of them
-//     are seen; picking those five takes selected offsets and a selection of the three flux rows, and measured slower
-//     than the sixth load (profiles/r10/f_trace_lines_variants.txt).
-//   else, full storage: six loads, T[3 c + i] = T(i, column c).
+// The lines are read in the class's own axis order (kernels.hpp mfma_class_frame, MfmaClassConst::cf_tr): row i' of the
+// result is component p[i'], and WHICH lines a facet sees is then the same for every class - the class is in the offsets.
+//   cube face: three loads, T[i'] = T(p[i'], a).  tl[i'] = offset of that line, uniform over the wave.  GHOST = 1: a lane
+//     whose neighbour lives in another block reads the packed remote trace instead, whose record IS g_i = T(i, a)
+//     (kernels.hip pack_one): offset gp[i'] = p[i'].  Remote records exist on these facets only.
+//   else, symmetric storage: the five lines the facet's two columns see, T'(x,x) T'(x,1) T'(1,1) T'(z,x) T'(z,1) with
+//     x = 0, z = 2 on facet 1 and x = 2, z = 0 on facet 2 (T' = the tensor in the frame).  (Picking five of the six lines
+//     in the FIXED axis order took selected offsets and a selection of the flux rows and measured slower than the sixth
+//     load, profiles/r10/f_trace_lines_variants.txt; in the frame there is nothing to select.)
+//   else, full storage: six loads, T[3 c + i'] = T(p[i'], column c of the two).
 // The loads stay unconditional and only their offsets are selected: a branch around them costs the F stages a factor
 // two (the hand-pipelined load/MFMA interleaving is lost).
-// (cube_face is a constant of the unrolled facet loop, not a run-time value)
-template <int SYM, int GHOST, typename R>
-__device__ __forceinline__ void load_trace(const bool cube_face, const R* p, bool ghost, const int (&tl)[6], R (&T)[6]) {
-  // (full storage: the lines of a column are 3 * 16 apart - one selected base per column, compile-time offsets from there)
-  if (cube_face) {
-    if (SYM) {
+// cube face: p = the lane's neighbour (or its remote record, or its own cell on the domain boundary) at the facet node
+template <int GHOST, typename R>
+__device__ __forceinline__ void load_trace_face(const R* p, bool ghost, const int (&tl)[6], const int (&gp)[3], R (&T)[6]) {
 #pragma unroll
-      for (int i = 0; i < 3; ++i) T[i] = p[GHOST ? (ghost ? i : tl[i]) : tl[i]];
-    } else {
-      const R* pa = p + ((GHOST && ghost) ? 0 : tl[0]);
+  for (int i = 0; i < 3; ++i) T[i] = p[GHOST ? (ghost ? gp[i] : tl[i]) : tl[i]];
+}
+// inner facet: the neighbour is another cell of the SAME cube, i.e. the same 16 lanes of another item of this cell group:
+// the base of its line c is wave-uniform (pl[c], an opaque scalar each - see line_of in mfma_stage_F) and a lane adds only
+// its own offset (node and cell) - no vector address arithmetic.
+template <int SYM, typename R>
+__device__ __forceinline__ void load_trace_inner(const __attribute__((address_space(1))) R* const (&pl)[6], unsigned lane_off, R (&T)[6]) {
 #pragma unroll
-      for (int i = 0; i < 3; ++i) T[i] = pa[GHOST ? (ghost ? i : i * 48) : i * 48];
-    }
-  } else if (SYM) {
-    T[0] = p[0];
-    T[1] = p[1 * 16];
-    T[2] = p[2 * 16];
-    T[3] = p[4 * 16];
-    T[4] = p[5 * 16];
-    T[5] = p[8 * 16];
-  } else {
-    const R *pa = p + tl[0], *pb = p + tl[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      T[i] = pa[i * 48];
-      T[3 + i] = pb[i * 48];
-    }
-  }
+  for (int c = 0; c < (SYM ? 5 : 6); ++c) T[c] = *lane_at_g(pl[c], lane_off);
 }
 
 // wave-uniform test on the bits (scalar compare and branch; there is no scalar f64 compare)
@@ -472,19 +474,19 @@ __device__ __forceinline__ float ndot<float>(float c0, float c1, float c2, float
 __device__ __forceinline__ double fma_of(double a, double b, double c) { return __builtin_fma(a, b, c); }
 __device__ __forceinline__ float fma_of(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 
-// Row i of a facet's flux, wf (c n)_j T_ij, out of the lines load_trace left in T: ndot with its exactly-zero terms left
-// out - the lower column's product first, the other one added by an fma, then wf.  A term 0 * finite changes no rounding,
-// so the value is what ndot over all three columns gives (the sign of a zero may differ).  cnf: (c n) of the facet,
-// tc: its entries at the non-zero columns (MfmaClassConst::tr_cn).
+// Row i' of facet f's flux, wf (c n)_j T_ij, out of the lines load_trace_face / load_trace_inner left in T: the terms of the facet's non-zero
+// columns alone - the lower column's product first, the other one added by an fma.  wc: wf (c n) at those columns in
+// ascending order (MfmaClassConst::cf_cn; wf = +-1, so the products are exact and formed once per facet).
 template <int SYM, typename R>
-__device__ __forceinline__ R trace_flux(const bool cube_face, int i, R wf, const R (&cnf)[3], const R (&tc)[2], const R (&T)[6]) {
-  if (cube_face) return wf * (tc[0] * T[i]);
-  if (SYM) {  // row i of the symmetric tensor in T00 T01 T02 T11 T12 T22
-    const int s0 = i, s1 = i == 0 ? 1 : (i == 1 ? 3 : 4), s2 = i == 0 ? 2 : (i == 1 ? 4 : 5);
-    return wf * ndot<R>(cnf[0], cnf[1], cnf[2], T[s0], T[s1], T[s2]);
+__device__ __forceinline__ R trace_flux(const int f, int i, const R (&wc)[2], const R (&T)[6]) {
+  if (f == 0 || f == 3) return wc[0] * T[i];
+  if (SYM) {  // T'(i', x) and T'(i', 1) are neighbours in the five lines: rows x, 1, z start at 0, 1, 3
+    const int x = f == 1 ? 0 : 2;
+    const int a = i == x ? 0 : (i == 1 ? 1 : 3);
+    if (f == 1) return fma_of(wc[1], T[a + 1], wc[0] * T[a]);
+    return fma_of(wc[1], T[a], wc[0] * T[a + 1]);
   }
-  const R r = tc[0] * T[i];
-  return wf * fma_of(tc[1], T[3 + i], r);
+  return fma_of(wc[1], T[3 + i], wc[0] * T[i]);
 }
 
 
@@ -1030,8 +1032,6 @@ __global__ __launch_bounds__(256, (mfma_resident_blocks<R, P>())) void mfma_stag
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int q = lane >> 4, w = lane & 15;
-  typedef __attribute__((address_space(4))) const MeshDev cMeshDev;
-  const cMeshDev* md = (const cMeshDev*)(unsigned long long)A.md;
   const R* __restrict__ in = reinterpret_cast<const R*>(A.in);
   const R* __restrict__ aux = reinterpret_cast<const R*>(A.aux);
   R* __restrict__ out = reinterpret_cast<R*>(A.out);
@@ -1052,32 +1052,46 @@ __global__ __launch_bounds__(256, (mfma_resident_blocks<R, P>())) void mfma_stag
     const nbr4 nbe = load_nbr4(A, item, w);
     if (!__any(L.active)) continue;
     const R* own = in + ((g * 6 + k) * (long)ND) * 9 * 16 + w;
-    int qo = q * 9 * 16;  // B rows: see mfma_stage_G
+    // B rows: a wave-uniform base (the item's first line; the class's line offset is added to it, in scalars) and the
+    // lane's offset from it - node 4 ks + q, cell w.  Opaque per item, as in mfma_stage_G.
+    const R* ownu = in + ((g * 6 + k) * (long)ND) * 9 * 16;
+    int qo = q * 9 * 16 + w;
     asm volatile("" : "+v"(qo));
-    const R* ownq = own + qo;
-    const R* ownl = (4 * (KS - 1) + q < ND) ? ownq + (KS - 1) * 4 * 9 * 16 : own;
-    auto brow = [&](int ks) { return (ks == KS - 1) ? ownl : ownq + ks * 4 * 9 * 16; };
+    const int qol = (4 * (KS - 1) + q < ND) ? qo + (KS - 1) * 4 * 9 * 16 : w;
+    auto brow = [&](int ks) { return (unsigned)((ks == KS - 1) ? qol : qo + ks * 4 * 9 * 16); };
     int lo = lane;
     asm volatile("" : "+v"(lo));
 
-    R Jm[3][3], cnf[4][3];
+    // The item works in its class's own axis order (kernels.hpp mfma_class_frame): accumulator i' is velocity component
+    // p[i'], tensor slot (a, b) is T(p[a], p[b]).  J^-1 and the facets' non-zero columns are then the same for every class;
+    // the class enters through the scale factors sm, the values of (c n) and the wave-uniform line offsets below.
+    R sm[3];
+    int vl[3], ol[9];
 #pragma unroll
-    for (int r = 0; r < 3; ++r)
+    for (int m = 0; m < 3; ++m) {
+      sm[m] = (R)kc.cf_s[m];
+      vl[m] = kc.cf_vel[m];
+    }
 #pragma unroll
-      for (int j = 0; j < 3; ++j) Jm[r][j] = (R)md->Jinv[k][r][j];
-#pragma unroll
-    for (int f = 0; f < 4; ++f)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) cnf[f][j] = (R)md->cn[k][f][j];
+    for (int c = 0; c < 9; ++c) ol[c] = kc.cf_own[SYM ? 1 : 0][c];
 
     // rows 16t + 4reg + q in acc[i][t][reg] (large tiles), row 16*MTF + 4s + q in accs[i][s] (small)
     d4 acc[3][M::MTFA];
     R accs[3][M::NSMA];
     const long e = (L.valid ? L.c : 0) * 6 + k;
-    const long ubase = ((g * 6 + k) * (long)ND) * 3 * 16 + w;
-    int qo3 = q * 3 * 16;  // output rows: per-item base + compile-time offsets (see brow)
+    // output rows: like the B rows a wave-uniform base per component line (component p[i'] at vl[i']) and the lane's offset
+    const long ubu = ((g * 6 + k) * (long)ND) * 3 * 16;
+    int qo3 = q * 3 * 16 + w;
     asm volatile("" : "+v"(qo3));
-    const long ub_q = ubase + qo3;
+    const long ub_q = ubu + qo3;
+    // (opaque scalars: left to itself the optimiser re-associates base + lane + line and adds the line per lane and access;
+    //  formed where a group of accesses starts, not per item: six scalar pairs held through the item spill in the float kernels)
+    typedef __attribute__((address_space(1))) R gR;
+    auto line_of = [&](const R* field, int i) {
+      const gR* l = (const gR*)(field + (ubu + vl[i]));
+      asm volatile("" : "+s"(l));
+      return l;
+    };
     // Fused combine u = c_self u + c_aux uh1 + c_new rhs (MODE 1), EARLY form: the old values are requested at the
     // START of the item, together with the first own rows, and enter the accumulators as (c_self u + c_aux uh1) / c_new;
     // the matrix products add rhs on top and the epilogue only scales by c_new and stores - no loads, no second
@@ -1117,27 +1131,33 @@ __global__ __launch_bounds__(256, (mfma_resident_blocks<R, P>())) void mfma_stag
     // old values of the in-place combine: every one of the item requested before the first is used
     R po[M::MTFA][4][3], pa[M::MTFA][4][3], pos[M::NSMA][3], pas[M::NSMA][3];
     auto fetch_old = [&]() {
+      const gR *outl[3], *auxl[3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        outl[i] = SELF ? line_of(out, i) : nullptr;
+        auxl[i] = line_of(aux, i);
+      }
 #pragma unroll
       for (int t = 0; t < MTF; ++t)
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
           // the last float tile is zero-padded: its rows beyond ND read a valid address and are not stored
           const bool row_ok = RT<R>::SMALL || (16 * t + 4 * reg + q < ND);
-          const long o = row_ok ? ub_q + (long)(16 * t + 4 * reg) * 3 * 16 : ubase;
+          const unsigned o = (unsigned)(row_ok ? qo3 + (16 * t + 4 * reg) * 3 * 16 : w);
 #pragma unroll
           for (int i = 0; i < 3; ++i) {
-            po[t][reg][i] = SELF ? LD_STREAM(&out[o + i * 16]) : R(0);
-            pa[t][reg][i] = LD_STREAM(&aux[o + i * 16]);
+            po[t][reg][i] = SELF ? LD_STREAM(lane_at_g(outl[i], o)) : R(0);
+            pa[t][reg][i] = LD_STREAM(lane_at_g(auxl[i], o));
           }
         }
 #pragma unroll
       for (int t = 0; t < NSM; ++t) {
         const int a = 16 * MTF + 4 * t + q;
-        const long o = (a < ND) ? ub_q + (long)(16 * MTF + 4 * t) * 3 * 16 : ubase;
+        const unsigned o = (unsigned)((a < ND) ? qo3 + (16 * MTF + 4 * t) * 3 * 16 : w);
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-          pos[t][i] = SELF ? LD_STREAM(&out[o + i * 16]) : R(0);
-          pas[t][i] = LD_STREAM(&aux[o + i * 16]);
+          pos[t][i] = SELF ? LD_STREAM(lane_at_g(outl[i], o)) : R(0);
+          pas[t][i] = LD_STREAM(lane_at_g(auxl[i], o));
         }
       }
     };
@@ -1167,25 +1187,26 @@ __global__ __launch_bounds__(256, (mfma_resident_blocks<R, P>())) void mfma_stag
     SG_PRIO(SG_PRIO_VOL);
     STAMP(st1);
     auto do_volume = [&]() {
-      // ---- volume: K runs over (r, node); B = T~_ir = Jinv_rj T_ij formed in registers
+      // ---- volume: K runs over (m, node); B = s_m T_i,p[m], one own line times one scalar (the tiles are the E'_m of
+      //      mfma_tables.cpp mfma_frags_F)
       {
         constexpr int PFV = sizeof(R) == 4 ? 2 : 1;  // k-steps of own tensors in flight ahead of the MFMAs
         R Tq[PFV][9];
 #pragma unroll
-        for (int s0 = 0; s0 < PFV && s0 < KS; ++s0) load_tensor<SYM>(brow(s0), 16, Tq[s0]);
+        for (int s0 = 0; s0 < PFV && s0 < KS; ++s0) load_tensor<SYM>(ownu, brow(s0), ol, Tq[s0]);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
           R T[9];
 #pragma unroll
           for (int c = 0; c < 9; ++c) T[c] = Tq[ks % PFV][c];
           if (ks + PFV < KS) {
-            load_tensor<SYM>(brow(ks + PFV), 16, Tq[ks % PFV]);
+            load_tensor<SYM>(ownu, brow(ks + PFV), ol, Tq[ks % PFV]);
           }
 #pragma unroll
           for (int r = 0; r < 3; ++r) {
             R Tt[3];
 #pragma unroll
-            for (int i = 0; i < 3; ++i) Tt[i] = Jm[r][0] * T[i * 3 + 0] + Jm[r][1] * T[i * 3 + 1] + Jm[r][2] * T[i * 3 + 2];
+            for (int i = 0; i < 3; ++i) Tt[i] = sm[r] * T[i * 3 + r];
 #pragma unroll
             for (int t = 0; t < MTT; ++t) {
               const R a = sAV[(t * 3 * KS + KS * r + ks) * 64 + lo];
@@ -1211,36 +1232,64 @@ __global__ __launch_bounds__(256, (mfma_resident_blocks<R, P>())) void mfma_stag
       // facet k-steps of neighbour traces in flight (three in double, in the registers the unseen lines freed, leave the
       // step where it is: profiles/r10/f_trace_lines_variants.txt)
       constexpr int PFL = sizeof(R) == 4 ? 3 : 2;
-      const R* np[4];
-      R wf[4];
-      int noff[4][KSF];
-      bool gh[4];
-      // the lines each facet's normal can see and (c n) at their columns (load_trace, trace_flux): wave-uniform
-      int tl[4][6];
-      R tc[4][2];
+      auto cube_face = [](int f) { return f == 0 || f == 3; };
+      // cube faces (slot f / 3): the lane's neighbour and whether it is a remote record; inner facets (slot f - 1): the line
+      // bases of the neighbour item of this cell group
+      const R* np[2];
+      bool gh[2];
+      const gR* npl[2][6];
+      R wc[4][2];   // wf (c n) at the facet's columns; wf = -1 on the domain boundary (cube faces only)
+      int noff[4][KSF];   // the lane's offset of the facet node at k-step ks (inner facets: its cell w included)
+      // the lines each facet's normal can see and the entries of a remote record, in the frame: wave-uniform
+      int tl[4][6], gp[3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) gp[i] = kc.cf_p[i];
 #pragma unroll
       for (int f = 0; f < 4; ++f) {
-        const NbrRef<R> NR = nbr_from_entry<ND, NF, 9>(A, nbe[f], 2 * kc.nb_axis[f] + (kc.nb_dir[f] > 0 ? 1 : 0), own);
-        np[f] = NR.p;
-        gh[f] = GHOST && NR.ghost;
 #pragma unroll
-        for (int c = 0; c < 6; ++c) tl[f][c] = kc.tr_line[SYM ? 1 : 0][f][c];
-        tc[f][0] = (R)kc.tr_cn[f][0];
-        tc[f][1] = (R)kc.tr_cn[f][1];
-        wf[f] = NR.physical ? R(-1) : R(1);
-        const int var = NR.ghost ? 1 : (NR.physical ? 2 : 0);
+        for (int c = 0; c < 6; ++c) tl[f][c] = kc.cf_tr[SYM ? 1 : 0][f][c];
+        int var = 0;
+        if (cube_face(f)) {
+          const NbrRef<R> NR = nbr_from_entry<ND, NF, 9>(A, nbe[f], 2 * kc.nb_axis[f] + (kc.nb_dir[f] > 0 ? 1 : 0), own);
+          np[f / 3] = NR.p;
+          gh[f / 3] = GHOST && NR.ghost;
+          const R wf = NR.physical ? R(-1) : R(1);
+          wc[f][0] = wf * (R)kc.cf_cn[f][0];
+          wc[f][1] = R(0);
+          var = NR.ghost ? 1 : (NR.physical ? 2 : 0);
+        } else {
+          // (layout-padding lanes, whose table entries say "domain boundary", read the neighbour item's padding like every
+          // other lane: allocated, and nothing of theirs is stored)
+          wc[f][0] = (R)kc.cf_cn[f][0];
+          wc[f][1] = (R)kc.cf_cn[f][1];
+        }
         const nbr4 o4 = sFt[((var * 6 + k) * 4 + f) * 4 + q];
 #pragma unroll
-        for (int ks = 0; ks < KSF; ++ks) noff[f][ks] = o4[ks];
+        for (int ks = 0; ks < KSF; ++ks) noff[f][ks] = cube_face(f) ? o4[ks] : o4[ks] + w;
       }
       R nq[PFL][6];
-      auto cube_face = [](int f) { return f == 0 || f == 3; };
+      // k-step ks of facet f into T.  The line bases of an inner facet are formed as opaque scalars (see line_of) when its
+      // first k-step is requested - all of them held from the set-up on are ten scalar pairs more than the float kernels have
+      auto request = [&](int f, int ks, R (&T)[6]) {
+        if (cube_face(f)) {
+          load_trace_face<GHOST>(np[f / 3] + noff[f][ks], gh[f / 3], tl[f], gp, T);
+          return;
+        }
+        if (ks == 0) {
+          const R* const nbu = in + ((g * 6 + kc.nb_cls[f]) * (long)ND) * 9 * 16;
+#pragma unroll
+          for (int c = 0; c < (SYM ? 5 : 6); ++c) {
+            npl[f - 1][c] = (const gR*)(nbu + tl[f][c]);
+            asm volatile("" : "+s"(npl[f - 1][c]));
+          }
+        }
+        load_trace_inner<SYM>(npl[f - 1], (unsigned)noff[f][ks], T);
+      };
       STAMP(sta);   // diagnostic builds: end of the neighbour set-up
       {
         constexpr int NS = 4 * KSF;
 #pragma unroll
-        for (int s = 0; s < PFL; ++s)
-          load_trace<SYM, GHOST>(cube_face(s / KSF), np[s / KSF] + noff[s / KSF][s % KSF], gh[s / KSF], tl[s / KSF], nq[s]);
+        for (int s = 0; s < PFL; ++s) request(s / KSF, s % KSF, nq[s]);
 #pragma unroll
         for (int f = 0; f < 4; ++f) {
           if (f == 1) STAMP(stb);   // diagnostic builds: end of facet 0
@@ -1250,10 +1299,9 @@ __global__ __launch_bounds__(256, (mfma_resident_blocks<R, P>())) void mfma_stag
             R fl[3];
 #pragma unroll
             for (int i = 0; i < 3; ++i)
-              fl[i] = trace_flux<SYM>(cube_face(f), i, wf[f], cnf[f], tc[f], nq[s % PFL]);
+              fl[i] = trace_flux<SYM>(f, i, wc[f], nq[s % PFL]);
             if (s + PFL < NS) {
-              const int f1 = (s + PFL) / KSF, k1 = (s + PFL) % KSF;
-              load_trace<SYM, GHOST>(cube_face(f1), np[f1] + noff[f1][k1], gh[f1], tl[f1], nq[s % PFL]);
+              request((s + PFL) / KSF, (s + PFL) % KSF, nq[s % PFL]);
             }
 #pragma unroll
             for (int t = 0; t < MTT; ++t) {
@@ -1306,7 +1354,7 @@ __global__ __launch_bounds__(256, (mfma_resident_blocks<R, P>())) void mfma_stag
           for (int r = 0; r < NR; ++r) {
             const int o = (4 * r + q < ND) ? 4 * r * 3 * es : 0;
 #pragma unroll
-            for (int i = 0; i < 3; ++i) uo[r][i] = pb[o + i * es];
+            for (int i = 0; i < 3; ++i) uo[r][i] = pb[o + vl[i]];      // (es = 16: component p[i'] of the node)
           }
 #pragma unroll
           for (int r = 0; r < NR; ++r)
@@ -1358,23 +1406,26 @@ __global__ __launch_bounds__(256, (mfma_resident_blocks<R, P>())) void mfma_stag
         }
     }
     if (L.active) {
+      gR* outl[3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) outl[i] = (gR*)line_of(out, i);
 #pragma unroll
       for (int t = 0; t < MTF; ++t)
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) {
-          const long o = ub_q + (long)(16 * t + 4 * reg) * 3 * 16;
+          const unsigned o = (unsigned)(qo3 + (16 * t + 4 * reg) * 3 * 16);
           if (RT<R>::SMALL || (16 * t + 4 * reg + q < ND)) {
 #pragma unroll
-            for (int i = 0; i < 3; ++i) ST_STREAM(&out[o + i * 16], acc[i][t][reg]);
+            for (int i = 0; i < 3; ++i) ST_STREAM(lane_at_g(outl[i], o), acc[i][t][reg]);
           }
         }
 #pragma unroll
       for (int t = 0; t < NSM; ++t) {
         const int a = 16 * MTF + 4 * t + q;
         if (a < ND) {
-          const long o = ub_q + (long)(16 * MTF + 4 * t) * 3 * 16;
+          const unsigned o = (unsigned)(qo3 + (16 * MTF + 4 * t) * 3 * 16);
 #pragma unroll
-          for (int i = 0; i < 3; ++i) ST_STREAM(&out[o + i * 16], accs[i][t]);
+          for (int i = 0; i < 3; ++i) ST_STREAM(lane_at_g(outl[i], o), accs[i][t]);
         }
       }
     }

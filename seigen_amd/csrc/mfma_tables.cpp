@@ -58,6 +58,27 @@ static inline int tile_row(const MfmaGeom& g, int t, int l) {
   return (t < g.mtf) ? 16 * t + (l & 15) : 16 * g.mtf + 4 * (t - g.mtf) + (l & 3);
 }
 
+// The same entry in long double (the operators themselves are doubles): the simplex fold of Eval
+static inline long double EvalL(const RefElem& re, int r, int a, int b) {
+  if (a >= re.nd || b >= re.nd) return 0.0L;
+  const long double cfold = (re.dim == 3) ? 0.25L : 0.5L;
+  long double v = re.D[((size_t)r * re.nd + a) * re.nd + b];
+  for (int bf = 0; bf < re.nf; ++bf) {
+    if (re.fnode[(size_t)0 * re.nf + bf] == b) v -= cfold * (long double)re.L[((size_t)0 * re.nd + a) * re.nf + bf];
+    if (re.fnode[(size_t)(r + 1) * re.nf + bf] == b) v += cfold * (long double)re.L[((size_t)(r + 1) * re.nd + a) * re.nf + bf];
+  }
+  return v;
+}
+
+// E'_m = E_m - E_{m-1} (E_{-1} = 0), the difference taken before rounding.  In a Kuhn class's own axis order (kernels.hpp
+// mfma_class_frame) J^-1 is the bidiagonal s_r e_p[r] - s_{r+1} e_p[r+1], so
+//   sum_r E_r (J^-1_rj T_ij) = sum_m E'_m (s_m T_i,p[m]):
+// the B operand of direction m is ONE stress line times one scalar, and the tiles do not depend on the class.
+double mfma_E(const RefElem& re, int r, int a, int b) { return Eval(re, r, a, b); }
+double mfma_Ediff(const RefElem& re, int m, int a, int b) {
+  return (double)(EvalL(re, m, a, b) - (m > 0 ? EvalL(re, m - 1, a, b) : 0.0L));
+}
+
 std::vector<double> mfma_frags_F(const RefElem& re) {
   MfmaGeom g = mfma_geom(re);
   std::vector<double> out((size_t)g.mtt * 3 * g.ks * 64, 0.0);
@@ -65,7 +86,7 @@ std::vector<double> mfma_frags_F(const RefElem& re) {
     for (int r = 0; r < 3; ++r)
       for (int k0 = 0; k0 < g.ks; ++k0) {
         size_t frag = (size_t)t * 3 * g.ks + (size_t)g.ks * r + k0;
-        for (int l = 0; l < 64; ++l) out[frag * 64 + l] = -Eval(re, r, tile_row(g, t, l), 4 * k0 + (l >> 4));
+        for (int l = 0; l < 64; ++l) out[frag * 64 + l] = -mfma_Ediff(re, r, tile_row(g, t, l), 4 * k0 + (l >> 4));
       }
   return out;
 }
@@ -218,7 +239,7 @@ std::vector<float> mfma32_frags_F(const RefElem& re) {
     for (int r = 0; r < 3; ++r)
       for (int k0 = 0; k0 < ks; ++k0) {
         size_t frag = (size_t)t * 3 * ks + (size_t)ks * r + k0;
-        for (int l = 0; l < 64; ++l) out[frag * 64 + l] = (float)-Eval(re, r, tile_row32(t, l), 4 * k0 + (l >> 4));
+        for (int l = 0; l < 64; ++l) out[frag * 64 + l] = (float)-mfma_Ediff(re, r, tile_row32(t, l), 4 * k0 + (l >> 4));
       }
   return out;
 }
@@ -355,8 +376,87 @@ MfmaConst mfma_const(const MeshDev& md) {
       }
     }
     mfma_trace_lines(md, k, kc);
+    mfma_class_frame(md, k, kc);
   }
   return c;
+}
+
+void mfma_class_frame(const MeshDev& md, int k, MfmaClassConst& kc) {
+  auto refuse = [&](const std::string& what) {
+    throw std::runtime_error("MFMA class frame: class " + std::to_string(k) + ": " + what +
+                             "; the F stage kernels need J^-1 = s_r e_p[r] - s_(r+1) e_p[r+1] for one permutation p of the axes");
+  };
+  // p[2]: the one non-zero of the last row; p[1], p[0]: the non-zero of the rows above that is not the column below
+  int p[3] = {-1, -1, -1};
+  for (int r = 2; r >= 0; --r) {
+    int nnz = 0;
+    for (int j = 0; j < 3; ++j) {
+      const double v = md.Jinv[k][r][j];
+      if (!std::isfinite(v)) refuse("J^-1 is not finite");
+      if (v == 0.0) continue;
+      nnz += 1;
+      if (r == 2 || j != p[r + 1]) p[r] = j;
+    }
+    if (nnz != (r == 2 ? 1 : 2) || p[r] < 0) refuse("row " + std::to_string(r) + " of J^-1 has " + std::to_string(nnz) + " non-zero entries");
+  }
+  if (p[0] == p[1] || p[0] == p[2] || p[1] == p[2]) refuse("the non-zero entries of J^-1 name no permutation");
+  double s[3];
+  for (int m = 0; m < 3; ++m) {
+    s[m] = md.Jinv[k][m][p[m]];
+    if (!(s[m] > 0.0)) refuse("a diagonal entry of J^-1 in the class's order is not positive");
+    if (m > 0 && md.Jinv[k][m - 1][p[m]] != -s[m]) refuse("the entry above a diagonal one is not its negative");
+  }
+  // (c n)_f = -1/2 grad lambda_f in the frame: every entry, the zeros included
+  for (int f = 0; f < 4; ++f)
+    for (int j = 0; j < 3; ++j) {
+      double want = 0.0;
+      if (f == 0) want = j == 0 ? 0.5 * s[0] : 0.0;
+      else if (j == f - 1) want = -0.5 * s[j];
+      else if (j == f) want = 0.5 * s[j];
+      if (md.cn[k][f][p[j]] != want) refuse("the scaled normal of facet " + std::to_string(f) + " is not -1/2 grad lambda");
+    }
+  if (md.nb_axis[k][0] != p[0] || md.nb_axis[k][3] != p[2] || md.nb_axis[k][1] >= 0 || md.nb_axis[k][2] >= 0)
+    refuse("facets 0 and 3 do not cross the cube faces normal to p[0] and p[2]");
+  for (int m = 0; m < 3; ++m) {
+    kc.cf_p[m] = p[m];
+    kc.cf_vel[m] = p[m] * 16;
+    kc.cf_s[m] = s[m];
+  }
+  kc.cf_cn[0][0] = md.cn[k][0][p[0]];
+  kc.cf_cn[0][1] = 0.0;
+  kc.cf_cn[1][0] = md.cn[k][1][p[0]];
+  kc.cf_cn[1][1] = md.cn[k][1][p[1]];
+  kc.cf_cn[2][0] = md.cn[k][2][p[1]];
+  kc.cf_cn[2][1] = md.cn[k][2][p[2]];
+  kc.cf_cn[3][0] = md.cn[k][3][p[2]];
+  kc.cf_cn[3][1] = 0.0;
+  for (int sym = 0; sym < 2; ++sym) {
+    auto line = [&](int a, int b) { return stress_line_slot(sym != 0, p[a], p[b]) * 16; };
+    for (int a = 0; a < 3; ++a)
+      for (int b = 0; b < 3; ++b) kc.cf_own[sym][3 * a + b] = line(a, b);
+    for (int f = 0; f < 4; ++f) {
+      int32_t* t = kc.cf_tr[sym][f];
+      if (f == 0 || f == 3) {
+        const int col = f == 0 ? 0 : 2;
+        for (int i = 0; i < 3; ++i) t[i] = line(i, col);
+        for (int c = 3; c < 6; ++c) t[c] = t[0];
+      } else if (sym) {
+        // facet 1 sees the frame's columns 0, 1; facet 2 the columns 2, 1: the same five slots with 0 and 2 exchanged
+        const int x = f == 1 ? 0 : 2, z = 2 - x;
+        t[0] = line(x, x);
+        t[1] = line(x, 1);
+        t[2] = line(1, 1);
+        t[3] = line(z, x);
+        t[4] = line(z, 1);
+        t[5] = t[0];
+      } else {
+        for (int i = 0; i < 3; ++i) {
+          t[i] = line(i, f - 1);
+          t[3 + i] = line(i, f);
+        }
+      }
+    }
+  }
 }
 
 void mfma_trace_lines(const MeshDev& md, int k, MfmaClassConst& kc) {

@@ -39,11 +39,15 @@ struct MfmaGeom {
 
 MfmaGeom mfma_geom(const RefElem& re);
 
-// F volume: out = sum_r (-D_r) T~_r  as one product with K = 3 * (4*ks):
-//   frag (t, kk), kk = ks*r + k0:  A[row][col] = -E_r[row0(t) + row][4 k0 + col]
+// F volume: out = sum_m (-E'_m) (s_m T_i,p[m])  as one product with K = 3 * (4*ks):
+//   frag (t, kk), kk = ks*m + k0:  A[row][col] = -E'_m[row0(t) + row][4 k0 + col]
 // where row tile t < mtf is large (row0 = 16 t) and t >= mtf small (row0 = 16 mtf + 4 (t - mtf))
-// (E_r = D_r minus the own-trace half of the central flux, see mfma_tables.cpp)
+// (E_r = D_r minus the own-trace half of the central flux; E'_m = E_m - E_{m-1}, the operator of direction m in a Kuhn
+// class's own axis order, see mfma_tables.cpp)
 std::vector<double> mfma_frags_F(const RefElem& re);
+// entry (a, b) of E_r and of E'_m, simplex element (a, b beyond nd: 0)
+double mfma_E(const RefElem& re, int r, int a, int b);
+double mfma_Ediff(const RefElem& re, int m, int a, int b);
 // G volume: the row tiles of E_0, E_1, E_2 one after the other:
 //   frag ((r*mtt + t)*ks + k0): A[row][col] = E_r[row0(t) + row][4 k0 + col]
 std::vector<double> mfma_frags_G(const RefElem& re);

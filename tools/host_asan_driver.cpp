@@ -196,6 +196,136 @@ static void trace_lines_3d(int degree) {
   }
 }
 
+// The class frame of the F stages (mfma_tables.cpp mfma_class_frame): p, s and the permuted (c n) rebuild the block's tables
+// exactly, every line offset is stress_line_slot of the permuted pair, the difference tiles are the E_m - E_(m-1) of the
+// operators, and tables of any other shape - one more non-zero, a J^-1 that is not the bidiagonal in the order p - are refused.
+static void class_frame_3d(int degree) {
+  RefElem re = make_refelem(3, degree, KIND_SIMPLEX);
+  const double hs[2][3] = {{0.3, 0.5, 0.7}, {2.0, 0.125, 0.75}};
+  auto refused = [](const MeshDev& m, int k) {
+    MfmaClassConst kc;
+    std::memset(&kc, 0, sizeof(kc));
+    try {
+      mfma_class_frame(m, k, kc);
+    } catch (const std::runtime_error&) {
+      return true;
+    }
+    return false;
+  };
+  double emax = 0.0;
+  for (int m = 0; m < 3; ++m)
+    for (int a = 0; a < re.nd; ++a)
+      for (int b = 0; b < re.nd; ++b) emax = std::fmax(emax, std::fabs(mfma_E(re, m, a, b)));
+  for (int m = 0; m < 3; ++m)
+    for (int a = 0; a < re.nd; a += 3)
+      for (int b = 0; b < re.nd; ++b) {
+        // (the tiles take the difference before rounding, this one after: at most two roundings in each E, one in the
+        // difference and one in E', each half an ulp of the largest entry at most)
+        const double e1 = mfma_E(re, m, a, b), e0 = m > 0 ? mfma_E(re, m - 1, a, b) : 0.0;
+        EXPECT(std::fabs(mfma_Ediff(re, m, a, b) - (e1 - e0)) <= 6 * 0x1p-53 * emax);
+      }
+  EXPECT(mfma_Ediff(re, 1, re.nd, 0) == 0.0 && mfma_Ediff(re, 1, 0, re.nd) == 0.0);
+  for (const auto& h : hs) {
+    MeshDev md;
+    std::memset(&md, 0, sizeof(md));
+    md.nd = re.nd;
+    md.nf = re.nf;
+    build_mesh_tables(3, degree, 0, h, re.fnode.data(), re.lattice.data(), md);
+    for (int k = 0; k < 6; ++k) {
+      MfmaClassConst kc;
+      std::memset(&kc, 0, sizeof(kc));
+      mfma_class_frame(md, k, kc);
+      const int* p = kc.cf_p;
+      EXPECT(p[0] >= 0 && p[0] < 3 && p[1] >= 0 && p[1] < 3 && p[2] >= 0 && p[2] < 3 && p[0] != p[1] && p[0] != p[2] && p[1] != p[2]);
+      double J[3][3] = {{0}}, cn[4][3] = {{0}};
+      for (int r = 0; r < 3; ++r) {
+        J[r][p[r]] = kc.cf_s[r];
+        if (r < 2) J[r][p[r + 1]] = -kc.cf_s[r + 1];
+      }
+      cn[0][p[0]] = kc.cf_cn[0][0];
+      cn[1][p[0]] = kc.cf_cn[1][0];
+      cn[1][p[1]] = kc.cf_cn[1][1];
+      cn[2][p[1]] = kc.cf_cn[2][0];
+      cn[2][p[2]] = kc.cf_cn[2][1];
+      cn[3][p[2]] = kc.cf_cn[3][0];
+      for (int r = 0; r < 3; ++r)
+        for (int j = 0; j < 3; ++j) EXPECT(J[r][j] == md.Jinv[k][r][j]);
+      for (int f = 0; f < 4; ++f)
+        for (int j = 0; j < 3; ++j) EXPECT(cn[f][j] == md.cn[k][f][j]);
+      EXPECT(kc.cf_cn[0][1] == 0.0 && kc.cf_cn[3][1] == 0.0);
+      for (int sym = 0; sym < 2; ++sym) {
+        for (int a = 0; a < 3; ++a) {
+          EXPECT(kc.cf_vel[a] == 16 * p[a]);
+          for (int b = 0; b < 3; ++b) EXPECT(kc.cf_own[sym][3 * a + b] == 16 * stress_line_slot(sym != 0, p[a], p[b]));
+        }
+        for (int f = 0; f < 4; ++f)
+          for (int c = 0; c < 6; ++c) EXPECT(kc.cf_tr[sym][f][c] >= 0 && kc.cf_tr[sym][f][c] < 9 * 16 && kc.cf_tr[sym][f][c] % 16 == 0);
+        // the flux from the listed lines alone is the flux over all three columns (the tensor not symmetric in full storage)
+        double slot[9];
+        for (int i = 0; i < 3; ++i)
+          for (int j = 0; j < 3; ++j) slot[i * 3 + j] = (!sym || i <= j) ? 1.0 + 0.37 * i - 0.61 * j + 0.05 * i * j : std::nan("");
+        for (int f = 0; f < 4; ++f)
+          for (int i = 0; i < 3; ++i) {      // row i of the frame = component p[i]
+            double full = 0.0, part;
+            for (int j = 0; j < 3; ++j) full = std::fma(md.cn[k][f][p[j]], slot[stress_line_slot(sym != 0, p[i], p[j])], full);
+            const int32_t* t = kc.cf_tr[sym][f];
+            if (f == 0 || f == 3) {
+              part = kc.cf_cn[f][0] * slot[t[i] / 16];
+            } else if (sym) {
+              const int x = f == 1 ? 0 : 2, a = i == x ? 0 : (i == 1 ? 1 : 3);
+              part = f == 1 ? std::fma(kc.cf_cn[f][1], slot[t[a + 1] / 16], kc.cf_cn[f][0] * slot[t[a] / 16])
+                            : std::fma(kc.cf_cn[f][1], slot[t[a] / 16], kc.cf_cn[f][0] * slot[t[a + 1] / 16]);
+            } else {
+              part = std::fma(kc.cf_cn[f][1], slot[t[3 + i] / 16], kc.cf_cn[f][0] * slot[t[i] / 16]);
+            }
+            EXPECT(full == part && std::isfinite(part));
+          }
+      }
+    }
+    // what the kernels could not run on
+    EXPECT(!refused(md, 0) && !refused(md, 5));
+    for (int k = 0; k < 6; ++k)
+      for (int r = 0; r < 3; ++r)
+        for (int j = 0; j < 3; ++j)
+          if (md.Jinv[k][r][j] == 0.0) {
+            MeshDev bad = md;
+            bad.Jinv[k][r][j] = 1e-300;                         // one more non-zero in J^-1, however small
+            EXPECT(refused(bad, k));
+          }
+    MeshDev bad = md;
+    bad.Jinv[1][0][md.nb_axis[1][0]] *= 1.0 + 1e-15;            // the entry above a diagonal one is no longer its negative ...
+    EXPECT(refused(bad, 1));
+    bad = md;
+    for (int j = 0; j < 3; ++j)
+      if (md.cn[3][1][j] == 0.0) bad.cn[3][1][j] = 1e-300;      // one more non-zero in a scaled normal
+    EXPECT(refused(bad, 3));
+    bad = md;
+    bad.cn[2][3][md.nb_axis[2][3]] *= 2.0;                      // a scaled normal that is not -1/2 grad lambda
+    EXPECT(refused(bad, 2));
+    bad = md;
+    std::swap(bad.Jinv[4][0], bad.Jinv[4][2]);                  // the bidiagonal upside down
+    EXPECT(refused(bad, 4));
+    bad = md;
+    bad.Jinv[0][2][md.nb_axis[0][3]] = -md.Jinv[0][2][md.nb_axis[0][3]];      // a negative scale
+    EXPECT(refused(bad, 0));
+    bad = md;
+    bad.Jinv[5][1][0] = std::nan("");
+    EXPECT(refused(bad, 5));
+    bad = md;
+    bad.nb_axis[2][0] = (md.nb_axis[2][0] + 1) % 3;             // facet 0 does not cross the face normal to p[0]
+    EXPECT(refused(bad, 2));
+    bool whole_refused = false;
+    bad = md;
+    bad.Jinv[3][2][(md.nb_axis[3][3] + 1) % 3] = 1e-300;
+    try {
+      (void)mfma_const(bad);
+    } catch (const std::runtime_error&) {
+      whole_refused = true;
+    }
+    EXPECT(whole_refused);
+  }
+}
+
 static void tile_tables_2d(int degree, int kind) {
   RefElem re = make_refelem(2, degree, kind);
   EXPECT(!tile2d_frags_V(re, 1.0).empty() && !tile2d_frags_V(re, -1.0).empty() && !tile2d_frags_L(re).empty());
@@ -1663,6 +1793,7 @@ int main() {
   for (int degree = 1; degree <= 4; ++degree) {
     mfma_tables_3d(degree);
     trace_lines_3d(degree);
+    class_frame_3d(degree);
     tile_tables_2d(degree, KIND_SIMPLEX);
     tile_tables_2d(degree, KIND_TENSOR);
   }
