@@ -399,6 +399,46 @@ int sg_set_receivers(sg_handle* h, int64_t nrec, const double* pts, int what, in
  * probe of every 5th VTU file (uy.py:36-43, vtktools.vtu.ProbeData). */
 int sg_get_receivers(sg_handle* h, double* out, size_t nbytes, int64_t* nsamples);
 
+/* ---- gauges: strain rate, rotation rate and dilatation rate recorded at physical points inside the time loop - what a
+ * strainmeter, a fibre (DAS) or a rotational seismometer delivers, beside the receivers' velocity seismograms -----------------
+ * A gauge is a physical point with a `kind`, sg_get_gradient_dev's: 0 gradient, 1 divergence, 2 curl, 3 symmetric strain rate,
+ * with that call's ncomp and component order; kind 2 in 1-D: SG_ERR_ARG.  Its value is the broken gradient of the velocity at
+ * the point: the gradient of the polynomial of the cell that holds it.
+ * The cell and xi of a point: sg_locate_points.  A block owns a gauge when the chosen cube (in the mesh's indices) lies in it:
+ * under any partition every point inside the mesh has exactly one owner, a point outside none.  The broken gradient is
+ * discontinuous across cells: on a grid line a gauge reads the LOWER cell's polynomial (the one-sided value from below), as a
+ * receiver reads the lower side.
+ * Arithmetic, for a gauge in a cell of class k, velocity component i:
+ *   D_r[a]  = d(phi_a)/d(xi_r) at xi            bitwise sg_tabulate_grad_cell(cell_type, dim, degree, 1, xi, .), dense over all
+ *                                               nd nodes for both cell types
+ *   t_r[i]  = sum_a D_r[a] * (double)u[a][i]    with fma from zero over a ascending
+ *   G_ij    = sum_r J[k][r][j] * t_r[i]         with fma from zero over r ascending; J is sg_gradient_tables' J
+ * and the combinations of kinds 1 to 3 are the gradient's: single additions, subtractions and one multiplication by 0.5, each
+ * rounded on its own in the order written there, the divergence as (G00 + G11) + G22.  FP32 blocks convert every nodal value
+ * first.  The bits therefore depend on the cell's nodal values, the point, the cell type, the degree, the class and h[] alone -
+ * not on the kernel family, the layout of the fields, the stream, graph replay or the partition.
+ * Series: a step is a completed LF4 step counted from the arming call - through sg_step (graph replay or eager, with or without
+ * a communicator) or through sg_end_step after host-driven stages.  Sample j (0-based) is taken of u1 after step (j+1)*every.
+ * Arm: npts points [npts][dim] (all of the mesh's gauges: each block keeps the ones it owns), owned[npts] out (0/1, may be
+ * NULL), every >= 1, capacity = samples the device buffer holds.  npts = 0 disarms; re-arming discards the old samples; a
+ * failed call leaves the previous gauges recording, samples intact.  sg_step(n) whose samples would exceed the capacity
+ * returns SG_ERR_STATE before it queues anything (fields, counters and trace untouched); sg_end_step of a step due a sample
+ * the trace has no room for returns SG_ERR_STATE and does not count the step.  No gauges armed: no extra launch, the same
+ * captured graphs. */
+int sg_set_gauges(sg_handle* h, int64_t npts, const double* pts, int kind, int64_t every, int64_t capacity, int32_t* owned);
+/* samples taken so far -> out[nsamples][npts][ncomp], rows of gauges this block does not own are 0.0; nbytes must be that of
+ * `capacity` samples; *nsamples = samples taken. */
+int sg_get_gauges(sg_handle* h, double* out, size_t nbytes, int64_t* nsamples);
+/* One shot: the same arithmetic on `field` (SG_FIELD_U or SG_FIELD_UH; a stress field: SG_ERR_ARG) as it stands behind
+ * everything the handle has queued, into host_out[npts][ncomp] (nbytes exactly that); rows not owned are 0.0; owned[npts] out
+ * (may be NULL).  Temporary device buffers and one blocking copy, as sg_get_gradient; it arms nothing, counts nothing, writes no
+ * field, and may be called between graph replays. */
+int sg_probe_gradient(sg_handle* h, int field, int kind, int64_t npts, const double* pts, double* host_out, size_t nbytes,
+                      int32_t* owned);
+/* device-free, like sg_injector_weights: cell[k] (or -1) and dphi[k][dim][nd] = D_r[a] of point k (0 where -1); degree <= 4.
+ * Returns nd, or SG_ERR_ARG. */
+int64_t sg_gauge_weights(const sg_config* cfg, int64_t npts, const double* pts, int64_t* cell, double* dphi);
+
 /* ---- injectors: force and stress series added at physical points inside the time loop - the driving side beside the
  * receivers, what puts a point force into the velocity equation or a data residual into an adjoint field ----------------
  * An injector is the transpose of a receiver.  Where the recorder forms sum_a phi_a(xi) field[cell][a][c], an injector adds

@@ -90,6 +90,10 @@ SYMBOLS = {
     "sg_set_receivers": (C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64, _P]),
     "sg_get_receivers": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_int64)]),
     "sg_injector_weights": (C.c_int, [C.POINTER(SgConfig), C.c_int64, _P, _P, _P]),
+    "sg_set_gauges": (C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int64, C.c_int64, _P]),
+    "sg_get_gauges": (C.c_int, [_P, _P, C.c_size_t, C.POINTER(C.c_int64)]),
+    "sg_probe_gradient": (C.c_int, [_P, C.c_int, C.c_int, C.c_int64, _P, _P, C.c_size_t, _P]),
+    "sg_gauge_weights": (C.c_int64, [C.POINTER(SgConfig), C.c_int64, _P, _P, _P]),
     "sg_inject": (C.c_int, [_P, C.c_int64, _P, C.c_int, _P]),
     "sg_set_injectors": (C.c_int, [_P, C.c_int64, _P, C.c_int, C.c_int64, _P, _P]),
     "sg_measure": (C.c_int, [_P, _P, C.c_int, _P]),

@@ -120,6 +120,19 @@ def gradient_tables(cfg):
     return Ct, J
 
 
+def gauge_weights(cfg, points, nd):
+    """(cell [npts], D [npts, dim, nd]) of the points [npts, dim] in the block `cfg` (an SgConfig) describes: the owning cell as
+    locate_points gives it and D[k, r, a] = d(phi_a)/d(xi_r) at the point - the dense rows of a gauge (sg_gauge_weights;
+    device-free); nd: scalar nodes per cell."""
+    pts = _f64(points).reshape(-1, cfg.dim)
+    cell = np.empty(len(pts), dtype=np.int64)
+    D = np.zeros((len(pts), cfg.dim, int(nd)))
+    got = _lib.load().sg_gauge_weights(C.byref(cfg), len(pts), pts.ctypes.data, cell.ctypes.data, D.ctypes.data)
+    if got != int(nd):
+        raise _lib.SeigenHipError("sg_gauge_weights returned %d, the cells have %d nodes" % (got, int(nd)))
+    return cell, D
+
+
 def mfma_class_frame(cfg, operators=False):
     """the class frame of the 3-D matrix-pipe F stages for the block `cfg` (an SgConfig) describes (sg_mfma_class_frame;
     device-free): p [6, 3], s [6, 3], cn [6, 4, 2], own [6, 2, 9], trace [6, 2, 4, 6], vel [6, 3] - line offsets in values of
@@ -539,6 +552,42 @@ class HipBlock(object):
         n = C.c_int64()
         check(self.lib.sg_get_receivers(self.h, out.ctypes.data, out.nbytes, C.byref(n)), self.h)
         return out[:n.value]
+
+    # ---- gauges (sg_set_gauges / sg_get_gauges / sg_probe_gradient) ------------------------------------
+    def gauge_shape(self, kind):
+        """the value shape of a gauge of `kind`, flat: (ncomp,)"""
+        return (int(np.prod(self.gradient_shape(kind, 0)[2:], dtype=np.int64)),)
+
+    def set_gauges(self, points, kind=3, every=1, capacity=0):
+        """Arm gauges at `points` [npts, dim] - all of the mesh's: the block records the ones it owns - sampling the broken
+        gradient of the velocity u1, or its divergence, curl or symmetric part (`kind` as get_gradient_dev's), after every
+        `every`-th step, room for `capacity` samples.  No points: disarm.  Returns owned [npts] (bool)."""
+        pts = _f64(points).reshape(-1, self.dim)
+        k = gradient_kind(kind) if len(pts) else 0
+        ncomp = self.gauge_shape(k)[0] if len(pts) else 0
+        owned = np.zeros(len(pts), dtype=np.int32)
+        check(self.lib.sg_set_gauges(self.h, len(pts), pts.ctypes.data, k, int(every), int(capacity), owned.ctypes.data), self.h)
+        self._gauge_shape = (int(capacity), len(pts), ncomp) if len(pts) else (0, 0, 0)
+        return owned.astype(bool)
+
+    def get_gauges(self):
+        """The samples taken so far, [n, npts, ncomp] in the component order of get_gradient_dev; rows of gauges the block does
+        not own are 0."""
+        out = np.zeros(getattr(self, "_gauge_shape", (0, 0, 0)))
+        n = C.c_int64()
+        check(self.lib.sg_get_gauges(self.h, out.ctypes.data, out.nbytes, C.byref(n)), self.h)
+        return out[:n.value]
+
+    def probe_gradient(self, field, kind, points):
+        """(values [npts, ncomp], owned [npts]): the gauges' arithmetic once, on `field` (FIELD_U, FIELD_UH) as it stands behind
+        everything queued; rows of points the block does not own are 0 (sg_probe_gradient)."""
+        pts = _f64(points).reshape(-1, self.dim)
+        k = gradient_kind(kind)
+        out = np.zeros((len(pts),) + self.gauge_shape(k))
+        owned = np.zeros(len(pts), dtype=np.int32)
+        check(self.lib.sg_probe_gradient(self.h, int(field), k, len(pts), pts.ctypes.data, out.ctypes.data, out.nbytes,
+                                         owned.ctypes.data), self.h)
+        return out, owned.astype(bool)
 
     # ---- monitor (sg_measure / sg_set_monitor / sg_get_monitor) ------------------------------------
     def _weights(self, w):

@@ -5,6 +5,7 @@
 //   frame.cpp    a field rastered on a cube-aligned pixel lattice into the caller's device buffer, queued on the stream
 //   grad.cpp     the broken gradient of a velocity field at the nodes into the caller's device buffer, queued on the stream
 //   peak.cpp     the peak maps: arming, the end-of-step launches, the read-outs through the host and on the stream
+//   gauge.cpp    the gauges: arming, the end-of-step launch, the read-out, the one-shot probe of the gradient at points
 //   stages.cpp   regions, stage launches, the LF4 step, graphs, halo packs, timing
 // and, without a device or a HIP header (the CPU sanitizer build, `make host-asan`):
 //   hostapi.cpp (hostlogic.hpp)  family choice, field layout, stage table, region boxes / items, point location, receiver and injector plans;
@@ -108,7 +109,7 @@ struct SourceTables {
   DevBuf<int32_t> slot, idx;
 };
 
-// What each of the five end-of-step hooks - receivers, monitor, spectra, peak maps, injectors (stages.cpp hooks) - keeps besides its
+// What each of the six end-of-step hooks - receivers, gauges, monitor, spectra, peak maps, injectors (stages.cpp hooks) - keeps besides its
 // tables.  ctr serves graph replay: it is the step index of the hook's launches in a capture - they read it (the kernels'
 // Args::ctr), a one-thread launch bumps it behind them, and sg_step sets it to clock.steps before it replays: the role of
 // sg_handle::src_ctr_d for the source.  A setter puts a zero there when it arms (arm_hook below).
@@ -129,6 +130,25 @@ struct ReceiverTables : StepSeries {   // clock.count: the capacity of the trace
   int what = 0;               // bit 0: velocity (dim values), bit 1: stress (dim x dim, row-major)
   int ncomp = 0;
   DevBuf<double> trace;       // [capacity][nown][ncomp]
+};
+
+// The gauges of sg_set_gauges (gauge.cpp, kernels_gauge.hip), on the device: the owned points' cells, classes and derivative rows
+// (hostlogic.hpp GaugePlan), the block's J, and the trace the kernel fills at the end of every `every`-th step
+struct GaugeTables : StepSeries {      // clock.count: the capacity of the trace
+  int64_t npts = 0;           // gauges armed (0: none; every block of a mesh is handed all of them)
+  int64_t nown = 0;           // ... of which this block owns these, in the order given
+  std::vector<int64_t> row;   // [nown] -> point index (the row of sg_get_gauges' output)
+  DevBuf<int64_t> item;       // [nown] item and
+  DevBuf<int32_t> lane;       // [nown] lane of the owning cell in the layout of the fields (hostlogic.hpp Layout)
+  DevBuf<int32_t> cls;        // [nown] its class
+  DevBuf<double> D;           // [nown][dim][nd] d(phi_a)/d(xi_r) at the point
+  DevBuf<double> J;           // [ncls][3][3] = MeshDev::Jinv
+  int kind = 0;               // sg_get_gradient_dev's: 0 gradient, 1 divergence, 2 curl, 3 symmetric strain rate
+  int ncomp = 0;
+  DevBuf<double> trace;       // [capacity][nown][ncomp]
+  // the hook's launch (gauge.cpp queue_gauges), set by the arming call: stages.cpp reaches the feature through the armed tables
+  // alone, as it reaches the peak maps
+  int (*queue)(sg_handle* h, hipStream_t stream, const int64_t* ctr, int64_t step) = nullptr;
 };
 
 // The injectors of sg_set_injectors (and, for the one launch, of sg_inject), on the device: the owned points grouped by cell
@@ -312,6 +332,7 @@ struct sg_handle {
   // Allocated by the first source and kept.
   DevBuf<int64_t> src_ctr_d;
   ReceiverTables rec;
+  GaugeTables gge;
   MonitorTables mon;
   MeasureScratch msr;
   InjectTables inj;

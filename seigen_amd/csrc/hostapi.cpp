@@ -281,6 +281,37 @@ ReceiverPlan plan_receivers(const NodeGeom& G, const Layout& L, int kind, int64_
   return pl;
 }
 
+void gauge_weights(int dim, int degree, int cell_kind, int nd, const double* xi, double* D) {
+  std::vector<double> dphi((size_t)nd * dim);
+  tabulate_grad(dim, degree, 1, xi, dphi.data(), cell_kind);
+  for (int r = 0; r < dim; ++r)
+    for (int a = 0; a < nd; ++a) D[(size_t)r * nd + a] = dphi[(size_t)a * dim + r];
+}
+
+GaugePlan plan_gauges(const NodeGeom& G, const Layout& L, int cell_kind, int64_t npts, const double* pts, int kind, int64_t capacity) {
+  const int d = G.d;
+  GaugePlan pl;
+  pl.own.assign((size_t)npts, 0);
+  pl.ncomp = grad_ncomp(d, kind);
+  const size_t per = (size_t)d * (size_t)L.nd;
+  for (int64_t k = 0; k < npts; ++k) {
+    double xi[3] = {0, 0, 0};
+    const int64_t cell = locate_point(G, pts + k * d, xi);
+    if (cell < 0) continue;
+    const int64_t cube = cell / L.ncls, cls = cell % L.ncls;
+    pl.own[(size_t)k] = 1;
+    pl.row.push_back(k);
+    pl.item.push_back(L.item(cube, cls));
+    pl.lane.push_back((int32_t)L.lane(cube));
+    pl.cls.push_back((int32_t)cls);
+    pl.D.resize(pl.D.size() + per);
+    gauge_weights(d, G.degree, cell_kind, (int)L.nd, xi, pl.D.data() + pl.D.size() - per);
+  }
+  const int64_t nown = (int64_t)pl.row.size();
+  if (nown > 0 && pl.ncomp > 0 && capacity > ((int64_t)1 << 40) / (nown * pl.ncomp)) throw std::invalid_argument("capacity too large");
+  return pl;
+}
+
 void injector_weights(const RefElem& re, int degree, double detj, const double* xi, double* psi) {
   std::vector<double> phi((size_t)re.nd);
   tabulate(re.dim, degree, 1, xi, phi.data(), re.kind);
@@ -661,6 +692,27 @@ int sg_injector_weights(const sg_config* cfg, int64_t npts, const double* pts, i
     return SG_ERR_ARG;
   }
   return SG_OK;
+}
+
+int64_t sg_gauge_weights(const sg_config* cfg, int64_t npts, const double* pts, int64_t* cell, double* dphi) {
+  if (!cfg || npts < 0 || (npts > 0 && (!pts || !cell || !dphi))) return SG_ERR_ARG;
+  if (cfg->dim < 1 || cfg->dim > 3 || cfg->degree < 1 || cfg->degree > 4) return SG_ERR_ARG;
+  for (int a = 0; a < cfg->dim; ++a)
+    if (cfg->n[a] < 1 || !(cfg->h[a] > 0.0)) return SG_ERR_ARG;
+  NodeGeom G;
+  if (!G.init(cfg, cfg->degree)) return SG_ERR_ARG;
+  const int d = cfg->dim, kind = cfg->diagonal == SG_DIAGONAL_QUAD ? KIND_TENSOR : KIND_SIMPLEX;
+  const int nd = G.nq;
+  for (int64_t k = 0; k < npts; ++k) {
+    double xi[3] = {0, 0, 0};
+    double* const D = dphi + (size_t)k * d * nd;
+    cell[k] = locate_point(G, pts + k * d, xi);
+    if (cell[k] >= 0)
+      gauge_weights(d, cfg->degree, kind, nd, xi, D);
+    else
+      for (int a = 0; a < d * nd; ++a) D[a] = 0.0;
+  }
+  return nd;
 }
 
 int sg_locate_points(const sg_config* cfg, int64_t npts, const double* pts, int64_t* cell, double* xi) {

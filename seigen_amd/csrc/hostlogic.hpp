@@ -1,6 +1,6 @@
 // Host logic of libseigen_hip that needs no device and no HIP header: which kernel family runs a block, the layout of its
 // fields, the six stages of an LF4 step, the boxes and items of the regions of a split stage, node coordinates of a block,
-// point location, the receiver plan, the injector plan, the transfer plan and the frame plan.  Defined in hostapi.cpp, which - with refelem.cpp, mesh_tables.cpp, mfma_tables.cpp,
+// point location, the receiver plan, the gauge plan, the injector plan, the transfer plan and the frame plan.  Defined in hostapi.cpp, which - with refelem.cpp, mesh_tables.cpp, mfma_tables.cpp,
 // sponge_tables.cpp and source_tables.cpp - also builds on its own for the CPU sanitizer target (`make host-asan`).
 #pragma once
 #include <algorithm>
@@ -348,6 +348,25 @@ struct ReceiverPlan {
   int ncomp = 0;               // what bit 0: velocity (dim values), bit 1: stress (dim x dim)
 };
 ReceiverPlan plan_receivers(const NodeGeom& G, const Layout& L, int kind, int64_t nrec, const double* pts, int what, int64_t capacity);
+
+// The gauges (seigen_hip.h sg_set_gauges / sg_probe_gradient; kernels_gauge.hip): the broken gradient of the velocity at physical
+// points.  D[r][a] = d(phi_a)/d(xi_r) at the point's reference coordinates, dense over all nd nodes for both cell kinds: bitwise
+// refelem.hpp tabulate_grad of the one point, transposed to rows the kernel's chain walks.
+void gauge_weights(int dim, int degree, int cell_kind, int nd, const double* xi, double* D);
+// What sg_set_gauges and sg_probe_gradient derive from the points: of the npts points pts[npts][dim] the ones this block owns
+// (locate_point: the receivers' rule; on a grid line the lower cell), in the order given - their row of the output, the item and
+// lane of the owning cell (Layout), the cell's class and D.  ncomp = grad_ncomp(dim, kind).  Throws std::invalid_argument where
+// capacity x owned x ncomp values of trace are more than 2^40.
+struct GaugePlan {
+  std::vector<int32_t> own;    // [npts]
+  std::vector<int64_t> row;    // [nown] -> point index
+  std::vector<int64_t> item;   // [nown]
+  std::vector<int32_t> lane;   // [nown]
+  std::vector<int32_t> cls;    // [nown]
+  std::vector<double> D;       // [nown][dim][nd]
+  int ncomp = 0;
+};
+GaugePlan plan_gauges(const NodeGeom& G, const Layout& L, int cell_kind, int64_t npts, const double* pts, int kind, int64_t capacity);
 
 // The injectors (seigen_hip.h sg_inject / sg_set_injectors): the transpose of the receivers.  Where the recorder forms
 // sum_a phi_a(xi) field[cell][a][c], an injector adds amp * psi_a to the same cell, psi = Mhat^-1 phi(xi) / |det J| - the L2

@@ -518,4 +518,32 @@ struct GradArgs {
 int launch_grad(const void* field, void* out, const double* C, const double* J, const GradArgs& a, int f32, int c32, int grid,
                 size_t lds_bytes, void* stream);
 
+// Gauges (kernels_gauge.hip; seigen_hip.h sg_set_gauges / sg_probe_gradient): the kind's ncomp values of the broken gradient of
+// the velocity buffer `field` (float where f32) at the owned points.  After step s (counted from the arming call; s from
+// *ctr + 1 under graph replay) with s % every == 0 and j = s / every - 1 < capacity, for gauge g in the cell of class cls[g]:
+//   t_r[i] = sum_a D[g][r][a] * (double)field[((item[g] * nd + a) * dim + i) * gw + lane[g]]   fma from zero over a ascending
+//   G_ij   = sum_r J[cls[g]][r][j] * t_r[i]                                                    fma from zero over r ascending
+// and out[j][g][c] the kind's combination (kernels_grad.hip combine: the same operations in the same order).  A one-shot names
+// ctr = null, step = every = capacity = 1.
+namespace gauge {
+constexpr int MAX_VALUES = 375;   // nd * dim of the largest element (125 nodes, 3 components): a wave's LDS slab
+constexpr int GRID_CAP = 1024;    // blocks of four waves; the grid strides over the gauges beyond it
+struct Args {
+  const int64_t* ctr;      // graph replay: *ctr + 1 is the step that just ended; null: `step`
+  int64_t step;
+  int64_t every, capacity; // (a sample index beyond the capacity is not written)
+  const int64_t* item;     // [nown]
+  const int32_t* lane;     // [nown]
+  const int32_t* cls;      // [nown]
+  const double* D;         // [nown][dim][nd]
+  const double* J;         // [ncls][3][3]
+  double* out;             // [capacity][nown][ncomp]
+  int64_t nown;
+  int32_t ncomp, kind;
+  int32_t dim, nd, gw, pad_;
+};
+}  // namespace gauge
+int launch_gauges(const void* field, const gauge::Args& a, int f32, void* stream);
+
+
 }  // namespace sg

@@ -512,8 +512,8 @@ static int queue_spectra(sg_handle* h, hipStream_t stream, const int64_t* ctr, i
 }
 
 // What runs at the end of every step, on the main stream behind stage S1's SECOND launch, as values: the hooks in the order
-// they run.  The receivers' recorder and the monitor sample u1 and s1 of the step that just ended, and so do the spectra and the
-// peak maps (peak.cpp) - before the injectors add the entry that belongs to the step that follows.  All five keep one protocol
+// they run.  The receivers' recorder, the gauges (gauge.cpp) and the monitor sample u1 and s1 of the step that just ended, and so
+// do the spectra and the peak maps (peak.cpp) - before the injectors add the entry that belongs to the step that follows.  All six keep one protocol
 // (hook_step, and the callers that walk this table); they differ in what stands here.
 struct Hook {
   StepSeries* series;   // the clock and the device-side step counter
@@ -527,9 +527,10 @@ struct Hook {
   int (*queue)(sg_handle* h, hipStream_t stream, const int64_t* ctr, int64_t step);   // the step by value, or *ctr + 1
   uint32_t bit;         // in sg_handle::in_graphs
 };
-using Hooks = std::array<Hook, 5>;
+using Hooks = std::array<Hook, 6>;
 static Hooks hooks(sg_handle* h) {
   return {{{&h->rec, h->rec.nrec > 0, h->rec.nown > 0, true, "receiver", "sg_get_receivers", queue_receivers, 2u << 0},
+           {&h->gge, h->gge.npts > 0, h->gge.nown > 0, true, "gauge", "sg_get_gauges", h->gge.queue, 2u << 5},
            {&h->mon, h->mon.armed, true, true, "monitor", "sg_get_monitor", queue_monitor, 2u << 1},
            {&h->spc, h->spc.nfreq > 0, true, false, "", "", queue_spectra, 2u << 2},
            {&h->pk, h->pk.what != 0, true, false, "", "", h->pk.queue, 2u << 4},

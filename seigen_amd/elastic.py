@@ -103,6 +103,29 @@ def _device_for_rank():
     return 0
 
 
+def fibre_points(dim, p0, p1, nchannels, gauge_length, nq=4):
+    """(points [nchannels * nq, dim], unit tangent [dim], weights [nq]) of a straight fibre from p0 to p1: `nchannels` channel
+    centres at equal spacing (the first at p0, the last at p1; one channel: the midpoint), per channel the `nq` Gauss-Legendre
+    points of the gauge length about its centre; the weights sum to one (an average)."""
+    p0 = np.asarray(p0, dtype=np.float64).reshape(dim)
+    p1 = np.asarray(p1, dtype=np.float64).reshape(dim)
+    length = float(np.linalg.norm(p1 - p0))
+    if not length > 0.0 or int(nchannels) < 1 or int(nq) < 1 or not float(gauge_length) >= 0.0:
+        raise ValueError("a fibre needs p0 != p1, nchannels >= 1, nq >= 1 and gauge_length >= 0")
+    t = (p1 - p0) / length
+    x, w = np.polynomial.legendre.leggauss(int(nq))
+    centres = np.array([0.5]) if int(nchannels) == 1 else np.linspace(0.0, 1.0, int(nchannels))
+    s = centres[:, None] * length + 0.5 * float(gauge_length) * x[None, :]
+    return (p0[None, None, :] + s[:, :, None] * t[None, None, :]).reshape(-1, dim), t, 0.5 * w
+
+
+def fibre_combine(t, w, nchannels, nq, eps):
+    """the channels' axial strain rate [n, nchannels] from the strain-rate traces eps [n, nchannels * nq, dim, dim] at
+    fibre_points: t . eps . t at every point, averaged with the weights over each channel's points"""
+    axial = np.einsum("i,npij,j->np", t, eps, t).reshape(eps.shape[0], int(nchannels), int(nq))
+    return axial @ w
+
+
 class ElasticLF4(object):
     r"""Elastic wave equation, DG in space, fourth-order leap-frog in time.
     Create with ``ElasticLF4.create(mesh, family, degree, dimension, solver)``."""
@@ -189,6 +212,9 @@ class ElasticLF4(object):
             self._step_index = 0
             self._receivers = None          # (points, every, what) of set_receivers
             self._receiver_times = []
+            self._gauges = None             # (points, every, kind, capacity) of set_gauges
+            self._gauge_times = []
+            self._fibre = None              # (tangent, weights, nchannels, nq) of set_fibre
             self._monitor = None            # `every` of set_monitor
             self._monitor_times = []
             self._spectra = None            # (freqs, every, nsamples, what, window) of set_spectra
@@ -552,6 +578,71 @@ class ElasticLF4(object):
         pts, every, what = self._receivers
         self._block.set_receivers(pts, what, every, len(times) // every)
         self._receiver_times = list(times[every - 1::every])
+
+    # ---- gauges: strain rate, rotation rate, dilatation rate at points (sg_set_gauges) -----------------
+    _GAUGE_KINDS = {"gradient": 0, "dilatation": 1, "rotation": 2, "strain_rate": 3}
+
+    def set_gauges(self, points, kind="strain_rate", every=1, capacity=None):
+        """Record the velocity's `kind` - "strain_rate" (symmetric part of the gradient), "gradient", "dilatation" (divergence)
+        or "rotation" (curl) - at the physical `points` [R, dim] after every `every`-th step of the next runs, on the device
+        inside the time loop (sg_set_gauges): what a strainmeter, a fibre or a rotational seismometer delivers.  The value is
+        that of the polynomial of the cell holding the point, on a grid line the lower cell's.  `capacity`: the samples
+        the device buffer holds (default: those of the run).  Collective with more than one rank: every point must have
+        exactly one owning block (ValueError naming the first that has not)."""
+        if kind not in self._GAUGE_KINDS:
+            raise ValueError("gauge kinds are %s, not %r" % (", ".join(repr(k) for k in self._GAUGE_KINDS), kind))
+        if kind == "rotation" and self.dimension == 1:
+            raise ValueError("no rotation in one dimension")
+        if int(every) < 1 or (capacity is not None and int(capacity) < 0):
+            raise ValueError("set_gauges needs every >= 1 and capacity >= 0")
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, self.dimension)
+        from .backend import locate_points
+        from .functionspace import block_config
+        cell, _ = locate_points(block_config(self.mesh, self.degree), pts)
+        owners = allreduce_sum_array((cell >= 0).astype(np.float64))
+        for k in range(len(pts)):
+            if owners[k] != 1:
+                raise ValueError("gauge %d at %r has %d owning blocks, not one (outside the mesh?)"
+                                 % (k, tuple(pts[k]), int(owners[k])))
+        self._gauges = (pts, int(every), self._GAUGE_KINDS[kind], None if capacity is None else int(capacity))
+        self._fibre = None
+
+    def gauge_traces(self):
+        """(times [n], values [n, R] + the kind's value shape) of the gauges of the last run: sample j after step
+        (j + 1) * every, at t = times[j]; "strain_rate" and "gradient": (dim, dim) with [i, j] = d u_i / d x_j, "dilatation": (),
+        "rotation": (3,) in 3-D, () in 2-D."""
+        if self._gauges is None:
+            raise RuntimeError("no gauges: call set_gauges before run")
+        pts, every, kind, capacity = self._gauges
+        d = self.dimension
+        tr = allreduce_sum_array(self._block.get_gauges())        # rows of the other blocks' gauges are 0 here
+        n = tr.shape[0]
+        value = {0: (d, d), 1: (), 2: (3,) if d == 3 else (), 3: (d, d)}[kind]
+        return np.array(self._gauge_times[:n]), tr.reshape((n, len(pts)) + value)
+
+    def _arm_gauges(self, times):
+        if self._gauges is None:
+            return
+        pts, every, kind, capacity = self._gauges
+        self._block.set_gauges(pts, kind, every, len(times) // every if capacity is None else capacity)
+        self._gauge_times = list(times[every - 1::every])
+
+    def set_fibre(self, p0, p1, nchannels, gauge_length, nq=4, every=1):
+        """A straight fibre from `p0` to `p1` with `nchannels` channels at equal spacing (the first at p0, the last at p1; one
+        channel: the midpoint).  Channel c records the axial strain rate t . eps . t, t the unit tangent, averaged over its
+        gauge length by `nq` Gauss-Legendre points: strain-rate gauges (set_gauges) at those points, combined from their
+        traces on the host (fibre_traces).  Replaces the gauges armed before."""
+        pts, t, w = fibre_points(self.dimension, p0, p1, nchannels, gauge_length, nq)
+        self.set_gauges(pts, "strain_rate", every)
+        self._fibre = (t, w, int(nchannels), int(nq))
+
+    def fibre_traces(self):
+        """(times [n], axial strain rate [n, nchannels]) of the fibre of the last run"""
+        if self._fibre is None:
+            raise RuntimeError("no fibre: call set_fibre before run")
+        t, w, nchannels, nq = self._fibre
+        times, eps = self.gauge_traces()
+        return times, fibre_combine(t, w, nchannels, nq, eps)
 
     # ---- injectors: force and stress series at points (sg_inject / sg_set_injectors) -----------------
     _INJECT_WHAT = {"velocity": 1, "stress": 2}
@@ -929,6 +1020,7 @@ class ElasticLF4(object):
                 self.upload_source(times)
             self._agree_on_stress_storage()
             self._arm_receivers(times)
+            self._arm_gauges(times)
             self._arm_monitor(times)
             self._arm_spectra(times)
             self._arm_peaks(times)

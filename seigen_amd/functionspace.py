@@ -267,6 +267,17 @@ class Function(object):
             raise ValueError("gradient is taken of a velocity Function that has a device field (u0 / u1, uh1 / utemp), not of a stress")
         return block.get_gradient_dev(field, kind, out=out, dtype=dtype)
 
+    def gradient_at(self, points, kind="grad"):
+        """The cell-local gradient of a velocity Function at the physical `points` [R, dim], as a numpy array [R] + the kind's
+        value shape (gradient's kinds): the derivative of the polynomial of the cell that holds each point, on a grid line
+        the lower cell's; one launch behind everything queued and one blocking copy (HipBlock.probe_gradient).  Rows of
+        points this block does not own (another block's, or outside the mesh) are 0: returns (values, owned [R])."""
+        block, field = self._bound("gradient_at")
+        if field not in (_lib.FIELD_U, _lib.FIELD_UH):
+            raise ValueError("gradient_at is taken of a velocity Function that has a device field (u0 / u1, uh1 / utemp), not of a stress")
+        values, owned = block.probe_gradient(field, kind, points)
+        return values.reshape((len(values),) + tuple(block.gradient_shape(kind, 0)[2:])), owned
+
     def from_torch(self, t):
         """Set the values from a contiguous float64 or float32 tensor [cells, nodes] + value_shape of the solver's device,
         moved on the device (a stress handed to a block in symmetric storage makes the host wait once)."""

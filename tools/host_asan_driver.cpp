@@ -911,7 +911,7 @@ static void box_ricker(int dim, int diagonal, int degree) {
   EXPECT(ricker_weights(a, t0, tf, dts, 0).empty());
 }
 
-// sg_set_receivers' host half (hostapi.cpp plan_receivers) on the split of point_location(): the rows are the points that
+// sg_set_receivers' and sg_set_gauges' host halves (hostapi.cpp plan_receivers, plan_gauges) on the split of point_location(): the rows are the points that
 // locate_point gives the block, in order; item and lane are the owning cell's in every layout; phi is the basis at the point
 static void receiver_plans(int dim, int diagonal, int degree) {
   const int kind = diagonal == SG_DIAGONAL_QUAD ? KIND_TENSOR : KIND_SIMPLEX, nd = num_nodes(dim, degree, kind), ncls = classes_of(dim, kind);
@@ -977,7 +977,46 @@ static void receiver_plans(int dim, int diagonal, int degree) {
         // a trace of more than 2^40 values is refused - where the block owns a receiver at all
         EXPECT(throws_invalid([&] { plan_receivers(G, Layout{gw, ncls, nd}, kind, np, pts.data(), what, ((int64_t)1 << 40) + 1); }) == !pl.row.empty());
       }
+    // sg_set_gauges' host half (hostapi.cpp plan_gauges) on the same points: the same rows, items and lanes, the cell's class,
+    // and D = sg_gauge_weights' rows = the tabulated derivative at the point, transposed
+    std::vector<int64_t> gcell(np);
+    std::vector<double> gD((size_t)np * dim * nd);
+    EXPECT(sg_gauge_weights(&blk, np, pts.data(), gcell.data(), gD.data()) == nd);
+    for (int gw : {1, 16, 64})
+      for (int gkind = 0; gkind < 4; ++gkind) {
+        if (grad_ncomp(dim, gkind) == 0) continue;
+        const NaiveLayout NL(gw, ncls, nd, 1, ncube);
+        const GaugePlan pl = plan_gauges(G, Layout{gw, ncls, nd}, kind, np, pts.data(), gkind, 7);
+        EXPECT(pl.ncomp == grad_ncomp(dim, gkind));
+        EXPECT((int64_t)pl.own.size() == np && pl.item.size() == pl.row.size() && pl.lane.size() == pl.row.size() &&
+               pl.cls.size() == pl.row.size() && pl.D.size() == pl.row.size() * dim * nd);
+        size_t r = 0;
+        for (int64_t k = 0; k < np && (int64_t)pl.own.size() == np; ++k) {
+          EXPECT((pl.own[(size_t)k] != 0) == (cell[(size_t)k] >= 0) && gcell[(size_t)k] == cell[(size_t)k]);
+          if (cell[(size_t)k] < 0) continue;
+          EXPECT(r < pl.row.size() && pl.row[r] == k);
+          if (r >= pl.row.size() || pl.D.size() != pl.row.size() * dim * nd) break;
+          EXPECT(pl.item[r] == NL.item[(size_t)cell[(size_t)k]] && pl.lane[r] == NL.lane[(size_t)cell[(size_t)k]]);
+          EXPECT(pl.cls[r] == (int32_t)(cell[(size_t)k] % ncls));
+          std::vector<double> dphi((size_t)nd * dim);
+          EXPECT(sg_tabulate_grad_cell(kind, dim, degree, 1, &xi[(size_t)k * dim], dphi.data()) == SG_OK);
+          for (int rr = 0; rr < dim; ++rr) {
+            double sum = 0.0;
+            for (int a = 0; a < nd; ++a) {
+              EXPECT(pl.D[(r * dim + rr) * nd + a] == dphi[(size_t)a * dim + rr]);
+              EXPECT(gD[((size_t)k * dim + rr) * nd + a] == dphi[(size_t)a * dim + rr]);
+              sum += dphi[(size_t)a * dim + rr];
+            }
+            EXPECT(std::fabs(sum) < 1e-9);     // the derivative of a partition of unity
+          }
+          r += 1;
+        }
+        EXPECT(r == pl.row.size());
+        EXPECT(throws_invalid([&] { plan_gauges(G, Layout{gw, ncls, nd}, kind, np, pts.data(), gkind, ((int64_t)1 << 40) + 1); }) == !pl.row.empty());
+      }
     const double far[3] = {-5.0, -5.0, -5.0};
+    EXPECT(plan_gauges(G, Layout{16, ncls, nd}, kind, 1, far, 3, ((int64_t)1 << 40) + 1).row.empty());
+    EXPECT(plan_gauges(G, Layout{16, ncls, nd}, kind, 0, nullptr, 3, 0).own.empty());
     EXPECT(plan_receivers(G, Layout{16, ncls, nd}, kind, 1, far, 3, ((int64_t)1 << 40) + 1).row.empty());
     EXPECT(plan_receivers(G, Layout{16, ncls, nd}, kind, 0, nullptr, 3, 0).own.empty());
   }
