@@ -43,8 +43,13 @@ Tolerances are the suite's own: FP64 tol_of() per application and 10 tol_of() fo
 (test_monitor_gpu.py, test_correlate_gpu.py); receivers 1e-14 (FP32 1e-6) against the host evaluation of the downloaded
 fields (test_receivers_gpu.py) and the step's tolerance against the oracle's.
 
-Not covered: the generic kernels and the simplex lane kernels, which choose_kernel_path never picks at these sizes, and 1-D
-blocks.  A row needs its four fields (and the second handle's) on the device and skips, with both numbers, where less than
+The step-end hooks and the device read-outs that came later - injectors, spectra, device transfers, frames, peak maps,
+gradient, gauges - run on the same rows, plans and windows in tests/test_large_offsets_hooks_gpu.py, against the restatements
+of their own modules; its docstring has the parts, the yardsticks and the memory of a row.
+
+Not covered: the generic kernels (gw = 1: the stage kernels and the `flat` kernels of xfer, frame and grad) and the simplex
+lane kernels, which choose_kernel_path never picks at these sizes, and 1-D blocks.  A row needs its four fields (and the
+second handle's) on the device and skips, with both numbers, where less than
 1.2 times that is free."""
 import ctypes as C
 

@@ -195,3 +195,99 @@ def test_reach_in_two_dimensions():
             nz = np.flatnonzero(np.abs(a.reshape(Z, -1)).max(axis=1) > 0)
             reach = max(reach, k0 - nz.min(), nz.max() - k0)
         assert reach <= want < lo.Shape(2, cell, 2).margin, (cell, reach)
+
+
+# ---- what tests/test_large_offsets_hooks_gpu.py rests on ---------------------------------------------------------------------
+from tests import test_large_offsets_hooks_gpu as hk  # noqa: E402
+
+
+@pytest.mark.parametrize("dim,cell,P", [(2, "left", 1), (3, "left", 1), (2, _Q, 1), (3, _Q, 1)])
+def test_reach_of_two_whole_steps_from_three_data_layers(dim, cell, P):
+    """R = hk.step_reach(): two whole steps of OracleLF4 from data in three layers leave every field of every stage exactly zero
+    outside 3 + 2 * 2 * R layers, and u1 or s1 nonzero in the outermost layer inside, on both sides - degree 1 shows it"""
+    sh = lo.Shape(dim, cell, P)
+    R = hk.step_reach(sh)
+    assert R == (6 if cell == _Q else (3 if dim == 2 else 2)) and hk.K == 2
+    reach = hk.K * R
+    Z = lo.DATA + 2 * reach + 6
+    k0 = reach + 3
+    m = omesh.structured(dim, sh.n(Z), tuple(sh.h[a] * k for a, k in enumerate(sh.n(Z))), "left", quadrilateral=sh.tensor)
+    orc = OracleLF4(m, P)
+    per = m.ncells // Z
+    assert per == sh.per
+    rng = np.random.default_rng(3)
+    sl = slice(k0 * per, (k0 + lo.DATA) * per)
+    orc.u0[sl] = rng.uniform(-1, 1, orc.u0[sl].shape)
+    s = rng.uniform(-1, 1, orc.s0[sl].shape)
+    orc.s0[sl] = 0.5 * (s + np.swapaxes(s, -1, -2))
+    orc.dt, orc.l, orc.mu = 0.04 * min(sh.h) / P ** 2, 0.5, 0.25
+    seen = []
+    for step in range(hk.K):
+        orc.step((step + 1) * orc.dt)
+        seen += [np.abs(a.reshape(Z, -1)).max(axis=1) for a in list(orc.last.values()) + [orc.u1, orc.s1]]
+    rows = np.max(seen, axis=0)
+    assert not rows[:k0 - reach].any() and not rows[k0 + lo.DATA + reach:].any(), np.flatnonzero(rows)
+    state = np.maximum(np.abs(orc.u1.reshape(Z, -1)).max(axis=1), np.abs(orc.s1.reshape(Z, -1)).max(axis=1))
+    assert state[k0 - reach] > 0 and state[k0 + lo.DATA + reach - 1] > 0, np.flatnonzero(state)
+
+
+@pytest.mark.parametrize("row", hk.ROWS, ids=[r.name for r in hk.ROWS])
+def test_hook_window_plans_are_not_vacuous(row):
+    """every mark window's hook window keeps its K R layers on both sides and holds lines on both sides of its mark; the hook
+    windows are disjoint and ascending (the top window's alone may start where the one below ends); the accumulator of the last
+    part lies past 2^32 bytes (tier B: past 2^31 elements) at every window; the caller's side of the whole-field transfer and
+    of the whole-block gradient passes the marks the GPU module's docstring claims; the memory figures of that docstring"""
+    sh = row.sh
+    Z, wins = lo.plan(sh, row.tier, row.ghost)
+    hws = hk.hook_windows(sh, Z, wins)
+    reach = hk.K * hk.step_reach(sh)
+    assert [hw.w for hw in hws] == wins
+    for a, b in zip(hws, hws[1:]):
+        assert a.k1 <= b.k0
+    for hw in hws[:-1]:
+        assert hw.k0 == hw.d0 - reach and hw.k1 == hw.d0 + lo.DATA + reach and hw.k0 >= 0 and hw.k1 <= Z
+        field, unit, value = hw.w.mark
+        ncomp, mark = sh.ncomp(field), lo.mark_elements(sh, unit, value)
+        cube = lo.first_cube_past(sh, ncomp, mark)
+        assert cube // sh.cubes_per_layer == hw.d0 + 1                  # the middle data layer
+        c0, c1 = hw.k0 * sh.cubes_per_layer, hw.k1 * sh.cubes_per_layer - 1
+        assert lo.device_offset(sh, ncomp, c0, 0, 0, 0) < mark <= lo.device_offset(sh, ncomp, c1, sh.ncls - 1, sh.nd - 1, ncomp - 1)
+    top = hws[-1]
+    assert top.k1 == Z and top.d0 + lo.DATA == Z and top.k0 <= top.d0 - hk.step_reach(sh)
+    assert top.k0 == max(top.d0 - reach, hws[-2].k1)
+    # the ranges that must stay initial lie outside every hook window and cover the cells 2^32 bytes below the first one
+    outside = hk.complement(hws, Z * sh.per)
+    named = hk.elsewhere_outside(sh, wins, hws)
+    assert named and all(any(a >= c and b <= d for c, d in outside) for a, b in named)
+    assert sum(b - a for a, b in outside) + sum(hw.ncells for hw in hws) == Z * sh.per
+    # spectra: accumulator (2 f + part) n + idx, n the field's padded word count, in doubles
+    fset, nfreq = hk.spectra_shape(row)
+    ncube_pad = -(-Z * sh.cubes_per_layer // sh.gw) * sh.gw
+    for k in fset:
+        ncomp = sh.ncomp("US"[k])
+        n = ncube_pad * sh.ncls * sh.nd * ncomp
+        for hw in hws[:-1]:
+            first = (2 * nfreq - 1) * n + lo.device_offset(sh, ncomp, hw.k0 * sh.cubes_per_layer // sh.gw * sh.gw, 0, 0, 0)
+            assert first * 8 > lo.BYTES_2_32
+            if row.tier == "B":
+                assert first > lo.ELEMS_2_31
+    # the caller's side, buf + rel * rows: the stress window's first cell against the marks
+    s_windows = [hw for hw in hws[:-1] if hw.w.mark[0] == "S"]
+    assert s_windows
+    row_values = sh.nd * sh.ncomp("S")
+    last = s_windows[-1]
+    if row.tier in hk.WHOLE_FIELD or row.name in hk.WHOLE_FIELD:
+        out_bytes = 4 if sh.dtype == "f32" else 8                       # the whole-field transfer: the block's own type
+        assert (last.cell0 + last.ncells) * row_values * out_bytes > lo.BYTES_2_32
+    grad_words = (last.cell0 + last.ncells) * row_values                # the whole-block gradient in float32: dim * dim values a node
+    if sh.dtype == "f32":
+        assert grad_words * 4 > lo.BYTES_2_32
+    if row.tier == "B":
+        assert last.cell0 * row_values < lo.ELEMS_2_31 < grad_words     # lines on both sides of 2^31 elements
+    if row.name == hk.STRIDED:
+        assert Z * sh.cubes_per_layer <= hk.STRIDE_J and 8 * hk.STRIDE_J == lo.ELEMS_2_31
+    need = hk.need(row, Z)
+    quoted = {"A-tets-P4": 40.1, "A-tets-P4-full": 40.1, "A-tets-P4-f32": 68.7, "A-hexlane-DQ2": 40.1, "A-tri-P4-f32": 79.5,
+              "B-tets-P4": 103.1, "B-tets-P4-f32": 80.2}
+    print("%s needs %.1f GB: %r" % (row.name, need["total"] / 1e9, {k: round(v / 1e9, 1) for k, v in need.items()}))
+    assert abs(need["total"] / 1e9 - quoted[row.name]) < 0.1, need
